@@ -9,7 +9,15 @@ Deconvolver.create_data_from_object + 20 x Deconvolver.iterate of the reference
 resident in HBM when the timed region starts; nothing crosses PCIe inside it.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype f32|f64] [--size 512|2048]
-                    [--workload headline|fig2sweep]
+                    [--workload headline|fig2sweep] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = milliseconds per timed step, ...).  --dump-outputs DIR also writes what the last timed step computed:
+DIR/estimate.npy and DIR/measurement.npy, the same seeded sample of frames from both (all frames while they fit in
+48 MiB; a frame too large for that is sampled by pixel), float32 from an f32 plan, float64 from an f64 plan; with the
+same arguments the inputs are the same in every run.  --full adds everything else the line used to carry: the
+roofline (in-situ kernel timings of one more cycle), the accuracy against the float64 oracle, the CPU baseline, the
+extra legs below and, at N > 1, the sweep.
 
 --gpus N > 1 without a launcher: this process starts `python -m torch.distributed.run
 --nproc-per-node N` on itself (before anything touches the GPU) and relays the ranks' one JSON
@@ -19,10 +27,10 @@ over ranks counts, and ONE gather of the final estimates over RCCL / xGMI follow
 The barrier, the reduction and the gather are the C ABI's (rl_comm_*, rl_gather*: RCCL loaded by
 librlsted.so itself); torch.distributed is only the fallback transport should that fail to start.
 
---size 2048 is BASELINE config 3 (synthetic 2048x2048 object, line-rescan, 4 views); the default single-GPU run
+--size 2048 is BASELINE config 3 (synthetic 2048x2048 object, line-rescan, 4 views); the --full single-GPU run
 also carries short legs of it ("size_2048"), of config 2's other half (512x512 line-rescan, 4 views: "line_rescan_512")
 and of the reference's own arithmetic (512x512 point, float64 plan: "f64_512") in the same JSON line (--no-extra-legs
-skips them).  With N > 1 ranks (or --workload fig2sweep) the line also carries "fig2_sweep": BASELINE config 4 -- 4 test
+skips them).  With --workload fig2sweep (or N > 1 ranks and --full) the line also carries "fig2_sweep": BASELINE config 4 -- 4 test
 objects x 6 doses x 3 scan modes x 16 seeds = 1152 tasks, K = 20 -- cut into cost-weighted shards by
 sharding.partition, each rank running its shard through rl_batch_run, ONE gather of the estimates on rank 0
 (rl_comm_gather_host), the gather timed separately.
@@ -299,6 +307,53 @@ def accuracy(plan, psf, size, dtype):
                                  'increment form of H was measured: tools/increment_form_study.py)')}
 
 
+DUMP_BYTES = 48 << 20       # --dump-outputs: at most this much per run
+DUMP_SEED = 20250101        # fixes which frames (and, for a frame too large, which pixels) are written
+
+
+def dump_frames(B, frame_bytes):
+    """The frames of the --dump-outputs sample: as many seeded frames (sorted) as fit in DUMP_BYTES, at least one.
+    frame_bytes: the bytes of one frame of all the arrays written together."""
+    n = int(min(B, max(1, DUMP_BYTES // frame_bytes)))
+    return np.arange(B) if n == B else np.sort(np.random.default_rng(DUMP_SEED).choice(B, n, replace=False))
+
+
+def plan_frames(plan, which, frames):
+    """Frames `frames` of a plan buffer ('estimate': (ny, nx) each, 'measurement': (V, ny, nx) each) in the buffer's own
+    precision, one download per frame straight from the device buffer: only these frames cross PCIe."""
+    import ctypes
+    from rescan_line_sted_amd import _lib
+    cai = plan.device_array(which).__cuda_array_interface__
+    shape, base = cai['shape'], cai['data'][0]
+    f32 = cai['typestr'] == '<f4'
+    per, es = int(np.prod(shape[1:])), (4 if f32 else 8)
+    out = np.empty((len(frames),) + tuple(shape[1:]), dtype=np.float64)
+    for i, f in enumerate(frames):
+        f = int(f)
+        if not 0 <= f < shape[0]:
+            raise IndexError('frame %d of a %d-frame plan' % (f, shape[0]))
+        _lib.check(_lib.lib.rl_device_download(plan.ctx.handle, ctypes.c_void_p(base + f * per * es),
+                                               _lib.RL_F32 if f32 else _lib.RL_F64, per, _lib.ptr(out[i])))
+    return out.astype(np.float32) if f32 else out
+
+
+def dump_outputs(plan, outdir, stub=False):
+    """--dump-outputs: what the last timed step left in the plan -- the estimates after K iterations and the noisy
+    measurements they were computed from -- as outdir/estimate.npy (n, ny, nx) and outdir/measurement.npy (n, V, ny, nx),
+    float32 from an f32 plan, float64 from an f64 plan.  The same seeded frames of both (dump_frames); should one frame
+    exceed its array's part of DUMP_BYTES (2048 x 2048 and up), a seeded sample of its pixels instead: (1, pixels)."""
+    os.makedirs(outdir, exist_ok=True)
+    es = 4 if getattr(plan, 'dtype', 'f32') == 'f32' else 8
+    frames = dump_frames(plan.B, (1 + plan.V) * plan.ny * plan.nx * es)
+    for name, share in (('estimate', 1), ('measurement', plan.V)):
+        a = getattr(plan, name)()[frames].astype(np.float32) if stub else plan_frames(plan, name, frames)
+        cap = DUMP_BYTES * share // (1 + plan.V)
+        if a.nbytes > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED + share).choice(a[0].size, cap // a.itemsize, replace=False))
+            a = a.reshape(len(frames), -1)[:, idx]
+        np.save(os.path.join(outdir, name + '.npy'), a)
+
+
 def extra_leg(size, n_views, dtype, B, steps, warmup, device, k_iters=K_ITERS, comm=None):
     """`steps` whole cycles (simulate + 20 RL iterations) of `B` frames of another workload shape, timed like the
     headline (synchronise, wall clock, synchronise): BASELINE config 3 (2048 x 2048 line-rescan), config 2's line-rescan
@@ -469,7 +524,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=None, help='frames per GPU per step (default 1024; 32 at --size 2048)')
     ap.add_argument('--workload', default='headline', choices=('headline', 'fig2sweep'),
-                    help='fig2sweep: also run BASELINE config 4 (the sharded figure-2 sweep; always run when N > 1)')
+                    help='fig2sweep: also run BASELINE config 4 (the sharded figure-2 sweep; also run by --full when N > 1)')
     ap.add_argument('--dtype', default='f32')
     ap.add_argument('--size', type=int, default=512, choices=(512, 2048))
     ap.add_argument('--allow-torch-transport', action='store_true',
@@ -477,8 +532,14 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-accuracy', action='store_true')
     ap.add_argument('--no-extra-legs', '--no-2048', dest='no_extra', action='store_true',
-                    help='skip the short 2048 x 2048, 512 x 512 line-rescan and float64 legs of the default run')
+                    help='skip the short 2048 x 2048, 512 x 512 line-rescan and float64 legs of the --full run')
+    ap.add_argument('--full', action='store_true',
+                    help='also the roofline, the accuracy check, the CPU baseline, the extra legs and (N > 1) the sweep')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write a seeded sample of what the last timed step computed to DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'RANK' not in os.environ:
         sys.exit(self_launch(args, sys.argv[1:]))
@@ -503,7 +564,7 @@ def main():
 
     # CPU legs first: this process has not touched the GPU yet, the workers are plain children
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not stub:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not stub:
         cpu = cpu_baseline(size, 6.0 if size == 512 else 20.0)
 
     comm, transport = (None, None)
@@ -551,75 +612,81 @@ def main():
         except Exception as exc:      # the gather is reported, never allowed to void the measurement
             gather = {'error': repr(exc), 'transport': transport}
 
-    # sanity of what was just computed (not timed)
-    est = plan.estimate()
-    assert np.isfinite(est).all() and est.min() >= 0
-
-    # ---- roofline: in-situ HIP-event durations of one whole cycle (every launch bracketed by the kernel's own
-    # begin / end events on the stream it goes to, slices overlapping as in the timed steps)
-    kt, FL = plan.time_cycle(K_ITERS, seed=4242)
     n_pix, V = size * size, len(psf)
     info = plan.info()
-    avg = {k: v[0] for k, v in kt.items()}
-    rl_kernels = ('colconv_H', 'rowpass_RATIO', 'colconv_Ht', 'rowpass_UPDATE')
-    total_ms = {k: kt[k][0] * kt[k][1] for k in rl_kernels}
-    kernel_ms = {'colconv': total_ms['colconv_H'] + total_ms['colconv_Ht'], 'rowpass_RATIO': total_ms['rowpass_RATIO'],
-                 'rowpass_UPDATE': total_ms['rowpass_UPDATE']}
-    dom = max(kernel_ms, key=kernel_ms.get)
-    # Algorithmic bytes exist per RL ITERATION: 4N(3V+4) per frame -- pass 1 (H + ratio) 4N(2V+1), pass 2
-    # (H_t + update) 4N(V+3); each pass is one column launch + one row launch and cannot be split between its two
-    # kernels.  So the roofline is quoted on the unit the bytes are defined for: one RL iteration over one slice of
-    # the batch = the four launches colconv, ROW_RATIO, colconv, ROW_UPDATE; `achieved` = its algorithmic bytes / the sum
-    # of the four launches' average durations, `traffic` = the sum of the four launches' fabric bytes from the PMC
-    # counters (FETCH_SIZE / WRITE_SIZE, separate rocprofv3 passes, gfx950 correction applied: tools/pmc_traffic.py,
-    # recorded offline for this exact launch shape).  The dominant kernel's own share is in `dominant_kernel`.
-    iter_ms = sum(avg[k] for k in rl_kernels)
-    alg_iter = 4 * n_pix * (3 * V + 4) * FL
-    achieved = alg_iter / (iter_ms * 1e-3) / 1e9
-    traffic, per_kernel_traffic, pmc_file = None, None, None
-    for name in ('pmc_traffic.json', 'pmc_traffic_%d.json' % size):
-        try:
-            pmc = json.load(open(os.path.join(ROOT, 'profiles', PROFILE_ROUND, name)))
-        except (OSError, ValueError):
-            continue
-        if (pmc.get('frames_per_launch') == FL and pmc.get('dtype') == args.dtype and pmc.get('n_psf') == V
-                and pmc.get('shape') == [size, size] and all(k in pmc for k in rl_kernels)):
-            per_kernel_traffic = {k: pmc[k]['fabric_bytes_per_launch'] for k in rl_kernels}
-            traffic = sum(per_kernel_traffic.values())
-            pmc_file = 'profiles/%s/%s' % (PROFILE_ROUND, name)
-            break
-    alg_frame = algorithmic_bytes_per_frame(n_pix, V, K_ITERS)
-    # The batch slices run on two streams: on average `concurrency` kernels are in flight, each with its
-    # share of the chip, so a kernel's own duration is longer than its cost to the step.
-    busy_ms = sum(v[0] * v[1] for v in kt.values())
-    concurrency = max(1.0, busy_ms / max(dev_ms / args.steps, 1e-9))
-    roofline = {
-        'bound': 'hbm', 'unit': 'GB/s', 'peak': HBM_PEAK_GBS,
-        'note': ('priced against the HBM roofline as BASELINE.json asks.  Round 4 (tools/valu_probe.hip with in-kernel cycle stamps, profiles/r04/'
-                 'sq_counters_512.txt): a wave issues one vector instruction per 8 cycles at most, a SIMD one per ~2 with >= 4-6 waves issuing; the three '
-                 'RL kernels keep the vector pipe ~45 % busy alone and the fabric at 2.8-4.3 TB/s -- neither unit is saturated, the launches are bound by '
-                 'how the load / transform / store phases of 6-8 waves per SIMD interleave; two slices in flight reach 4.9-5.1 TB/s of fabric traffic, '
-                 '1.75x the algorithmic bytes because every spectrum crosses memory between its row and its column pass (DESIGN.md section 4)') if size < 1024 else
-                ('priced against the HBM roofline as BASELINE.json asks; at this size the slices stream through HBM and every kernel of '
-                 'the iteration runs at 3.1-4.4 TB/s of fabric traffic alone (profiles/r03/split_2048, point_2048_head): a plain copy on this part '
-                 'moves 5.1 TB/s (tools/gpu/gpu_stream_rate.py): the loop is near the streaming rate for its bytes, which are ~2-3x the image-sized passes because every spectrum crosses '
-                 'memory between its row and its column pass (DESIGN.md section 3)'),
-        'kernel': ('one RL iteration over one slice = 6 launches: split column pass of H (k_colconv_outer<FWD>, <INV>), k_rowpass<RATIO>, '
-                   'split column pass of H_t (k_colconv_outer<FWD>, <INV_SUM>), k_rowpass<UPDATE>; colconv_H / colconv_Ht = both halves'
-                   if (not stub and plan.strategy().get('split_column_pass')) else
-                   'one RL iteration over one slice = 4 launches: k_colconv, k_rowpair<RATIO>, k_colconv, k_rowpair<UPDATE>'),
-        'achieved': achieved, 'frac': achieved / HBM_PEAK_GBS,
-        'algorithmic_bytes': alg_iter, 'traffic': traffic, 'traffic_over_algorithmic': traffic / alg_iter if traffic else None,
-        'traffic_per_kernel': per_kernel_traffic, 'traffic_source': pmc_file,
-        'per': 'RL iteration over %d frames (the slice every launch of the loop covers)' % FL,
-        'dominant_kernel': {'name': dom, 'share_of_rl_kernel_time': kernel_ms[dom] / sum(kernel_ms.values())},
-        'kernels_in_flight': concurrency, 'frac_per_chip_share': achieved * concurrency / HBM_PEAK_GBS,
-        'timing': 'kernel begin/end HIP events (hipExtLaunchKernelGGL) on every launch of one whole cycle, slices overlapping on their streams as in the timed steps (rl_deconv_time_cycle)',
-        'kernel_avg_ms': avg, 'kernel_launches_per_cycle': {k: v[1] for k, v in kt.items()},
-        'frames_per_launch': FL, 'frame_pairs': plan.strategy()['frame_pairs'] if not stub else None,
-        'whole_path': {'algorithmic_bytes_per_frame': alg_frame, 'GBps': alg_frame * (value / world) / 1e9,
-                       'frac': alg_frame * (value / world) / 1e9 / HBM_PEAK_GBS},
-    }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(plan, args.dump_outputs, stub)
+
+    # everything below the headline figure: --full only
+    roofline = None
+    if args.full:
+        # sanity of what was just computed (not timed)
+        est = plan.estimate()
+        assert np.isfinite(est).all() and est.min() >= 0
+
+        # ---- roofline: in-situ HIP-event durations of one whole cycle (every launch bracketed by the kernel's own
+        # begin / end events on the stream it goes to, slices overlapping as in the timed steps)
+        kt, FL = plan.time_cycle(K_ITERS, seed=4242)
+        avg = {k: v[0] for k, v in kt.items()}
+        rl_kernels = ('colconv_H', 'rowpass_RATIO', 'colconv_Ht', 'rowpass_UPDATE')
+        total_ms = {k: kt[k][0] * kt[k][1] for k in rl_kernels}
+        kernel_ms = {'colconv': total_ms['colconv_H'] + total_ms['colconv_Ht'], 'rowpass_RATIO': total_ms['rowpass_RATIO'],
+                     'rowpass_UPDATE': total_ms['rowpass_UPDATE']}
+        dom = max(kernel_ms, key=kernel_ms.get)
+        # Algorithmic bytes exist per RL ITERATION: 4N(3V+4) per frame -- pass 1 (H + ratio) 4N(2V+1), pass 2
+        # (H_t + update) 4N(V+3); each pass is one column launch + one row launch and cannot be split between its two
+        # kernels.  So the roofline is quoted on the unit the bytes are defined for: one RL iteration over one slice of
+        # the batch = the four launches colconv, ROW_RATIO, colconv, ROW_UPDATE; `achieved` = its algorithmic bytes / the sum
+        # of the four launches' average durations, `traffic` = the sum of the four launches' fabric bytes from the PMC
+        # counters (FETCH_SIZE / WRITE_SIZE, separate rocprofv3 passes, gfx950 correction applied: tools/pmc_traffic.py,
+        # recorded offline for this exact launch shape).  The dominant kernel's own share is in `dominant_kernel`.
+        iter_ms = sum(avg[k] for k in rl_kernels)
+        alg_iter = 4 * n_pix * (3 * V + 4) * FL
+        achieved = alg_iter / (iter_ms * 1e-3) / 1e9
+        traffic, per_kernel_traffic, pmc_file = None, None, None
+        for name in ('pmc_traffic.json', 'pmc_traffic_%d.json' % size):
+            try:
+                pmc = json.load(open(os.path.join(ROOT, 'profiles', PROFILE_ROUND, name)))
+            except (OSError, ValueError):
+                continue
+            if (pmc.get('frames_per_launch') == FL and pmc.get('dtype') == args.dtype and pmc.get('n_psf') == V
+                    and pmc.get('shape') == [size, size] and all(k in pmc for k in rl_kernels)):
+                per_kernel_traffic = {k: pmc[k]['fabric_bytes_per_launch'] for k in rl_kernels}
+                traffic = sum(per_kernel_traffic.values())
+                pmc_file = 'profiles/%s/%s' % (PROFILE_ROUND, name)
+                break
+        alg_frame = algorithmic_bytes_per_frame(n_pix, V, K_ITERS)
+        # The batch slices run on two streams: on average `concurrency` kernels are in flight, each with its
+        # share of the chip, so a kernel's own duration is longer than its cost to the step.
+        busy_ms = sum(v[0] * v[1] for v in kt.values())
+        concurrency = max(1.0, busy_ms / max(dev_ms / args.steps, 1e-9))
+        roofline = {
+            'bound': 'hbm', 'unit': 'GB/s', 'peak': HBM_PEAK_GBS,
+            'note': ('priced against the HBM roofline as BASELINE.json asks.  Round 4 (tools/valu_probe.hip with in-kernel cycle stamps, profiles/r04/'
+                     'sq_counters_512.txt): a wave issues one vector instruction per 8 cycles at most, a SIMD one per ~2 with >= 4-6 waves issuing; the three '
+                     'RL kernels keep the vector pipe ~45 % busy alone and the fabric at 2.8-4.3 TB/s -- neither unit is saturated, the launches are bound by '
+                     'how the load / transform / store phases of 6-8 waves per SIMD interleave; two slices in flight reach 4.9-5.1 TB/s of fabric traffic, '
+                     '1.75x the algorithmic bytes because every spectrum crosses memory between its row and its column pass (DESIGN.md section 4)') if size < 1024 else
+                    ('priced against the HBM roofline as BASELINE.json asks; at this size the slices stream through HBM and every kernel of '
+                     'the iteration runs at 3.1-4.4 TB/s of fabric traffic alone (profiles/r03/split_2048, point_2048_head): a plain copy on this part '
+                     'moves 5.1 TB/s (tools/gpu/gpu_stream_rate.py): the loop is near the streaming rate for its bytes, which are ~2-3x the image-sized passes because every spectrum crosses '
+                     'memory between its row and its column pass (DESIGN.md section 3)'),
+            'kernel': ('one RL iteration over one slice = 6 launches: split column pass of H (k_colconv_outer<FWD>, <INV>), k_rowpass<RATIO>, '
+                       'split column pass of H_t (k_colconv_outer<FWD>, <INV_SUM>), k_rowpass<UPDATE>; colconv_H / colconv_Ht = both halves'
+                       if (not stub and plan.strategy().get('split_column_pass')) else
+                       'one RL iteration over one slice = 4 launches: k_colconv, k_rowpair<RATIO>, k_colconv, k_rowpair<UPDATE>'),
+            'achieved': achieved, 'frac': achieved / HBM_PEAK_GBS,
+            'algorithmic_bytes': alg_iter, 'traffic': traffic, 'traffic_over_algorithmic': traffic / alg_iter if traffic else None,
+            'traffic_per_kernel': per_kernel_traffic, 'traffic_source': pmc_file,
+            'per': 'RL iteration over %d frames (the slice every launch of the loop covers)' % FL,
+            'dominant_kernel': {'name': dom, 'share_of_rl_kernel_time': kernel_ms[dom] / sum(kernel_ms.values())},
+            'kernels_in_flight': concurrency, 'frac_per_chip_share': achieved * concurrency / HBM_PEAK_GBS,
+            'timing': 'kernel begin/end HIP events (hipExtLaunchKernelGGL) on every launch of one whole cycle, slices overlapping on their streams as in the timed steps (rl_deconv_time_cycle)',
+            'kernel_avg_ms': avg, 'kernel_launches_per_cycle': {k: v[1] for k, v in kt.items()},
+            'frames_per_launch': FL, 'frame_pairs': plan.strategy()['frame_pairs'] if not stub else None,
+            'whole_path': {'algorithmic_bytes_per_frame': alg_frame, 'GBps': alg_frame * (value / world) / 1e9,
+                           'frac': alg_frame * (value / world) / 1e9 / HBM_PEAK_GBS},
+        }
 
     out = {
         'metric': 'simulated frames/s (%dx%d, 20 RL iters)' % (size, size),
@@ -630,9 +697,10 @@ def main():
                    'fft': '%dx%d' % (info['ly'], info['lx']), 'sharding': 'frames over ranks, no data-path collective'},
         'device_ms_per_step': dev_ms / args.steps,
         'final_gather': gather,
-        'roofline': roofline,
     }
-    if rank == 0 and not args.no_accuracy and not stub and size == 512:   # (the oracle needs minutes per 2048^2 frame)
+    if roofline is not None:
+        out['roofline'] = roofline
+    if args.full and rank == 0 and not args.no_accuracy and not stub and size == 512:   # (the oracle needs minutes per 2048^2 frame)
         out['accuracy'] = accuracy(plan, psf, size, args.dtype)
         # predictions H(est) <= 0 met by the ratio kernels in everything this plan ran (rl_deconv_unresolved): 0 = the f32 transforms resolve this workload
         out['accuracy']['unresolved_predictions'] = plan.unresolved()
@@ -640,7 +708,7 @@ def main():
         out['cpu_baseline'] = cpu
     # further shapes in the same record, a few steps each (single-process runs only -- the N-rank runs measure the
     # headline): BASELINE config 3 (2048^2 line-rescan), config 2's line-rescan half, the reference's float64 arithmetic
-    if size == 512 and world == 1 and comm is None and not stub and not args.no_extra and args.dtype == 'f32':
+    if args.full and size == 512 and world == 1 and comm is None and not stub and not args.no_extra and args.dtype == 'f32':
         del plan
         # (every leg >= 0.5 s of timed device work)
         for key, leg, k in (('size_2048', (2048, 4, 'f32', 32, 5, 1), K_ITERS), ('line_rescan_512', (512, 4, 'f32', 256, 12, 1), K_ITERS),
@@ -652,15 +720,15 @@ def main():
                 out[key] = {'error': repr(exc)}
     # N ranks: the 2048 x 2048 shapes as replicas, one per GPU (north star: "throughput on synthetic 512x512 and 2048x2048 images
     # reported at 1, 2, 4 and 8 GPUs"), timed like the headline
-    if world > 1 and size == 512 and not stub and not args.no_extra and args.dtype == 'f32':
+    if args.full and world > 1 and size == 512 and not stub and not args.no_extra and args.dtype == 'f32':
         del plan
         for key, leg in (('size_2048', (2048, 4, 'f32', 32, 5, 1)), ('point_2048', (2048, 1, 'f32', 32, 16, 1))):
             try:
                 out[key] = extra_leg(*leg, local_rank, K_ITERS, comm)
             except Exception as exc:
                 out[key] = {'error': repr(exc)}
-    # BASELINE config 4 through the sharder: whenever there is more than one rank, or on request
-    if world > 1 or args.workload == 'fig2sweep':
+    # BASELINE config 4 through the sharder: on request, or in a --full run of more than one rank
+    if args.workload == 'fig2sweep' or (args.full and world > 1):
         try:
             out['fig2_sweep'] = fig2_sweep_leg(comm, rank, world, local_rank, stub)
         except Exception as exc:

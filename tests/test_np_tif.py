@@ -1,6 +1,6 @@
 """np_tif mirror: round trips (the reference's own self-test, np_tif.py:445-462,
-re-expressed), ImageJ layout, and -- in the build container only -- reading the
-reference's real ImageJ-written test objects."""
+re-expressed), ImageJ layout, and reading the reference's real ImageJ-written test
+objects (copies of its test_object_*.tif under tests/golden/)."""
 import os
 
 import numpy as np
@@ -8,7 +8,7 @@ import pytest
 
 from rescan_line_sted_amd import np_tif
 
-REF = '/root/reference/figure_generation'
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
 
 @pytest.mark.parametrize('shape', [(7,), (5, 6), (3, 5, 6), (1, 128, 128)])
@@ -45,9 +45,8 @@ def test_imagej_layout_and_description(tmp_path):
         np_tif.array_to_tif(a, fn, slices=4, channels=2)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree only exists in the build container')
 def test_reads_the_reference_test_objects(golden):
     objs = golden('objects')
     for name in ('cat', 'astronaut', 'lines', 'rings'):
-        a = np_tif.tif_to_array(os.path.join(REF, 'test_object_%s.tif' % name))
+        a = np_tif.tif_to_array(os.path.join(GOLDEN, 'test_object_%s.tif' % name))
         assert a.dtype == objs[name].dtype and np.array_equal(a, objs[name])

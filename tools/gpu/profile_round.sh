@@ -9,8 +9,8 @@ R=${1:-r04}
 OUT=gpurun_out/$R/prof
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-ARGS512="--steps 2 --warmup 1 --batch 256 --no-cpu-baseline --no-extra-legs --no-accuracy"
-ARGS2048="--size 2048 --steps 1 --warmup 1 --no-cpu-baseline"
+ARGS512="--full --steps 2 --warmup 1 --batch 256 --no-cpu-baseline --no-extra-legs --no-accuracy"
+ARGS2048="--full --size 2048 --steps 1 --warmup 1 --no-cpu-baseline"
 run() { echo "== $*" >&2; timeout -k 10 600 "$@"; }
 f() { find $OUT/$1 -name "*$2" | head -1; }
 run rocprofv3 --kernel-trace --stats -d $OUT/stats512 --output-format csv -- python3 bench.py $ARGS512 > $OUT/bench512_under_rocprof.json 2> $OUT/stats512.err

@@ -4,10 +4,10 @@ R=${1:-r04}
 O=gpurun_out/$R
 mkdir -p $O
 tools/gpu/profile_round.sh $R > $O/profile_round.log 2>&1; tail -3 $O/profile_round.log
-timeout -k 10 600 python3 bench.py > $O/bench_$R.json 2> $O/bench_$R.err; echo "bench rc $?"; tail -2 $O/bench_$R.err
-timeout -k 10 300 python3 bench.py --workload fig2sweep --no-extra-legs --no-cpu-baseline --no-accuracy --steps 10 > $O/bench_fig2sweep_$R.json 2> /dev/null; echo "sweep rc $?"
+timeout -k 10 600 python3 bench.py --full > $O/bench_$R.json 2> $O/bench_$R.err; echo "bench rc $?"; tail -2 $O/bench_$R.err
+timeout -k 10 300 python3 bench.py --full --workload fig2sweep --no-extra-legs --no-cpu-baseline --no-accuracy --steps 10 > $O/bench_fig2sweep_$R.json 2> /dev/null; echo "sweep rc $?"
 # the N-rank code path at world size 1 (RCCL communicator of the C ABI: barrier, max, broadcast of the PSF sets, device gather)
-RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29511 timeout -k 10 300 python3 bench.py --gpus 1 --workload fig2sweep --steps 5 --warmup 2 --no-cpu-baseline --no-extra-legs --no-accuracy > $O/bench_launcher_world1.json 2> $O/bench_launcher_world1.err; echo "world-1 launcher path rc $?"
+RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29511 timeout -k 10 300 python3 bench.py --gpus 1 --full --workload fig2sweep --steps 5 --warmup 2 --no-cpu-baseline --no-extra-legs --no-accuracy > $O/bench_launcher_world1.json 2> $O/bench_launcher_world1.err; echo "world-1 launcher path rc $?"
 python3 - <<PY
 import json
 d = json.load(open('$O/bench_$R.json'))
