@@ -105,6 +105,26 @@ int rl_deconv_reset_estimate(rl_deconv* h);
  * from that estimate.  Uploads estimate [batch][ny][nx]; the next rl_deconv_iterate continues from it. */
 int rl_deconv_set_estimate(rl_deconv* h, const double* estimate);
 
+/* Biggs-Andrews accelerated Richardson-Lucy (Biggs & Andrews, Appl. Opt. 36, 1766, 1997), per plan, off by default.  Opt in:
+ * it departs from the reference's iteration by design.  With psi(y) one reference iteration
+ * (:520-531) applied to y, x_0 = ones, per frame and k = 0, 1, ...:
+ *     x_{k+1} = psi(y_k)                                                y_0 = x_0
+ *     g_k     = x_{k+1} - y_k
+ *     a_{k+1} = clamp(sum g_k g_{k-1} / sum g_{k-1} g_{k-1}, 0, 1)      (0 for k = 0, or a denominator that is 0 / not finite)
+ *     y_{k+1} = max(x_{k+1} + a_{k+1} (x_{k+1} - x_k), 0)
+ * Sums over the frame's ny * nx pixels, accumulated in float64 in a fixed order (no atomics): a frame's result in a float64 plan
+ * does not depend on its batch.  The estimate after K iterations is x_K.  The history (x_k, y_k, g_k, the partial sums) spans
+ * rl_deconv_iterate calls -- iterate(3) then iterate(2) is iterate(5) -- and restarts with new data (rl_deconv_set_measurement,
+ * rl_deconv_simulate*, every chunk of rl_batch_run / rl_batch_submit), rl_deconv_reset_estimate, rl_deconv_set_estimate (a set
+ * estimate is an x_k without history: the next step has a = 0) and a change of mode; rl_forward / rl_adjoint leave it alone.
+ * The mode applies from the next iterate / batch run on; switching it on allocates three more images per frame.
+ * At very low dose the extrapolation reaches the noise-fitting regime in fewer iterations, as plain Richardson-Lucy does later. */
+#define RL_ACCEL_NONE 0
+#define RL_ACCEL_BIGGS_ANDREWS 1
+int rl_deconv_set_acceleration(rl_deconv* h, int mode);
+/* out [batch]: the a that formed each frame's last extrapolated point (0 before one). */
+int rl_deconv_get_alpha(rl_deconv* h, double* out);
+
 int rl_deconv_get_object(rl_deconv* h, double* out);        /* [batch][ny][nx]        */
 int rl_deconv_get_noiseless(rl_deconv* h, double* out);     /* [batch][n_psf][ny][nx] */
 int rl_deconv_get_measurement(rl_deconv* h, double* out);   /* [batch][n_psf][ny][nx] */

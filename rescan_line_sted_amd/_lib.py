@@ -14,6 +14,16 @@ LIB_PATH = os.environ.get('RLSTED_LIB') or os.path.join(_HERE, '_lib', 'librlste
 RL_F32, RL_F64 = 0, 1
 RNG_NONE, RNG_PHILOX = 0, 1
 DTYPES = {'f32': RL_F32, 'float32': RL_F32, 'f64': RL_F64, 'float64': RL_F64}
+RL_ACCEL_NONE, RL_ACCEL_BIGGS_ANDREWS = 0, 1
+ACCELERATIONS = {None: RL_ACCEL_NONE, 'none': RL_ACCEL_NONE, 'biggs-andrews': RL_ACCEL_BIGGS_ANDREWS}
+
+
+def accel_mode(acceleration):
+    """None / 'none' -> RL_ACCEL_NONE, 'biggs-andrews' -> RL_ACCEL_BIGGS_ANDREWS."""
+    try:
+        return ACCELERATIONS[acceleration]
+    except (KeyError, TypeError):
+        raise ValueError("acceleration must be None or 'biggs-andrews'; got %r" % (acceleration,)) from None
 
 # name -> (restype, argtypes); exactly the symbols include/rlsted.h declares
 _c = ctypes
@@ -36,6 +46,8 @@ PROTOTYPES = {
     'rl_deconv_iterate': (_i, [_vp, _i]),
     'rl_deconv_reset_estimate': (_i, [_vp]),
     'rl_deconv_set_estimate': (_i, [_vp, _dp]),
+    'rl_deconv_set_acceleration': (_i, [_vp, _i]),
+    'rl_deconv_get_alpha': (_i, [_vp, _dp]),
     'rl_deconv_get_object': (_i, [_vp, _dp]),
     'rl_deconv_get_noiseless': (_i, [_vp, _dp]),
     'rl_deconv_get_measurement': (_i, [_vp, _dp]),
@@ -192,7 +204,9 @@ def common_psf_shape(psfs):
 class DeconvPlan:
     """rl_deconv: `batch` frames sharing one PSF set and one image shape."""
 
-    def __init__(self, psfs, batch, ny, nx, dtype='f32', device=0, stream=0):
+    def __init__(self, psfs, batch, ny, nx, dtype='f32', device=0, stream=0, acceleration=None):
+        """acceleration: None (plain Richardson-Lucy, the reference's iteration) or 'biggs-andrews' (set_acceleration)."""
+        mode = accel_mode(acceleration)
         psfs = [as_f64(p) for p in psfs]
         for p in psfs:
             if p.ndim != 3 or p.shape[0] != 1:
@@ -206,6 +220,9 @@ class DeconvPlan:
         self.handle = _vp()
         check(lib.rl_deconv_create(self.ctx.handle, ptr(self.psf_stack), self.V, self.py, self.px,
                                    self.B, self.ny, self.nx, DTYPES[dtype], ctypes.byref(self.handle)))
+        self.acceleration = None
+        if mode:
+            self.set_acceleration(acceleration)
 
     def __del__(self):
         h = getattr(self, 'handle', None)
@@ -257,6 +274,20 @@ class DeconvPlan:
     def set_estimate(self, est):
         est = as_f64(est).reshape(self.B, self.ny, self.nx)
         check(lib.rl_deconv_set_estimate(self.handle, ptr(est)))
+
+    def set_acceleration(self, acceleration):
+        """None: plain Richardson-Lucy; 'biggs-andrews': vector-extrapolated Richardson-Lucy (include/rlsted.h
+        rl_deconv_set_acceleration) from the next iterate / batch run on.  A change of mode
+        restarts the extrapolation history; the estimate stays."""
+        mode = accel_mode(acceleration)
+        check(lib.rl_deconv_set_acceleration(self.handle, mode))
+        self.acceleration = 'biggs-andrews' if mode else None
+
+    def alpha(self):
+        """(B,) float64: the extrapolation weight that formed each frame's last extrapolated point (0 before one)."""
+        out = np.zeros(self.B, dtype=np.float64)
+        check(lib.rl_deconv_get_alpha(self.handle, ptr(out)))
+        return out
 
     def _get(self, fn, shape, out=None):
         if out is None:

@@ -16,6 +16,7 @@
 #include <chrono>
 #include <vector>
 
+#include "accel_kernels.hpp"
 #include "aux_kernels.hpp"
 #include "conv_kernels.hpp"
 #include "kernel_table.hpp"
@@ -167,6 +168,58 @@ struct rl_deconv {
     int col_order = 4;
     bool inplace = true;     // single-view RL iterations entirely in spec_a (RLSTED_INPLACE=0: spec_a -> spec_b -> spec_a)
     bool est_ready = false;    // est holds a valid estimate
+    // ---- Biggs-Andrews acceleration (accel_kernels.hpp, rl_deconv_set_acceleration): per frame the previous point x_{k-1}, the
+    // extrapolated point y_k and the step g_k in three image buffers, the dot products' per-workgroup partials and the a of the
+    // last extrapolated point in float64 -- allocated when the mode is first switched on.  The history spans rl_deconv_iterate
+    // calls; acc_steps = the psi steps taken in it (0: none -- new data, a set estimate, a change of mode).
+    int accel = RL_ACCEL_NONE;
+    void *acc_x = nullptr, *acc_y = nullptr, *acc_g = nullptr;
+    double *acc_part = nullptr, *acc_alpha = nullptr;
+    long acc_steps = 0;
+    int acc_blocks() const { return accel_blocks(n_img(), esize(dtype)); }
+    int ensure_accel() {
+        const size_t img = (size_t)B * n_img() * esize(dtype), part = (size_t)B * acc_blocks() * 2 * sizeof(double);
+        for (void** p : {&acc_x, &acc_y, &acc_g})
+            if (!*p) {
+                HIP_TRY(hipMalloc(p, img));
+                bytes += img;
+            }
+        if (!acc_part) {
+            HIP_TRY(hipMalloc((void**)&acc_part, part));
+            bytes += part;
+        }
+        if (!acc_alpha) {
+            HIP_TRY(hipMalloc((void**)&acc_alpha, (size_t)B * sizeof(double)));
+            HIP_TRY(hipMemsetAsync(acc_alpha, 0, (size_t)B * sizeof(double), ctx->stream));
+            bytes += (size_t)B * sizeof(double);
+        }
+        return RL_OK;
+    }
+    int accel_reset() {   // (on the context's stream, before any slice of the next run forks off it)
+        acc_steps = 0;
+        if (acc_alpha) HIP_TRY(hipMemsetAsync(acc_alpha, 0, (size_t)B * sizeof(double), ctx->stream));
+        return RL_OK;
+    }
+    // psi step s of the history on frames [f0, f0 + nf): extrapolate (not from the start x_0 = ones, whose y_0 is x_0 -- the shortcut
+    // iteration still applies), rebuild the spectrum of est = y_s where the loop reads one, iterate, then g_s and its partials.
+    // ROW_UPDATE's spectrum is of x_{s+1}, not of the next y: the pair loop skips that store, the others leave it for ROW_FWD.
+    int accel_step(int f0, int nf, long s, bool first, bool from_ones) {
+        const size_t o = (size_t)f0 * n_img();
+        double* part = acc_part + (size_t)f0 * acc_blocks() * 2;
+        if (!from_ones) {
+            HIP_TRY(accel_extrapolate(dtype, off(est, o), off(acc_y, o), off(acc_x, o), part, acc_alpha + f0, n_img(), nf,
+                                      s == 0 ? ACC_FRESH : 0, cur()));
+            if (pair) RL_TRY(row_pair(ROW_FWD, nf, nullptr, pair_spec(f0), off(est, o), nullptr, nullptr));
+            else if (!sep) RL_TRY(row(ROW_FWD, (unsigned)nf, nullptr, off(spec_a, (size_t)f0 * n_spec() * 2), off(est, o), nullptr, nullptr));
+        }
+        drop_last_spectrum = pair;
+        const int rc = iterate_chunk(f0, nf, first, from_ones);
+        drop_last_spectrum = false;
+        RL_TRY(rc);
+        HIP_TRY(accel_reduce(dtype, off(est, o), off(acc_y, o), off(acc_g, o), part, n_img(), nf,
+                             (from_ones ? ACC_Y_ONES : 0) | (s > 0 ? ACC_HAVE_PREV : 0), cur()));
+        return RL_OK;
+    }
     bool spec_valid = false;   // spec_a holds rowFFT(est)
     long iterations = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -655,7 +708,7 @@ struct rl_deconv {
         // per slice; `lanes` slices are in flight at once, together about the 256 MiB Infinity Cache
         const double budget_mb = getenv("RLSTED_CHUNK_MB") ? atof(getenv("RLSTED_CHUNK_MB")) : (lanes > 1 ? 108.0 : 288.0);
         const double specs = (V == 1 && inplace) ? 1.0 : 1.0 + V;   // spectra alive in an iteration
-        const double per_frame = (specs * 2.0 * n_spec() + (1.0 + V) * n_img()) * esize(dtype);
+        const double per_frame = (specs * 2.0 * n_spec() + (1.0 + V + (accel ? 3.0 : 0.0)) * n_img()) * esize(dtype);   // (+ x, y, g)
         // Frames of 32 MB and more (2048^2 up) do not live in the Infinity Cache whatever the slice: there the slice
         // only has to fill the chip -- ~1 GB per slice measured best at 2048^2 (point 658 -> 713, 4 views 180 -> 192
         // frames/s over 2-frame / 1-frame slices).
@@ -837,6 +890,7 @@ struct rl_deconv {
         // Lanes stay open between the back-to-back cycles of rl_deconv_bench_cycles (defer_join): slice s of every cycle
         // goes to the same lane, so stream order alone keeps each slice's buffers consistent and the lanes need not meet.
         const bool keep_open = defer_join && nl > 1;
+        if (accel && restart) RL_TRY(accel_reset());   // each run from ones (a task of rl_batch_run included) starts a fresh history
         if (nl > 1 && !lanes_open) {
             RL_TRY(ensure_lanes());
             HIP_TRY(hipEventRecord(fork, ctx->stream));
@@ -883,6 +937,10 @@ struct rl_deconv {
             // transforms of that launch, the spectrum store); an rl_deconv_iterate that continues rebuilds it with one ROW_FWD.
             const bool drop = pair && k >= 4 && !keep_last_spectrum;
             for (int i = 0; i < k && rc == RL_OK; ++i) {
+                if (accel) {
+                    rc = accel_step(f0, nf, acc_steps + i, shortcut && i == 0, restart && i == 0);
+                    continue;
+                }
                 drop_last_spectrum = drop && i == k - 1;
                 rc = iterate_chunk(f0, nf, shortcut && i == 0, restart && i == 0);
             }
@@ -905,6 +963,10 @@ struct rl_deconv {
             iterations = 0;
         }
         if (pair && k >= 4 && !keep_last_spectrum) spec_valid = false;   // the last iteration left no spectrum behind
+        if (accel) {
+            spec_valid = false;   // (a plain iterate after a change of mode rebuilds it; an accelerated one transforms y)
+            acc_steps += k;
+        }
         iterations += k;
         return RL_OK;
     }
@@ -995,7 +1057,8 @@ int rl_deconv_destroy(rl_deconv* h) {
     for (int l = 0; l < rl_deconv::kMaxLanes; ++l)
         if (h->lane_stream[l]) (void)hipStreamSynchronize(h->lane_stream[l]);
     void* bufs[] = {h->psf_hat_pair, h->psf_hat_pair_re, h->spec_ones_pair, h->sep_u, h->sep_v, h->sep_uf, h->sep_vf, h->spec_ones, h->psf_hat_re, h->psf_hat, h->spec_a, h->spec_b, h->spec_x, h->obj, h->noiseless, h->meas, h->est, h->norm, h->scratch,
-                    h->stage_dev, h->stage_aux, h->stage_sums, h->slice_ws, h->key_seeds, h->key_ids, h->unresolved};
+                    h->stage_dev, h->stage_aux, h->stage_sums, h->slice_ws, h->key_seeds, h->key_ids, h->unresolved,
+                    h->acc_x, h->acc_y, h->acc_g, h->acc_part, h->acc_alpha};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
@@ -1462,6 +1525,30 @@ int rl_deconv_set_estimate(rl_deconv* h, const double* estimate) {
     RL_TRY(h->upload(estimate, h->est, (size_t)h->B * h->n_img()));
     h->est_ready = true;
     h->spec_valid = false;   // the next iterate rebuilds rowFFT(estimate)
+    RL_TRY(h->accel_reset());   // a set estimate is a point with no history
+    return RL_OK;
+}
+
+int rl_deconv_set_acceleration(rl_deconv* h, int mode) {
+    if (!h) return fail(RL_ERR_INVALID, "handle is NULL");
+    if (mode != RL_ACCEL_NONE && mode != RL_ACCEL_BIGGS_ANDREWS) return fail(RL_ERR_INVALID, "unknown acceleration mode");
+    if (mode == h->accel) return RL_OK;
+    HIP_TRY(hipSetDevice(h->ctx->device));
+    if (mode != RL_ACCEL_NONE) RL_TRY(h->ensure_accel());
+    h->accel = mode;
+    h->spec_valid = false;
+    return h->accel_reset();
+}
+
+int rl_deconv_get_alpha(rl_deconv* h, double* out) {
+    if (!h || !out) return fail(RL_ERR_INVALID, "NULL argument");
+    HIP_TRY(hipSetDevice(h->ctx->device));
+    if (!h->acc_alpha) {
+        std::fill(out, out + h->B, 0.0);
+        return RL_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(out, h->acc_alpha, (size_t)h->B * sizeof(double), hipMemcpyDeviceToHost, h->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(h->ctx->stream));
     return RL_OK;
 }
 
@@ -1479,11 +1566,12 @@ int rl_deconv_iterate(rl_deconv* h, int k) {
     RL_TRY(h->refresh_meas_levels());
     HIP_TRY(hipEventRecord(h->ev0, h->ctx->stream));
     bool restart = !h->est_ready;
-    if (!restart && !h->spec_valid && h->pair) {
+    // (an accelerated plan transforms the extrapolated point inside the loop instead)
+    if (!restart && !h->spec_valid && h->pair && !h->accel) {
         RL_TRY(h->row_pair(ROW_FWD, h->B, nullptr, h->spec_a, h->est, nullptr, nullptr));
         h->spec_valid = true;
     }
-    if (!restart && !h->spec_valid && !h->sep) {   // H / H_t were called in between: rebuild rowFFT(est)
+    if (!restart && !h->spec_valid && !h->sep && !h->accel) {   // H / H_t were called in between: rebuild rowFFT(est)
         RL_TRY(h->row(ROW_FWD, (unsigned)h->B, nullptr, h->spec_a, h->est, nullptr, nullptr));
         h->spec_valid = true;
     }

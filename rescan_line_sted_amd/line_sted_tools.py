@@ -16,6 +16,12 @@ the device arithmetic: 'f64' (default for this class: bit-level agreement with
 the reference to ~1e-12) or 'f32' (the BASELINE throughput mode, <=1e-5
 normwise at 20 iterations).  Environment variable RLSTED_DTYPE overrides the
 default.
+
+Acceleration: `Deconvolver(acceleration='biggs-andrews')` and
+`deconvolve(..., acceleration='biggs-andrews')` run Biggs-Andrews vector-
+extrapolated Richardson-Lucy -- fewer iterations for the same fit to the data,
+by design not the reference's sequence of estimates.
+The default, None, is the reference's iteration.
 """
 import os
 import time
@@ -39,11 +45,12 @@ class Deconvolver:
     (nz, ny, nx) float64 arrays, estimate updated in place by iterate()."""
 
     def __init__(self, psfs, output_prefix=None, verbose=True, dtype=None,
-                 device=None, rng='numpy'):
+                 device=None, rng='numpy', acceleration=None):
         """'psfs' is a list of numpy arrays, one for each PSF (ref:479-494).
-        dtype/device/rng are extensions: device arithmetic type, GPU index and
-        the Poisson generator ('numpy' = the reference's np.random.poisson on
-        the host, 'philox' = counter-based generator on the device)."""
+        dtype/device/rng/acceleration are extensions: device arithmetic type, GPU
+        index, the Poisson generator ('numpy' = the reference's np.random.poisson
+        on the host, 'philox' = counter-based generator on the device) and the
+        iteration (None = the reference's, 'biggs-andrews' = extrapolated)."""
         self.psfs = list(psfs)
         if output_prefix is None:
             output_prefix = os.getcwd()
@@ -57,6 +64,8 @@ class Deconvolver:
         self.dtype = dtype or _DEFAULT_DTYPE
         self.device = _DEFAULT_DEVICE if device is None else device
         self.rng = rng
+        _lib.accel_mode(acceleration)                   # (a bad name fails here, not at the first iteration)
+        self.acceleration = acceleration
         for p in self.psfs:
             if np.ndim(p) != 3:
                 raise NotImplementedError('PSFs must be 3-D arrays (pz, py, px); got %s' % (np.shape(p),))
@@ -95,7 +104,8 @@ class Deconvolver:
         if p is None or (p.B, p.ny, p.nx) != (nz, ny, nx):
             if p is not None and self._estimate_stale:      # keep what the old plan computed
                 self._estimate, self._estimate_stale = p.estimate(), False
-            self._plan = DeconvPlan(self._plan_psfs(nz), nz, ny, nx, dtype=self.dtype, device=self.device)
+            self._plan = DeconvPlan(self._plan_psfs(nz), nz, ny, nx, dtype=self.dtype, device=self.device,
+                                    acceleration=self.acceleration)
             self._measurement_on_device = False             # the host copy is pushed again when needed
             self._estimate_push = self._estimate is not None and np.shape(self._estimate) == (nz, ny, nx)
             if hasattr(self, 'H_t_normalization'):
@@ -335,14 +345,16 @@ def simulate(objects, psfs, total_brightness=None, seed=0, dtype='f32', device=N
     return plan, plan.noiseless(), plan.measurement()
 
 
-def deconvolve(measurement, psfs, iterations, dtype='f32', device=None, plan=None):
+def deconvolve(measurement, psfs, iterations, dtype='f32', device=None, plan=None, acceleration=None):
     """K Richardson-Lucy iterations on a batch: measurement (B, V, ny, nx).
+    acceleration: None (plain) or 'biggs-andrews' (a given plan is switched to it).
     Returns the estimates (B, ny, nx)."""
     measurement = np.asarray(measurement, dtype=np.float64)
     B, V, ny, nx = measurement.shape
     if plan is None:
         plan = DeconvPlan(psfs, B, ny, nx, dtype=dtype,
                           device=_DEFAULT_DEVICE if device is None else device)
+    plan.set_acceleration(acceleration)
     plan.set_measurement(measurement)
     plan.reset_estimate()
     plan.iterate(iterations)
