@@ -32,6 +32,19 @@ bool debug_sync();                         // RLSTED_DEBUG_SYNC set: sync + chec
 
 using rl::fail;
 
+namespace rl {
+// host float64 values -> a device array of h.size() elements of `dtype` (twiddle tables, stencil taps)
+inline int upload_as(int dtype, const std::vector<double>& h, void* dev) {
+    if (dtype == RL_F64) {
+        HIP_TRY(hipMemcpy(dev, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    } else {
+        const std::vector<float> f(h.begin(), h.end());
+        HIP_TRY(hipMemcpy(dev, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    return RL_OK;
+}
+}  // namespace rl
+
 struct rl_ctx {
     // grow-only device scratch for the PSF pipeline (float64 elements)
     double* psf_work = nullptr;
@@ -89,13 +102,10 @@ struct rl_ctx {
         std::vector<double> h(n, 0.0);
         if (count > 0) (column ? t->fill_tw_col[dtype] : t->fill_tw)(h.data());
         void* dev = nullptr;
-        if (dtype == RL_F64) {
-            HIP_TRY(hipMalloc(&dev, sizeof(double) * n));
-            HIP_TRY(hipMemcpy(dev, h.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-        } else {
-            std::vector<float> f(h.begin(), h.end());
-            HIP_TRY(hipMalloc(&dev, sizeof(float) * n));
-            HIP_TRY(hipMemcpy(dev, f.data(), sizeof(float) * n, hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc(&dev, (dtype == RL_F64 ? sizeof(double) : sizeof(float)) * n));
+        if (int r = rl::upload_as(dtype, h, dev)) {
+            (void)hipFree(dev);
+            return r;
         }
         tw[key] = dev;
         *out = dev;

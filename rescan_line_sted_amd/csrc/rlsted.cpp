@@ -13,7 +13,6 @@
 #include <cstring>
 #include <map>
 #include <string>
-#include <chrono>
 #include <vector>
 
 #include "accel_kernels.hpp"
@@ -62,10 +61,92 @@ const int kLengths[] = {64, 192, 256, 576, 1152, 2304, 4608};
 
 size_t esize(int dtype) { return dtype == RL_F32 ? 4 : 8; }
 
+constexpr int kMaxLanes = 4;
+
+// Every RLSTED_* switch of a plan (RLSTED_DEBUG_SYNC is process wide: rl::debug_sync; RLSTED_SEP_TH: sep_kernels.hip).  Read once,
+// when the plan is created; nothing after plan_options() looks at the environment.  The defaults are the measured optimum.
+struct PlanOptions {
+    // ---- schedule
+    bool chunk_mb_set = false;   // RLSTED_CHUNK_MB: working set of one batch slice in MB; unset: 108 (one lane: 288) and the
+    double chunk_mb = 0;         //   rules of chunk_frames() that only apply when no budget was given
+    // Slices of the batch are independent: they are iterated on `lanes` HIP streams at once so that
+    // the tail of one slice's kernel (the last, partly filled round of workgroups) overlaps another
+    // slice's kernels.  RLSTED_LANES=1: one slice after the other on the context's stream (at most kMaxLanes).
+    int lanes = 2;
+    bool inplace = true;         // RLSTED_INPLACE=0: single-view RL iterations spec_a -> spec_b -> spec_a instead of entirely in spec_a
+    // RLSTED_COL_ORDER: column kernel work order, images per block of the tile order (fft_kernels.hip k_colconv):
+    // 1 image-major ... >= images per launch: tile-major.  Measured at 512^2, 32-frame
+    // slices: 1: 16.80 k, 2: 16.88 k, 4: 16.98 k, 8: 16.81 k, 32: 16.56 k frames/s.
+    int col_order = 4;
+    bool pair = false;           // RLSTED_PAIR: frame pairs in the RL loop; unset: single-view f32 plans (deconv_build)
+    double pair_max_ratio = 4.0; // RLSTED_PAIR_MAX_RATIO: largest level ratio inside a pair (rl_deconv::levels_ok)
+    // ---- arithmetic (each identical in exact arithmetic)
+    bool sub_one = false;        // RLSTED_SUB_ONE: the second half of every iteration on `ratio - 1`; unset: f32 plans of the product build
+    int fuse_views = -1;         // RLSTED_FUSE_VIEWS: -1 unset (H_t views summed in the Fourier domain on f32 plans, not on f64), 0 / 1 as
+                                 //   given; 0 also asks for the reference's per-view clamp, which `ratio - 1` cannot give (rl_deconv_create)
+    bool col_split = true;       // RLSTED_COL_SPLIT=0: no split column pass (rl_deconv::col_split)
+    bool real_psf = true;        // RLSTED_REAL_PSF=0: keep the complex multiplier for real PSF spectra
+    bool ones_shortcut = true;   // RLSTED_ONES_SHORTCUT=0: the first iteration transforms its frame of ones instead of reading spec_ones
+    // ---- strategy (deconv_build)
+    int sep = 1;                 // RLSTED_SEP: separable stencils 0 never, 1 rank-1 PSFs with py + px <= 16, 2 whenever rank 1
+    int sep_one = 1;             // RLSTED_SEP_ONE: 0 two passes, 1 one kernel up to 24 taps a side, 2 one kernel whenever the tile fits LDS
+    int direct = 1;              // RLSTED_DIRECT: direct 2-D stencil 0 never, 1 up to 49 taps, 2 whenever the tile fits LDS
+    // ---- storage-precision study builds (conv_kernels.hpp RL_SPEC_QUANT): log2 of the DC bound of an estimate-type / ratio-type spectrum
+    bool q_exp_est_set = false, q_exp_ratio_set = false;   // RLSTED_Q_EXP_EST, RLSTED_Q_EXP_RATIO
+    int q_exp_est = 14, q_exp_ratio = 14;
+};
+
+PlanOptions plan_options(int dtype, int n_psf) {
+    PlanOptions o;
+    auto flag = [](const char* name, bool unset) {
+        const char* s = getenv(name);
+        return s ? atoi(s) != 0 : unset;
+    };
+    auto number = [](const char* name, int unset, bool* set = nullptr) {
+        const char* s = getenv(name);
+        if (set) *set = s != nullptr;
+        return s ? atoi(s) : unset;
+    };
+    if (const char* s = getenv("RLSTED_CHUNK_MB")) {
+        o.chunk_mb_set = true;
+        o.chunk_mb = atof(s);
+    }
+    o.lanes = std::min(std::max(number("RLSTED_LANES", o.lanes), 1), kMaxLanes);
+    o.inplace = flag("RLSTED_INPLACE", o.inplace);
+    o.col_order = std::max(number("RLSTED_COL_ORDER", o.col_order), 1);
+    o.pair = flag("RLSTED_PAIR", dtype == RL_F32 && n_psf == 1);
+    if (const char* s = getenv("RLSTED_PAIR_MAX_RATIO")) o.pair_max_ratio = atof(s);
+    o.sub_one = flag("RLSTED_SUB_ONE", dtype == RL_F32 && RL_SPEC_QUANT == 0);
+    if (const char* s = getenv("RLSTED_FUSE_VIEWS")) o.fuse_views = atoi(s) != 0 ? 1 : 0;
+    o.col_split = flag("RLSTED_COL_SPLIT", o.col_split);
+    o.real_psf = flag("RLSTED_REAL_PSF", o.real_psf);
+    o.ones_shortcut = flag("RLSTED_ONES_SHORTCUT", o.ones_shortcut);
+    o.sep = number("RLSTED_SEP", o.sep);
+    o.sep_one = number("RLSTED_SEP_ONE", o.sep_one);
+    o.direct = number("RLSTED_DIRECT", o.direct);
+    o.q_exp_est = number("RLSTED_Q_EXP_EST", o.q_exp_est, &o.q_exp_est_set);
+    o.q_exp_ratio = number("RLSTED_Q_EXP_RATIO", o.q_exp_ratio, &o.q_exp_ratio_set);
+    return o;
+}
+
+// Device temporaries of the plan set-up: freed when the scope ends, whichever way it ends (hipFree waits for the device).
+struct TempBuffers {
+    std::vector<void*> bufs;
+    int get(void** p, size_t bytes) {
+        HIP_TRY(hipMalloc(p, bytes));
+        bufs.push_back(*p);
+        return RL_OK;
+    }
+    ~TempBuffers() {
+        for (void* b : bufs) (void)hipFree(b);
+    }
+};
+
 }  // namespace
 
 struct rl_deconv {
     rl_ctx* ctx = nullptr;
+    PlanOptions opt;
     int V = 0, py = 0, px = 0, B = 0, ny = 0, nx = 0, dtype = RL_F32;
     int ly = 0, lx = 0, kx = 0, pitch = 0;
     const KernelTable *ty = nullptr, *tx = nullptr;
@@ -82,11 +163,10 @@ struct rl_deconv {
     // storage-precision study builds (conv_kernels.hpp RL_SPEC_QUANT): powers of two that bring the DC term of an
     // estimate-type / ratio-type spectrum to 2^14 (RLSTED_Q_EXP_EST / RLSTED_Q_EXP_RATIO = log2 of the DC bound)
     float q_est = 1.0f, q_ratio = 1.0f;
-    bool ones_shortcut = true; // first iteration reads spec_ones instead of transforming a frame of ones (RLSTED_ONES_SHORTCUT=0: off)
     // f32 plans (conv_kernels.hpp rl_ratio): the normaliser H_t(ones) from the PSFs' integral images instead of the f32 transform
-    // path (RLSTED_EXACT_NORM=0: off), and -- non-negative PSFs -- the second half of every iteration on `ratio - 1`
+    // path (deconv_build), and -- non-negative PSFs -- the second half of every iteration on `ratio - 1`
     // (RLSTED_SUB_ONE=0: off).  Both shrink f32 rounding error, neither changes the arithmetic in exact terms.
-    bool exact_norm = false, sub_one = false;
+    bool sub_one = false;
     // `ratio - 1` clamps the SUM of the views' back-projections where the reference clamps each view's (ref:587).  The two agree
     // whenever no view's term is negative -- always for one view, and for several as long as the measurement has no negative
     // pixel (PSFs >= 0 is a condition of sub_one).  A multi-view measurement WITH negative pixels (background-subtracted data
@@ -96,7 +176,6 @@ struct rl_deconv {
     // lanes of the ROW_RATIO launches that met a prediction H(est) <= 0 inside the image (conv_kernels.hpp rl_ratio: such a pixel is
     // neutral); device counter, read by rl_deconv_unresolved.  Zero on data whose predictions the plan's arithmetic resolves.
     unsigned long long* unresolved = nullptr;
-    bool in_rl_loop = false;   // set by iterate_chunk: only there do the H_t column launches carry `ratio - 1` (rl_adjoint's input is an image)
     bool sub() const { return sub_one && !(V > 1 && meas_negative); }
     void* obj = nullptr;       // [B][ny][nx]
     void* noiseless = nullptr; // [B*V][ny][nx]
@@ -106,20 +185,49 @@ struct rl_deconv {
     void* scratch = nullptr;   // [B*V][ny][nx] staging for rl_forward / rl_adjoint
     size_t bytes = 0;
     bool have_obj = false, have_meas = false;
+    // ---- device memory: every buffer of the plan comes from alloc() and goes in rl_deconv_destroy -- or in release(), for one that is
+    // replaced during the plan's life.  `bytes` (rl_deconv_info's device_bytes) adds up what alloc() handed out, less the small buffers
+    // that never were part of that figure (UNCOUNTED).  SLACK: RL_STREAM_SLACK zeroed bytes behind the buffer -- the streaming row
+    // kernels load whole 64-lane segments without clamping; lanes past the end of the last row of a buffer read (and discard) these bytes.
+    enum { UNCOUNTED = 1, SLACK = 2 };
+    struct Owned { void* p; size_t counted; };
+    std::vector<Owned> owned;
+    template <typename P>
+    int alloc(P** p, size_t n, int flags = 0) {
+        const size_t total = n + ((flags & SLACK) ? RL_STREAM_SLACK : 0);
+        HIP_TRY(hipMalloc((void**)p, total));
+        owned.push_back({(void*)*p, (flags & UNCOUNTED) ? 0 : total});
+        bytes += owned.back().counted;
+        if (flags & SLACK) HIP_TRY(hipMemsetAsync((char*)*p + n, 0, RL_STREAM_SLACK, ctx->stream));
+        return RL_OK;
+    }
+    template <typename P>
+    int release(P** p) {
+        for (Owned& o : owned)
+            if (*p && o.p == (void*)*p) {
+                HIP_TRY(hipFree(o.p));
+                bytes -= o.counted;
+                o = owned.back();
+                owned.pop_back();
+                break;
+            }
+        *p = nullptr;
+        return RL_OK;
+    }
+    // host float64 values -> a device array of the plan's dtype (the stencils' taps)
+    int upload_taps(void** p, const std::vector<double>& v) {
+        RL_TRY(alloc(p, v.size() * esize(dtype), UNCOUNTED));
+        return rl::upload_as(dtype, v, *p);
+    }
     // H_t views summed before the inverse transforms (one clamp of the sum instead of one per
     // view, ref:587): default for f32 plans, off for f64 (faithful); RLSTED_FUSE_VIEWS=0/1 overrides
     bool fuse_views = false;
-    // Slices of the batch are independent: they are iterated on `lanes` HIP streams at once so that
-    // the tail of one slice's kernel (the last, partly filled round of workgroups) overlaps another
-    // slice's kernels.  RLSTED_LANES=1: one slice after the other on the context's stream.
-    static constexpr int kMaxLanes = 4;
-    int lanes = 2;
     hipStream_t lane_stream[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t lane_done[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t fork = nullptr;
     hipStream_t active = nullptr;                     // stream the kernel launch helpers use
-    bool defer_join = false, lanes_open = false;      // rl_deconv_bench_cycles: no lane join between its cycles
-    void* slice_ws = nullptr;                         // per-slice Poisson work lists of run_cycle()
+    bool lanes_open = false;                          // the lanes were left unjoined: between the back-to-back cycles of rl_deconv_bench_cycles
+    void* slice_ws = nullptr;                         // per-slice Poisson work lists of run_slices()
     void *key_seeds = nullptr, *key_ids = nullptr;    // per-frame Philox keys of rl_deconv_simulate_keyed
     size_t slice_ws_bytes = 0, slice_ws_stride = 0;
     // ---- rl_batch_submit: the tasks of a chunk -- objects, brightness targets, Philox keys -- are staged in one page-locked
@@ -139,8 +247,6 @@ struct rl_deconv {
     size_t batch_out_bytes = 0;
     hipStream_t copy_stream = nullptr;
     unsigned long batch_chunks = 0;
-    const unsigned long long* run_key_seeds = nullptr;   // keyed Poisson draws of run_slices (device, [B]); nullptr: one seed
-    const unsigned* run_key_ids = nullptr;
     size_t slot_objects_bytes() const { return (size_t)B * n_img() * sizeof(double); }
     size_t slot_header_bytes() const { return ((size_t)B * (8 + 8 + 4 + 4) + 15) / 16 * 16; }
     size_t slot_host_bytes() const { return slot_header_bytes() + slot_objects_bytes(); }
@@ -151,10 +257,7 @@ struct rl_deconv {
         if (!copy_stream) HIP_TRY(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
         for (BatchSlot& sl : bslot) {
             if (!sl.host) HIP_TRY(hipHostMalloc((void**)&sl.host, slot_host_bytes(), hipHostMallocDefault));
-            if (!sl.dev) {
-                HIP_TRY(hipMalloc((void**)&sl.dev, slot_host_bytes() + 8 + aux_sums_elems((size_t)B) * sizeof(double)));
-                bytes += slot_host_bytes() + 8 + aux_sums_elems((size_t)B) * sizeof(double);
-            }
+            if (!sl.dev) RL_TRY(alloc(&sl.dev, slot_host_bytes() + 8 + aux_sums_elems((size_t)B) * sizeof(double)));
             if (!sl.uploaded) HIP_TRY(hipEventCreateWithFlags(&sl.uploaded, hipEventDisableTiming));
             if (!sl.freed) HIP_TRY(hipEventCreateWithFlags(&sl.freed, hipEventDisableTiming));
         }
@@ -162,11 +265,6 @@ struct rl_deconv {
         return RL_OK;
     }
     hipStream_t cur() const { return active ? active : ctx->stream; }
-    // column kernel work order: images per block of the tile order (fft_kernels.hip k_colconv):
-    // 1 image-major ... >= images per launch: tile-major (RLSTED_COL_ORDER).  Measured at 512^2, 32-frame
-    // slices: 1: 16.80 k, 2: 16.88 k, 4: 16.98 k, 8: 16.81 k, 32: 16.56 k frames/s.
-    int col_order = 4;
-    bool inplace = true;     // single-view RL iterations entirely in spec_a (RLSTED_INPLACE=0: spec_a -> spec_b -> spec_a)
     bool est_ready = false;    // est holds a valid estimate
     // ---- Biggs-Andrews acceleration (accel_kernels.hpp, rl_deconv_set_acceleration): per frame the previous point x_{k-1}, the
     // extrapolated point y_k and the step g_k in three image buffers, the dot products' per-workgroup partials and the a of the
@@ -180,18 +278,11 @@ struct rl_deconv {
     int ensure_accel() {
         const size_t img = (size_t)B * n_img() * esize(dtype), part = (size_t)B * acc_blocks() * 2 * sizeof(double);
         for (void** p : {&acc_x, &acc_y, &acc_g})
-            if (!*p) {
-                HIP_TRY(hipMalloc(p, img));
-                bytes += img;
-            }
-        if (!acc_part) {
-            HIP_TRY(hipMalloc((void**)&acc_part, part));
-            bytes += part;
-        }
+            if (!*p) RL_TRY(alloc(p, img));
+        if (!acc_part) RL_TRY(alloc(&acc_part, part));
         if (!acc_alpha) {
-            HIP_TRY(hipMalloc((void**)&acc_alpha, (size_t)B * sizeof(double)));
+            RL_TRY(alloc(&acc_alpha, (size_t)B * sizeof(double)));
             HIP_TRY(hipMemsetAsync(acc_alpha, 0, (size_t)B * sizeof(double), ctx->stream));
-            bytes += (size_t)B * sizeof(double);
         }
         return RL_OK;
     }
@@ -212,10 +303,7 @@ struct rl_deconv {
             if (pair) RL_TRY(row_pair(ROW_FWD, nf, nullptr, pair_spec(f0), off(est, o), nullptr, nullptr));
             else if (!sep) RL_TRY(row(ROW_FWD, (unsigned)nf, nullptr, off(spec_a, (size_t)f0 * n_spec() * 2), off(est, o), nullptr, nullptr));
         }
-        drop_last_spectrum = pair;
-        const int rc = iterate_chunk(f0, nf, first, from_ones);
-        drop_last_spectrum = false;
-        RL_TRY(rc);
+        RL_TRY(iterate_chunk({f0, nf, first, from_ones, /* drop_spectrum */ pair}));
         HIP_TRY(accel_reduce(dtype, off(est, o), off(acc_y, o), off(acc_g, o), part, n_img(), nf,
                              (from_ones ? ACC_Y_ONES : 0) | (s > 0 ? ACC_HAVE_PREV : 0), cur()));
         return RL_OK;
@@ -226,6 +314,17 @@ struct rl_deconv {
     double last_iter_ms = 0, last_sim_ms = 0;
 
     enum ColKind { COL_H, COL_HT_VIEW, COL_HT_FUSED };
+    // One Richardson-Lucy iteration on frames [f0, f0 + nf), as its four passes and their launches are told of it.
+    // first: the estimate is 1 (just filled) -- H(estimate) is spec_ones for every frame, so the column pass of H is skipped and
+    //   ROW_RATIO reads the shared spectra (bit for bit what the pass would write);
+    // from_ones: (study builds) the ratio of the iteration that starts from estimate = 1 is measurement / H(1), data scale: its
+    //   ratio-type spectra carry q_est;
+    // drop_spectrum: ROW_UPDATE does not transform the new estimate forward again (pair loop: the last iteration of a long run).
+    struct Iter { int f0, nf; bool first, from_ones, drop_spectrum; };
+    // scale of a ratio-type spectrum (ROW_RATIO's output, the H_t columns' input); it == nullptr: a launch outside the loop (rl_adjoint)
+    float ratio_scale(const Iter* it) const { return it && it->from_ones ? q_est : q_ratio; }
+    // H_t inside a `ratio - 1` iteration: the spectra of residuals (rl_adjoint's input is an image)
+    bool residual(ColKind kind, const Iter* it) const { return it && kind != COL_H && sub(); }
     // ---- frame pairs (conv_kernels.hpp rowpair_body; RLSTED_PAIR): two frames ride through one complex image, the
     // Richardson-Lucy loop of a single-view plan then runs on spectra [pairs][ny][lx] -- no Hermitian packing /
     // splitting around the row transforms.  The simulation and the H / H_t calls keep the per-frame layout.
@@ -235,14 +334,13 @@ struct rl_deconv {
     // next to one 1e5 times brighter would carry ~1e5 times its own error through H.  Frames are paired only while every
     // pair's levels (sums of the object / measurement images) are within kPairMaxRatio of each other
     // (RLSTED_PAIR_MAX_RATIO); otherwise the plan runs its per-frame loop, which every pair plan also holds.
-    double pair_max_ratio = 4.0;
     std::vector<double> obj_level, meas_level;   // per frame (host): sum of the object / of the measurement over its views
     bool levels_ok(const std::vector<double>& lv) const {
         if ((int)lv.size() != B) return true;    // nothing known yet
         for (int f = 0; f + 1 < B; f += 2) {
             const double lo = std::min(lv[f], lv[f + 1]), hi = std::max(lv[f], lv[f + 1]);
             if (lo == 0.0 && hi == 0.0) continue;   // two empty frames
-            if (!(lo > 0.0) || !std::isfinite(hi) || hi > pair_max_ratio * lo) return false;
+            if (!(lo > 0.0) || !std::isfinite(hi) || hi > opt.pair_max_ratio * lo) return false;
         }
         return true;
     }
@@ -282,74 +380,108 @@ struct rl_deconv {
         meas_negative = flag != 0;
         return RL_OK;
     }
-    bool keep_last_spectrum = false;   // RLSTED_KEEP_LAST_SPECTRUM=1: every iteration ends with rowFFT(estimate)
-    bool drop_last_spectrum = false;   // set by run_slices for the last iteration of a long run: ROW_UPDATE skips rowFFT(estimate)
     void *psf_hat_pair = nullptr, *psf_hat_pair_re = nullptr;   // psf_hat at full width: [lx][ly] (transposed layout)
     void* spec_ones_pair = nullptr;                              // column-transformed spectrum of a pair of ones frames
     // Row pitch of a pair spectrum (complex elements): lx, or lx + 32 for the long rows (lx >= 1152).  A pitch of exactly lx
     // makes the row stride (lx * 8 bytes in f32: 18432 / 36864) an EVEN multiple of 256 bytes, and the column kernels' tile
     // rows -- one 64-byte segment per row -- then fall on a fraction of the memory channels; + 256 bytes makes it an odd
-    // multiple (RLSTED_PAIR_PAD columns).  Worth 2-4 % on the long rows, costs 3 % at lx = 576 (4608-byte rows: left alone).
+    // multiple.  Worth 2-4 % on the long rows, costs 3 % at lx = 576 (4608-byte rows: left alone).
     int pair_pitch = 0;
     size_t n_spec_pair() const { return spec_image_elems(ny, pair_pitch); }
     void* pair_spec(int f0) const { return (char*)spec_a + (size_t)(f0 / 2) * n_spec_pair() * 2 * esize(dtype); }
-    // kind: COL_H (pair spectrum -> V images; in place when V == 1), COL_HT_VIEW (V == 1, in place) or COL_HT_FUSED
-    // (V images summed in the Fourier domain -> pair spectrum)
+    // ---- column / row launches.  Layout of the spectra: HALF -- per frame, [ny][pitch] with kx columns -- or PAIR -- two frames in
+    // one complex image, [ny][pair_pitch] with lx columns.
+    enum Layout { HALF, PAIR };
+    // what the column launches share; in_sb / in_sv / order / residual / xs_in / xs_out are their callers' to change
     template <typename T>
-    int col_pair_t(const void* in, void* out, int pairs, ColKind kind) {
+    ColParams<T> col_params(Layout lay, ColKind kind, int mode, const void* in, void* out, int images, const Iter* it) {
         ColParams<T> p;
         p.in = (const cx<T>*)in;
         p.out = (cx<T>*)out;
-        p.psf_hat = (const cx<T>*)psf_hat_pair;
-        p.psf_hat_re = (const T*)psf_hat_pair_re;
-        p.qscale = kind == COL_H ? q_est : q_ratio;
+        p.psf_hat = (const cx<T>*)(lay == PAIR ? psf_hat_pair : psf_hat);
+        p.psf_hat_re = (const T*)(lay == PAIR ? psf_hat_pair_re : psf_hat_re);
+        p.qscale = kind == COL_H ? q_est : ratio_scale(it);
         p.tw = (const cx<T>*)twy;
-        p.ny = ny; p.kx = lx; p.pitch = pair_pitch; p.V = V;
-        p.mode = V == 1 ? COL_PER_IMAGE : (kind == COL_H ? COL_H_MULTI : COL_HT_SUM);
+        p.ny = ny; p.kx = lay == PAIR ? lx : kx; p.pitch = lay == PAIR ? pair_pitch : pitch; p.V = V;
+        p.mode = mode;
         p.in_sb = 1; p.in_sv = 0;
-        p.images = pairs; p.order = col_order;
-        p.residual = (kind != COL_H && sub() && in_rl_loop) ? 1 : 0;   // H_t inside a `ratio - 1` iteration: the spectrum of a residual
+        p.images = images;
+        p.order = opt.col_order;
+        return p;
+    }
+    // grid: the tiles of p.kx columns x p.images.  cont: second launch of one pass (TimedLaunch)
+    template <typename T>
+    int launch_col(const ColParams<T>& p, ColKind kind, bool cont = false) {
         const int C = ty->C[dtype];
-        TimedScope t(this, kind == COL_H ? TK_COL_H : TK_COL_HT);
-        HIP_TRY(ty->launch_col(dtype, &p, (unsigned)((lx + C - 1) / C), (unsigned)pairs, cur()));
+        const unsigned gx = (unsigned)((p.kx + C - 1) / C), gy = (unsigned)p.images;
+        {
+            TimedScope t(this, kind == COL_H ? TK_COL_H : TK_COL_HT, true, cont);
+            HIP_TRY(ty->launch_col(dtype, &p, gx, gy, cur()));
+        }
+        if (rl::debug_sync()) {
+            hipError_t e = hipStreamSynchronize(cur());
+            if (e != hipSuccess)
+                return fail(RL_ERR_HIP, "column kernel L=" + std::to_string(ly) + " mode " + std::to_string(p.mode) + " grid " +
+                                            std::to_string(gx) + "x" + std::to_string(gy) + ": " + hipGetErrorString(e));
+        }
         return RL_OK;
     }
-    int col_pair(const void* in, void* out, int pairs, ColKind kind) {
+    // kind: COL_H (pair spectrum -> V images; in place when V == 1), COL_HT_VIEW (V == 1, in place) or COL_HT_FUSED
+    // (V images summed in the Fourier domain -> pair spectrum)
+    template <typename T>
+    int col_pair_t(const void* in, void* out, int pairs, ColKind kind, const Iter* it) {
+        ColParams<T> p = col_params<T>(PAIR, kind, V == 1 ? COL_PER_IMAGE : (kind == COL_H ? COL_H_MULTI : COL_HT_SUM), in, out, pairs, it);
+        p.residual = residual(kind, it) ? 1 : 0;
+        return launch_col(p, kind);
+    }
+    int col_pair(const void* in, void* out, int pairs, ColKind kind, const Iter* it = nullptr) {
         const size_t sp = n_spec_pair() * 2 * esize(dtype);
         const size_t in_per = kind == COL_H ? 1 : (size_t)V, out_per = kind == COL_H ? (size_t)V : 1;
         for (int p0 = 0; p0 < pairs; p0 += kMaxGridY) {
             const int np = std::min((int)kMaxGridY, pairs - p0);
             const void* i = (const char*)in + (size_t)p0 * in_per * sp;
             void* o = (char*)out + (size_t)p0 * out_per * sp;
-            RL_TRY(dtype == RL_F32 ? col_pair_t<float>(i, o, np, kind) : col_pair_t<double>(i, o, np, kind));
+            RL_TRY(dtype == RL_F32 ? col_pair_t<float>(i, o, np, kind, it) : col_pair_t<double>(i, o, np, kind, it));
         }
         return RL_OK;
     }
-    int col_pair(void* io, int pairs, bool h_mode) { return col_pair(io, io, pairs, h_mode ? COL_H : COL_HT_VIEW); }
-    // frames: images covered (even, or the batch's last odd one); spectra and images start at the launch's first pair
+    // One row launch.  HALF: `images` launch rows (grid.y).  PAIR: `images` frames (even, or the batch's last odd one), a launch row
+    // per (pair, view); spectra and images start at the launch's first pair.
     template <typename T>
-    int row_pair_t(int mode, int frames, const void* spec_in, void* spec_out, const void* src, void* dst, const void* nrm, int in_mod, int views) {
+    int row_t(Layout lay, int mode, int images, const void* spec_in, void* spec_out, const void* src, void* dst, const void* nrm,
+              const void* scale, int views, int in_mod, const Iter* it) {
         RowParams<T> p;
         p.in_mod = in_mod;
         p.sub_one = sub() ? 1 : 0;
         p.unresolved = unresolved;
-        p.qscale = mode == ROW_RATIO ? q_ratio : q_est;
+        p.qscale = mode == ROW_RATIO ? ratio_scale(it) : q_est;
         p.spec_in = (const cx<T>*)spec_in;
         p.spec_out = (cx<T>*)spec_out;
         p.src = (const T*)src;
         p.dst = (T*)dst;
         p.norm = (const T*)nrm;
-        p.scale = nullptr;
+        p.scale = (const T*)scale;
         p.tw = (const cx<T>*)twx;
-        p.ny = ny; p.nx = nx; p.pitch = pair_pitch; p.V = views;
-        p.frames = frames;
-        TimedScope t(this, mode == ROW_RATIO ? TK_RATIO : mode == ROW_UPDATE ? TK_UPDATE : TK_FWD);
-        HIP_TRY(tx->launch_row_pair(dtype, mode, &p, (unsigned)((frames + 1) / 2 * views), cur()));
+        p.ny = ny; p.nx = nx; p.pitch = lay == PAIR ? pair_pitch : pitch; p.V = views;
+        p.frames = images;
+        const int Q = tx->Q[dtype];
+        const unsigned gx = (unsigned)(((ny + 1) / 2 + Q - 1) / Q), gy = (unsigned)(lay == PAIR ? (images + 1) / 2 * views : images);
+        {
+            TimedScope t(this, mode == ROW_RATIO ? TK_RATIO : mode == ROW_UPDATE ? TK_UPDATE : mode == ROW_FWD ? TK_FWD : TK_INV);
+            HIP_TRY(lay == PAIR ? tx->launch_row_pair(dtype, mode, &p, gy, cur()) : tx->launch_row(dtype, mode, &p, gx, gy, cur()));
+        }
+        if (rl::debug_sync()) {
+            hipError_t e = hipStreamSynchronize(cur());
+            if (e != hipSuccess)
+                return fail(RL_ERR_HIP, std::string(lay == PAIR ? "pair " : "") + "row kernel mode " + std::to_string(mode) + " L=" +
+                                            std::to_string(lx) + " grid " + std::to_string(lay == PAIR ? 1u : gx) + "x" + std::to_string(gy) +
+                                            ": " + hipGetErrorString(e));
+        }
         return RL_OK;
     }
     // views > 1 (ROW_RATIO of a multi-view plan): one launch image per (pair, view); spectra [pair][view], images [frame][view]
     int row_pair(int mode, int frames, const void* spec_in, void* spec_out, const void* src, void* dst, const void* nrm, int in_mod = 0,
-                 int views = 1) {
+                 int views = 1, const Iter* it = nullptr) {
         const size_t sp = n_spec_pair() * 2 * esize(dtype), im = n_img() * esize(dtype);
         const int step = 2 * ((int)kMaxGridY / views);
         for (int f0 = 0; f0 < frames; f0 += step) {
@@ -358,14 +490,14 @@ struct rl_deconv {
             void* so = spec_out ? (char*)spec_out + (size_t)(f0 / 2) * views * sp : nullptr;
             const void* sr = src ? (const char*)src + (size_t)f0 * views * im : nullptr;
             void* ds = dst ? (char*)dst + (size_t)f0 * im : nullptr;
-            RL_TRY(dtype == RL_F32 ? row_pair_t<float>(mode, nf, si, so, sr, ds, nrm, in_mod, views)
-                                   : row_pair_t<double>(mode, nf, si, so, sr, ds, nrm, in_mod, views));
+            RL_TRY(dtype == RL_F32 ? row_t<float>(PAIR, mode, nf, si, so, sr, ds, nrm, nullptr, views, in_mod, it)
+                                   : row_t<double>(PAIR, mode, nf, si, so, sr, ds, nrm, nullptr, views, in_mod, it));
         }
         return RL_OK;
     }
 
     // ---- separable strategy (sep_kernels.hip): every view rank 1 (p = u v^T) and small -> direct row + column stencils
-    // instead of the FFT path.  RLSTED_SEP: 0 never, 1 (default) when py + px <= RLSTED_SEP_MAX_TAPS (16: the measured
+    // instead of the FFT path.  RLSTED_SEP: 0 never, 1 (default) when py + px <= 16 (the measured
     // crossover, profiles/r02/separable_vs_fft.json -- the FFT path's cost does not depend on the PSF size), 2 whenever rank 1.
     bool sep = false;
     void *sep_u = nullptr, *sep_v = nullptr;   // [V][py], [V][px] in the plan's dtype
@@ -403,11 +535,11 @@ struct rl_deconv {
         }
         return RL_OK;
     }
-    // H of nf frames: x [nf] -> out [nf*V] (clamped)
-    int sep_forward(const void* x, void* out, int nf) {
+    // H of nf frames: x [nf] -> out [nf*V] (clamped); tmp: the row-pass results of these frames (their part of sep_tmp())
+    int sep_forward(const void* x, void* out, void* tmp, int nf) {
         if (sep_one) return sep2d_(SEP_STORE_, x, nullptr, nullptr, out, nf);
-        RL_TRY(sep_rows_(x, sep_tmp(), nf * V, V));
-        return sep_cols_(SEP_STORE_, sep_tmp(), nullptr, nullptr, out, nf * V);
+        RL_TRY(sep_rows_(x, tmp, nf * V, V));
+        return sep_cols_(SEP_STORE_, tmp, nullptr, nullptr, out, nf * V);
     }
     int sep_iterate(int f0, int nf) {   // ref:520-531
         void* e = off(est, (size_t)f0 * n_img());
@@ -469,108 +601,67 @@ struct rl_deconv {
     size_t n_img() const { return (size_t)ny * nx; }
     size_t n_spec() const { return spec_image_elems(ny, pitch); }   // complex elements of one spectrum image
 
-    bool col_multi = true;   // RLSTED_COL_MULTI=0 (A/B knob): V per-image column launches even where the multi-view modes exist
-    // KernelTable::col_multi: bit 0 COL_H_MULTI, bit 1 COL_HT_SUM.  wave_private_y(): the Fourier-domain view sum exists (and is wanted)
-    bool wave_private_y() const { return col_multi && (ty->col_multi[dtype] & 2) != 0; }
-    bool h_multi() const { return col_multi && (ty->col_multi[dtype] & 1) != 0; }
+    // KernelTable::col_multi: bit 0 COL_H_MULTI, bit 1 COL_HT_SUM (a table without them: V per-image column launches).
+    // wave_private_y(): the Fourier-domain view sum exists
+    bool wave_private_y() const { return (ty->col_multi[dtype] & 2) != 0; }
+    bool h_multi() const { return (ty->col_multi[dtype] & 1) != 0; }
     // The split column pass (conv_kernels.hpp COL_SPLIT_*; f32 multi-view plans on the long column transforms): H transforms a frame's
-    // spectrum once for its V views, H_t sums the views' products before one inverse transform (RLSTED_COL_SPLIT=0: A/B knob)
-    bool split_wanted = true;
-    bool split_ht = true;    // H_t through the split pass (RLSTED_SPLIT_HT=0: V whole-pass launches + the pre-summed update; measured)
-    bool split_h = true;     // H through the split pass too (RLSTED_SPLIT_H=0: H_t only -- measured in round 4)
-    bool col_split() const { return split_wanted && dtype == RL_F32 && V > 1 && ty->split_tile_elems > 0; }
+    // spectrum once for its V views, H_t sums the views' products before one inverse transform (RLSTED_COL_SPLIT=0: A/B knob).
+    // H goes through it from three views on: with two the forward half saved (1 + V against 2 V column transforms) does not pay
+    // for parking the spectrum -- measured, 2048^2: 2 views 429 (split) against 449 frames/s, 4 views 269 against 258 (DESIGN.md section 3)
+    bool split_h() const { return V >= 3; }
+    bool col_split() const { return opt.col_split && dtype == RL_F32 && V > 1 && ty->split_tile_elems > 0; }
     size_t n_spec_x() const { return (size_t)((kx + ty->C[RL_F32] - 1) / ty->C[RL_F32]) * ty->split_tile_elems; }
     // one half of the split pass over `images` launch rows
-    int col_split_launch(int mode, const void* in, void* out, const void* xs_in, void* xs_out, int images, int in_sb, int in_sv, ColKind kind,
-                         bool cont) {
-        ColParams<float> p;
-        p.in = (const cx<float>*)in;
-        p.out = (cx<float>*)out;
+    int col_split_launch(int mode, const void* in, void* out, const void* xs_in, void* xs_out, int images, ColKind kind, bool cont,
+                         const Iter* it) {
+        ColParams<float> p = col_params<float>(HALF, kind, mode, in, out, images, it);
         p.xs_in = (const cx<float>*)xs_in;
         p.xs_out = (cx<float>*)xs_out;
-        p.psf_hat = (const cx<float>*)psf_hat;
-        p.psf_hat_re = (const float*)psf_hat_re;
-        p.qscale = kind == COL_H ? q_est : q_ratio;
-        p.tw = (const cx<float>*)twy;
-        p.ny = ny; p.kx = kx; p.pitch = pitch; p.V = V;
-        p.mode = mode;
-        p.in_sb = in_sb; p.in_sv = in_sv;
-        p.images = images;
         p.order = 1;
-        const int C = ty->C[dtype];
-        {
-            TimedScope t(this, kind == COL_H ? TK_COL_H : TK_COL_HT, true, cont);
-            HIP_TRY(ty->launch_col(dtype, &p, (unsigned)((kx + C - 1) / C), (unsigned)images, cur()));
-        }
-        if (rl::debug_sync()) {
-            hipError_t e = hipStreamSynchronize(cur());
-            if (e != hipSuccess) return fail(RL_ERR_HIP, "split column kernel mode " + std::to_string(mode) + ": " + hipGetErrorString(e));
-        }
-        return RL_OK;
+        return launch_col(p, kind, cont);
     }
     // kind COL_H: `in` = the frames' spectra -> out = frames * V images; COL_HT_FUSED: in = frames * V images -> out = frames
     // xs: this slice's part of spec_x (frames * V images of n_spec_x() elements)
-    int col_split_pass(const void* in, void* out, void* xs, int frames, ColKind kind) {
+    int col_split_pass(const void* in, void* out, void* xs, int frames, ColKind kind, const Iter* it = nullptr) {
         const size_t sp = n_spec() * 2 * sizeof(float), sx = n_spec_x() * 2 * sizeof(float);
         const int step = std::max(1, kMaxGridY / V);
         for (int f0 = 0; f0 < frames; f0 += step) {
             const int nf = std::min(step, frames - f0);
             void* x = (char*)xs + (size_t)f0 * V * sx;
             if (kind == COL_H) {
-                RL_TRY(col_split_launch(COL_SPLIT_FWD, (const char*)in + (size_t)f0 * sp, nullptr, nullptr, x, nf, 1, 0, kind, false));
-                RL_TRY(col_split_launch(COL_SPLIT_INV, nullptr, (char*)out + (size_t)f0 * V * sp, x, nullptr, nf * V, 1, 0, kind, true));
+                RL_TRY(col_split_launch(COL_SPLIT_FWD, (const char*)in + (size_t)f0 * sp, nullptr, nullptr, x, nf, kind, false, it));
+                RL_TRY(col_split_launch(COL_SPLIT_INV, nullptr, (char*)out + (size_t)f0 * V * sp, x, nullptr, nf * V, kind, true, it));
             } else {
-                RL_TRY(col_split_launch(COL_SPLIT_FWD, (const char*)in + (size_t)f0 * V * sp, nullptr, nullptr, x, nf * V, 1, 0, kind, false));
-                RL_TRY(col_split_launch(COL_SPLIT_INV_SUM, nullptr, (char*)out + (size_t)f0 * sp, x, nullptr, nf, 1, 0, kind, true));
+                RL_TRY(col_split_launch(COL_SPLIT_FWD, (const char*)in + (size_t)f0 * V * sp, nullptr, nullptr, x, nf * V, kind, false, it));
+                RL_TRY(col_split_launch(COL_SPLIT_INV_SUM, nullptr, (char*)out + (size_t)f0 * sp, x, nullptr, nf, kind, true, it));
             }
         }
         return RL_OK;
     }
     bool psf_transposed() const { return ty->psf_transposed[dtype] != 0; }   // psf_hat is [view][Kx][Ly]
     template <typename T>
-    int col_t(const void* in, void* out, int frames, ColKind kind) {
-        ColParams<T> p;
-        p.in = (const cx<T>*)in;
-        p.out = (cx<T>*)out;
-        p.psf_hat = (const cx<T>*)psf_hat;
-        p.psf_hat_re = (const T*)psf_hat_re;
-        p.qscale = kind == COL_H ? q_est : q_ratio;
-        p.tw = (const cx<T>*)twy;
-        p.ny = ny; p.kx = kx; p.pitch = pitch; p.V = V;
-        unsigned gy = (unsigned)(frames * V);
-        p.mode = COL_PER_IMAGE;
-        p.in_sb = kind == COL_H ? 1 : V;
-        p.in_sv = kind == COL_H ? 0 : 1;
+    int col_t(const void* in, void* out, int frames, ColKind kind, const Iter* it) {
+        int mode = COL_PER_IMAGE, gy = frames * V;
         if (V > 1 && kind == COL_H && h_multi()) {
-            p.mode = COL_H_MULTI;
-            gy = (unsigned)frames;
+            mode = COL_H_MULTI;
+            gy = frames;
         } else if (V > 1 && kind == COL_HT_FUSED && wave_private_y()) {
-            p.mode = COL_HT_SUM;
-            gy = (unsigned)frames;
+            mode = COL_HT_SUM;
+            gy = frames;
         } else if (kind == COL_HT_FUSED && V > 1) {
             return fail(RL_ERR_STATE, "internal: fused H_t needs a wave-private column transform");
         }
-        const int C = ty->C[dtype];
-        const unsigned gx = (unsigned)((kx + C - 1) / C);
-        p.images = (int)gy;
-        p.order = col_order;
-        p.residual = (kind != COL_H && sub() && in_rl_loop) ? 1 : 0;   // H_t inside a `ratio - 1` iteration: the spectra of residuals
-        {
-            TimedScope t(this, kind == COL_H ? TK_COL_H : TK_COL_HT);
-            HIP_TRY(ty->launch_col(dtype, &p, gx, gy, cur()));
-        }
-        if (rl::debug_sync()) {
-            hipError_t e = hipStreamSynchronize(cur());
-            if (e != hipSuccess)
-                return fail(RL_ERR_HIP, "column kernel L=" + std::to_string(ly) + " grid " + std::to_string(gx) + "x" +
-                                            std::to_string(gy) + ": " + hipGetErrorString(e));
-        }
-        return RL_OK;
+        ColParams<T> p = col_params<T>(HALF, kind, mode, in, out, gy, it);
+        p.in_sb = kind == COL_H ? 1 : V;
+        p.in_sv = kind == COL_H ? 0 : 1;
+        p.residual = residual(kind, it) ? 1 : 0;
+        return launch_col(p, kind);
     }
     // grid.y carries the image index of a launch: at most kMaxGridY images per launch, larger batches
     // are launched in pieces (whole frames each) with the pointers moved on
     static constexpr int kMaxGridY = 65535;
-    int col(const void* in, void* out, int frames, ColKind kind) {
+    int col(const void* in, void* out, int frames, ColKind kind, const Iter* it = nullptr) {
         const size_t sp = n_spec() * 2 * esize(dtype);   // bytes of one spectrum image
         const size_t in_per = kind == COL_H ? 1 : (size_t)V, out_per = kind == COL_HT_FUSED ? 1 : (size_t)V;
         const int step = std::max(1, kMaxGridY / V);
@@ -578,45 +669,12 @@ struct rl_deconv {
             const int nf = std::min(step, frames - f0);
             const void* i = (const char*)in + (size_t)f0 * in_per * sp;
             void* o = (char*)out + (size_t)f0 * out_per * sp;
-            RL_TRY(dtype == RL_F32 ? col_t<float>(i, o, nf, kind) : col_t<double>(i, o, nf, kind));
-        }
-        return RL_OK;
-    }
-    int col(const void* in, void* out, int frames, bool h_mode) { return col(in, out, frames, h_mode ? COL_H : COL_HT_VIEW); }
-    template <typename T>
-    int row_t(int mode, unsigned gy, const void* spec_in, void* spec_out, const void* src, void* dst, const void* nrm,
-              const void* scale, int views, int in_mod = 0) {
-        RowParams<T> p;
-        p.in_mod = in_mod;
-        p.sub_one = sub() ? 1 : 0;
-        p.unresolved = unresolved;
-        p.qscale = mode == ROW_RATIO ? q_ratio : q_est;
-        p.spec_in = (const cx<T>*)spec_in;
-        p.spec_out = (cx<T>*)spec_out;
-        p.src = (const T*)src;
-        p.dst = (T*)dst;
-        p.norm = (const T*)nrm;
-        p.scale = (const T*)scale;
-        p.tw = (const cx<T>*)twx;
-        p.ny = ny; p.nx = nx; p.pitch = pitch; p.V = views;
-        const int Q = tx->Q[dtype];
-        const unsigned pairs = (unsigned)((ny + 1) / 2);
-        p.frames = (int)gy;
-        {
-            TimedScope t(this, mode == ROW_RATIO ? TK_RATIO : mode == ROW_UPDATE ? TK_UPDATE : mode == ROW_FWD ? TK_FWD : TK_INV);
-            HIP_TRY(tx->launch_row(dtype, mode, &p, (pairs + Q - 1) / Q, gy, cur()));
-        }
-        if (rl::debug_sync()) {
-            hipError_t e = hipStreamSynchronize(cur());
-            if (e != hipSuccess)
-                return fail(RL_ERR_HIP, "row kernel mode " + std::to_string(mode) + " L=" + std::to_string(lx) + " grid " +
-                                            std::to_string((pairs + Q - 1) / Q) + "x" + std::to_string(gy) + ": " +
-                                            hipGetErrorString(e));
+            RL_TRY(dtype == RL_F32 ? col_t<float>(i, o, nf, kind, it) : col_t<double>(i, o, nf, kind, it));
         }
         return RL_OK;
     }
     int row(int mode, unsigned gy, const void* spec_in, void* spec_out, const void* src, void* dst, const void* nrm,
-            const void* scale = nullptr, int views = -1, int in_mod = 0) {
+            const void* scale = nullptr, int views = -1, int in_mod = 0, const Iter* it = nullptr) {
         if (views < 0) views = V;
         const size_t sp = n_spec() * 2 * esize(dtype), im = n_img() * esize(dtype);
         const bool multi = mode == ROW_UPDATE || mode == ROW_ADJ;   // `views` input spectra per image
@@ -630,8 +688,8 @@ struct rl_deconv {
             const void* sr = src ? (const char*)src + (size_t)g0 * im : nullptr;
             void* ds = dst ? (char*)dst + (size_t)g0 * im : nullptr;
             const void* sc = scale ? (const char*)scale + (size_t)g0 * esize(dtype) : nullptr;
-            RL_TRY(dtype == RL_F32 ? row_t<float>(mode, ng, si, so, sr, ds, nrm, sc, views, in_mod)
-                                   : row_t<double>(mode, ng, si, so, sr, ds, nrm, sc, views, in_mod));
+            RL_TRY(dtype == RL_F32 ? row_t<float>(HALF, mode, (int)ng, si, so, sr, ds, nrm, sc, views, in_mod, it)
+                                   : row_t<double>(HALF, mode, (int)ng, si, so, sr, ds, nrm, sc, views, in_mod, it));
         }
         return RL_OK;
     }
@@ -647,10 +705,9 @@ struct rl_deconv {
     int ensure_stage() {
         if (stage_dev) return RL_OK;
         kStageElems = std::max(n_img(), std::min(kStageMax, (size_t)B * V * n_img()));
-        HIP_TRY(hipMalloc((void**)&stage_dev, kStageElems * sizeof(double)));
-        HIP_TRY(hipMalloc((void**)&stage_aux, (size_t)B * sizeof(double)));
-        HIP_TRY(hipMalloc((void**)&stage_sums, aux_sums_elems((size_t)B * V) * sizeof(double)));
-        bytes += kStageElems * sizeof(double);
+        RL_TRY(alloc(&stage_dev, kStageElems * sizeof(double)));
+        RL_TRY(alloc(&stage_aux, (size_t)B * sizeof(double), UNCOUNTED));
+        RL_TRY(alloc(&stage_sums, aux_sums_elems((size_t)B * V) * sizeof(double), UNCOUNTED));
         return RL_OK;
     }
     // images: `count` images of n_img() pixels; target (host, per image) may be nullptr
@@ -692,33 +749,25 @@ struct rl_deconv {
         return RL_OK;
     }
 
-    // noiseless = H(obj) on the device
-    int forward_object() {
-        if (sep) return sep_forward(obj, noiseless, B);
-        RL_TRY(row(ROW_FWD, (unsigned)B, nullptr, spec_a, obj, nullptr, nullptr));
-        RL_TRY(col(spec_a, spec_b, B, true));
-        RL_TRY(row(ROW_INV, (unsigned)(B * V), spec_b, nullptr, nullptr, noiseless, nullptr));
-        return RL_OK;
-    }
     // ---- frame chunks: run the whole K-iteration loop on a slice of the batch whose
     // working set (spectra + measurement + estimate) fits the 256 MiB Infinity Cache,
     // so the inter-kernel traffic is served on die instead of from HBM.
     char* off(void* base, size_t elems) const { return (char*)base + elems * esize(dtype); }
     int chunk_frames() const {
         // per slice; `lanes` slices are in flight at once, together about the 256 MiB Infinity Cache
-        const double budget_mb = getenv("RLSTED_CHUNK_MB") ? atof(getenv("RLSTED_CHUNK_MB")) : (lanes > 1 ? 108.0 : 288.0);
-        const double specs = (V == 1 && inplace) ? 1.0 : 1.0 + V;   // spectra alive in an iteration
+        const double budget_mb = opt.chunk_mb_set ? opt.chunk_mb : (opt.lanes > 1 ? 108.0 : 288.0);
+        const double specs = one_buffer() ? 1.0 : 1.0 + V;   // spectra alive in an iteration
         const double per_frame = (specs * 2.0 * n_spec() + (1.0 + V + (accel ? 3.0 : 0.0)) * n_img()) * esize(dtype);   // (+ x, y, g)
         // Frames of 32 MB and more (2048^2 up) do not live in the Infinity Cache whatever the slice: there the slice
         // only has to fill the chip -- ~1 GB per slice measured best at 2048^2 (point 658 -> 713, 4 views 180 -> 192
         // frames/s over 2-frame / 1-frame slices).
-        int c = (int)((!getenv("RLSTED_CHUNK_MB") && per_frame >= 32.0 * 1048576.0 ? 1024.0 : budget_mb) * 1048576.0 / per_frame);
+        int c = (int)((!opt.chunk_mb_set && per_frame >= 32.0 * 1048576.0 ? 1024.0 : budget_mb) * 1048576.0 / per_frame);
         // many views: at least 8 frames per slice when no budget was given -- fewer leave the column
         // kernels (37 workgroups per 512^2 frame) too small to fill the chip (6 / 8 views: +10 % / +7 %)
-        if (!getenv("RLSTED_CHUNK_MB") && c < 8 && per_frame * 8.0 <= 300.0 * 1048576.0) c = 8;
+        if (!opt.chunk_mb_set && c < 8 && per_frame * 8.0 <= 300.0 * 1048576.0) c = 8;
         // ... and enough frames for the column launches to fill the chip once (two 8-wave workgroups per CU): 512^2 has 37 column
         // tiles per frame, so 16 frames -- measured 3 / 4 views 6968 -> 7826 / 5840 -> 6100 frames/s over 8-frame slices
-        if (!getenv("RLSTED_CHUNK_MB") && V > 1) {
+        if (!opt.chunk_mb_set && V > 1) {
             const int cw = ty->C[dtype] > 0 ? ty->C[dtype] : 8, tiles = (kx + cw - 1) / cw;
             const int need = ((512 + tiles - 1) / tiles + 7) / 8 * 8;
             if (c < need && per_frame * need <= 300.0 * 1048576.0) c = need;
@@ -752,125 +801,79 @@ struct rl_deconv {
         if (fork) return RL_OK;
         HIP_TRY(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
         // (equal priorities: lane 0 at the highest stream priority and lane 1 at the lowest measured 17.2 k against 18.1 k frames/s)
-        for (int l = 0; l < lanes; ++l) {
+        for (int l = 0; l < opt.lanes; ++l) {
             HIP_TRY(hipStreamCreateWithFlags(&lane_stream[l], hipStreamNonBlocking));
             HIP_TRY(hipEventCreateWithFlags(&lane_done[l], hipEventDisableTiming));
         }
         return RL_OK;
     }
-    // first: the iteration starts from estimate = 1 (just filled): H(estimate) is spec_ones for every frame, so the
-    // column pass of H is skipped and ROW_RATIO reads the shared spectra (bit for bit what the pass would write)
-    int iterate_chunk(int f0, int nf, bool first = false, bool from_ones = false) {
-        // (study builds: the ratio of the iteration that starts from estimate = 1 is measurement / H(1), data scale)
-        struct ScaleGuard {
-            float& q; float keep;
-            ~ScaleGuard() { q = keep; }
-        } scale_guard{q_ratio, q_ratio};
-        struct LoopGuard {
-            bool& f;
-            ~LoopGuard() { f = false; }
-        } loop_guard{in_rl_loop};
-        in_rl_loop = true;
-        if (from_ones) q_ratio = q_est;
-        if (sep) return sep_iterate(f0, nf);
-        if (pair) {   // the whole iteration in the pair spectra, in place
-            void* sp = pair_spec(f0);
-            const int np = (nf + 1) / 2;
-            if (first) {
-                RL_TRY(row_pair(ROW_RATIO, nf, spec_ones_pair, sp, off(meas, (size_t)f0 * n_img()), nullptr, nullptr, 1));
-            } else {
-                RL_TRY(col_pair(sp, np, true));
-                RL_TRY(row_pair(ROW_RATIO, nf, sp, sp, off(meas, (size_t)f0 * n_img()), nullptr, nullptr));
-            }
-            RL_TRY(col_pair(sp, np, false));
-            RL_TRY(row_pair(ROW_UPDATE, nf, sp, drop_last_spectrum ? nullptr : sp, nullptr, off(est, (size_t)f0 * n_img()), norm));
-            return RL_OK;
-        }
-        void* sa = off(spec_a, (size_t)f0 * n_spec() * 2);
-        void* sb = off(spec_b, (size_t)f0 * V * n_spec() * 2);
-        if (first && V == 1 && inplace) {
-            RL_TRY(row(ROW_RATIO, (unsigned)nf, spec_ones, sa, off(meas, (size_t)f0 * n_img()), nullptr, nullptr, nullptr, -1, 1));
-            RL_TRY(col(sa, sa, nf, false));
-            RL_TRY(row(ROW_UPDATE, (unsigned)nf, sa, sa, nullptr, off(est, (size_t)f0 * n_img()), norm));
-            return RL_OK;
-        }
-        if (V == 1 && inplace) {
-            // one view: every pass maps a spectrum onto itself (a column tile / a row pair is read
-            // completely before it is written), so the whole iteration runs in spec_a -- a third
-            // less working set per frame for the Infinity Cache, and stores that hit lines just read
-            RL_TRY(col(sa, sa, nf, true));
-            RL_TRY(row(ROW_RATIO, (unsigned)nf, sa, sa, off(meas, (size_t)f0 * n_img()), nullptr, nullptr));
-            RL_TRY(col(sa, sa, nf, false));
-            RL_TRY(row(ROW_UPDATE, (unsigned)nf, sa, sa, nullptr, off(est, (size_t)f0 * n_img()), norm));
-            return RL_OK;
-        }
-        if (col_split()) {
-            // the split column pass: 1 + V and V + 1 column transforms per frame instead of 2 V and (fused) V + 1 on one register set
-            void* sx = off(spec_x, (size_t)f0 * V * n_spec_x() * 2);
-            if (first) {
-                RL_TRY(row(ROW_RATIO, (unsigned)(nf * V), spec_ones, sb, off(meas, (size_t)f0 * V * n_img()), nullptr, nullptr, nullptr, -1, V));
-            } else {
-                if (split_h) RL_TRY(col_split_pass(sa, sb, sx, nf, COL_H));
-                else RL_TRY(col(sa, sb, nf, true));          // (RLSTED_SPLIT_H=0: V whole-pass launches, nothing parked on this side)
-                RL_TRY(row(ROW_RATIO, (unsigned)(nf * V), sb, sb, off(meas, (size_t)f0 * V * n_img()), nullptr, nullptr));
-            }
-            if (fuse_views && split_ht) {
-                RL_TRY(col_split_pass(sb, sa, sx, nf, COL_HT_FUSED));
-                RL_TRY(row(ROW_UPDATE, (unsigned)nf, sa, sa, nullptr, off(est, (size_t)f0 * n_img()), norm, nullptr, 1));
-            } else {
-                RL_TRY(col(sb, sb, nf, false));
-                RL_TRY(row(ROW_UPDATE, (unsigned)nf, sb, sa, nullptr, off(est, (size_t)f0 * n_img()), norm));
-            }
-            return RL_OK;
-        }
-        if (first) {
-            RL_TRY(row(ROW_RATIO, (unsigned)(nf * V), spec_ones, sb, off(meas, (size_t)f0 * V * n_img()), nullptr, nullptr, nullptr, -1, V));
-        } else {
-            RL_TRY(col(sa, sb, nf, true));                                                                   // H(est), column part
-            RL_TRY(row(ROW_RATIO, (unsigned)(nf * V), sb, sb, off(meas, (size_t)f0 * V * n_img()), nullptr, nullptr));   // meas / H(est)
-        }
-        if (fuse_views && V > 1 && wave_private_y()) {
-            // views summed in the Fourier domain: one inverse column + one inverse row transform per frame
-            RL_TRY(col(sb, sa, nf, COL_HT_FUSED));
-            RL_TRY(row(ROW_UPDATE, (unsigned)nf, sa, sa, nullptr, off(est, (size_t)f0 * n_img()), norm, nullptr, 1));
-        } else {
-            RL_TRY(col(sb, sb, nf, false));                                                                  // H_t, column part
-            RL_TRY(row(ROW_UPDATE, (unsigned)nf, sb, sa, nullptr, off(est, (size_t)f0 * n_img()), norm));   // est *= H_t / norm
-        }
-        return RL_OK;
+    // ---- one iteration = four passes (stencil plans: sep_iterate).  Each pass picks its variant from the plan: the pair loop -- the
+    // whole iteration in the pair spectra, in place --, one buffer -- one view: every pass maps a spectrum onto itself (a column tile /
+    // a row pair is read completely before it is written), so the whole iteration runs in spec_a: a third less working set per frame
+    // for the Infinity Cache, and stores that hit lines just read -- or spec_a -> spec_b (V spectra per frame) -> spec_a.
+    bool one_buffer() const { return V == 1 && opt.inplace; }
+    void* est_spec(int f0) const { return pair ? pair_spec(f0) : off(spec_a, (size_t)f0 * n_spec() * 2); }   // rowFFT(estimate)
+    // H(estimate), then the ratios' spectra
+    void* ratio_spec(int f0) const { return pair || one_buffer() ? est_spec(f0) : off(spec_b, (size_t)f0 * V * n_spec() * 2); }
+    void* parked(int f0) const { return off(spec_x, (size_t)f0 * V * n_spec_x() * 2); }   // the slice's part of spec_x
+    // The H_t columns sum the views in the Fourier domain: one inverse column + one inverse row transform per frame, ROW_UPDATE reads
+    // one spectrum -- through the split pass (1 + V and V + 1 column transforms per frame instead of 2 V and V + 1 on one register set)
+    // or COL_HT_SUM.  Otherwise (f64 plans, RLSTED_FUSE_VIEWS=0) V per-view launches and the pre-summed update.
+    bool ht_fused() const { return fuse_views && V > 1 && (col_split() || wave_private_y()); }
+    int pass_h(const Iter& it) {        // H(estimate), column part
+        if (it.first) return RL_OK;
+        if (pair) return col_pair(est_spec(it.f0), ratio_spec(it.f0), (it.nf + 1) / 2, COL_H, &it);
+        if (col_split() && split_h()) return col_split_pass(est_spec(it.f0), ratio_spec(it.f0), parked(it.f0), it.nf, COL_H, &it);
+        return col(est_spec(it.f0), ratio_spec(it.f0), it.nf, COL_H, &it);   // (a split plan of two views: V whole-pass launches, nothing parked on this side)
     }
-    int start_estimate() {
-        RL_TRY(start_estimate_chunk(0, B));
-        est_ready = true;
-        spec_valid = true;
-        iterations = 0;
-        return RL_OK;
+    int pass_ratio(const Iter& it) {    // measurement / H(estimate)
+        void* r = ratio_spec(it.f0);
+        const void* m = off(meas, (size_t)it.f0 * V * n_img());
+        if (pair) return row_pair(ROW_RATIO, it.nf, it.first ? spec_ones_pair : r, r, m, nullptr, nullptr, it.first ? 1 : 0, 1, &it);
+        return row(ROW_RATIO, (unsigned)(it.nf * V), it.first ? spec_ones : r, r, m, nullptr, nullptr, nullptr, -1, it.first ? V : 0, &it);
     }
-    int iterate_once() {
-        RL_TRY(iterate_chunk(0, B));
-        ++iterations;
-        return RL_OK;
+    int pass_ht(const Iter& it) {       // H_t, column part
+        void* r = ratio_spec(it.f0);
+        if (pair) return col_pair(r, r, (it.nf + 1) / 2, COL_HT_VIEW, &it);
+        if (!ht_fused()) return col(r, r, it.nf, COL_HT_VIEW, &it);
+        if (col_split()) return col_split_pass(r, est_spec(it.f0), parked(it.f0), it.nf, COL_HT_FUSED, &it);
+        return col(r, est_spec(it.f0), it.nf, COL_HT_FUSED, &it);
+    }
+    int pass_update(const Iter& it) {   // est *= H_t / norm, and rowFFT(est) for the next iteration
+        void *e = off(est, (size_t)it.f0 * n_img()), *s = est_spec(it.f0);
+        if (pair) return row_pair(ROW_UPDATE, it.nf, s, it.drop_spectrum ? nullptr : s, nullptr, e, norm);
+        if (ht_fused()) return row(ROW_UPDATE, (unsigned)it.nf, s, s, nullptr, e, norm, nullptr, 1);
+        return row(ROW_UPDATE, (unsigned)it.nf, ratio_spec(it.f0), s, nullptr, e, norm);
+    }
+    int iterate_chunk(const Iter& it) {
+        if (sep) return sep_iterate(it.f0, it.nf);
+        RL_TRY(pass_h(it));
+        RL_TRY(pass_ratio(it));
+        RL_TRY(pass_ht(it));
+        return pass_update(it);
+    }
+    // noiseless = H(obj) on the device, for rl_deconv_set_object.  Not forward_slice(0, B): a split plan's simulation goes through the
+    // split column pass, whose sums round differently from these whole-pass launches (the last bits of noiseless differ).
+    int forward_object() {
+        if (sep) return sep_forward(obj, noiseless, sep_tmp(), B);
+        RL_TRY(row(ROW_FWD, (unsigned)B, nullptr, spec_a, obj, nullptr, nullptr));
+        RL_TRY(col(spec_a, spec_b, B, COL_H));
+        return row(ROW_INV, (unsigned)(B * V), spec_b, nullptr, nullptr, noiseless, nullptr);
     }
     // noiseless = H(obj) on a slice
     int forward_slice(int f0, int nf) {
-        if (sep) {
-            const size_t o = (size_t)f0 * V * n_img();
-            if (sep_one) return sep2d_(SEP_STORE_, off(obj, (size_t)f0 * n_img()), nullptr, nullptr, off(noiseless, o), nf);
-            RL_TRY(sep_rows_(off(obj, (size_t)f0 * n_img()), off(sep_tmp(), o), nf * V, V));
-            return sep_cols_(SEP_STORE_, off(sep_tmp(), o), nullptr, nullptr, off(noiseless, o), nf * V);
-        }
+        const size_t o = (size_t)f0 * V * n_img();
+        if (sep) return sep_forward(off(obj, (size_t)f0 * n_img()), off(noiseless, o), off(sep_tmp(), o), nf);
         void* sb = off(spec_b, (size_t)f0 * V * n_spec() * 2);
         // (frame pairs: the other lane's slice iterates in spec_a in the pair layout, whose slice boundaries are not
         // this layout's -- the simulation then stays in spec_b, in place)
         void* sa = !pair ? off(spec_a, (size_t)f0 * n_spec() * 2) : sb;
         RL_TRY(row(ROW_FWD, (unsigned)nf, nullptr, sa, off(obj, (size_t)f0 * n_img()), nullptr, nullptr));
-        if (col_split()) RL_TRY(col_split_pass(sa, sb, off(spec_x, (size_t)f0 * V * n_spec_x() * 2), nf, COL_H));   // (the same values as the whole pass)
-        else RL_TRY(col(sa, sb, nf, true));
-        RL_TRY(row(ROW_INV, (unsigned)(nf * V), sb, nullptr, nullptr, off(noiseless, (size_t)f0 * V * n_img()), nullptr));
+        if (col_split()) RL_TRY(col_split_pass(sa, sb, parked(f0), nf, COL_H));   // (the same values as the whole pass)
+        else RL_TRY(col(sa, sb, nf, COL_H));
+        RL_TRY(row(ROW_INV, (unsigned)(nf * V), sb, nullptr, nullptr, off(noiseless, o), nullptr));
         return RL_OK;
     }
-    // one whole simulate + deconvolve cycle, slice by slice
-    int run_cycle(int k, int rng_kind, uint64_t seed) { return run_slices(k, true, true, rng_kind, seed); }
     int join_open_lanes() {   // after a failed cycle between deferred joins
         if (!lanes_open) return RL_OK;
         lanes_open = false;
@@ -881,29 +884,30 @@ struct rl_deconv {
         }
         return RL_OK;
     }
-    // (optionally restart from est = 1 and) run k iterations, slice by slice
-    int run_iterations(int k, bool restart) { return run_slices(k, restart, false, 0, 0); }
-    int run_slices(int k, bool restart, bool simulate, int rng_kind, uint64_t seed) {
+    // the Poisson draw of a whole cycle: one seed for the batch, or -- rl_batch_submit -- a Philox key per frame (device arrays of B entries)
+    struct Draw { int rng_kind; uint64_t seed; const unsigned long long* key_seeds; const unsigned* key_ids; };
+    // (optionally restart from est = 1 and) run k iterations, slice by slice.  draw: one whole simulate + deconvolve cycle -- each
+    // slice first computes noiseless = H(obj) and draws its measurement.  cycle_follows: another cycle follows at once (rl_deconv_bench_cycles).
+    int run_slices(int k, bool restart, const Draw* draw = nullptr, bool cycle_follows = false) {
         const int cf = chunk_frames();
         const int slices = (B + cf - 1) / cf;
-        const int nl = slices < lanes ? slices : lanes;
-        // Lanes stay open between the back-to-back cycles of rl_deconv_bench_cycles (defer_join): slice s of every cycle
+        const int nl = slices < opt.lanes ? slices : opt.lanes;
+        // Lanes stay open between the back-to-back cycles of rl_deconv_bench_cycles (cycle_follows): slice s of every cycle
         // goes to the same lane, so stream order alone keeps each slice's buffers consistent and the lanes need not meet.
-        const bool keep_open = defer_join && nl > 1;
+        const bool keep_open = cycle_follows && nl > 1;
         if (accel && restart) RL_TRY(accel_reset());   // each run from ones (a task of rl_batch_run included) starts a fresh history
         if (nl > 1 && !lanes_open) {
             RL_TRY(ensure_lanes());
             HIP_TRY(hipEventRecord(fork, ctx->stream));
             for (int l = 0; l < nl; ++l) HIP_TRY(hipStreamWaitEvent(lane_stream[l], fork, 0));
         }
-        if (simulate) {   // one Poisson work list per slice: slices on different lanes run at the same time
+        if (draw) {   // one Poisson work list per slice: slices on different lanes run at the same time
             const size_t stride = (aux_poisson_workspace_bytes((size_t)cf * V * n_img()) + 255) / 256 * 256;
             if (slice_ws_bytes < stride * slices) {
                 HIP_TRY(hipDeviceSynchronize());
-                if (slice_ws) HIP_TRY(hipFree(slice_ws));
-                slice_ws = nullptr;
-                HIP_TRY(hipMalloc(&slice_ws, stride * slices));
-                bytes += stride * slices - slice_ws_bytes;
+                slice_ws_bytes = 0;
+                RL_TRY(release(&slice_ws));
+                RL_TRY(alloc(&slice_ws, stride * slices));
                 slice_ws_bytes = stride * slices;
             }
             slice_ws_stride = stride;
@@ -917,10 +921,9 @@ struct rl_deconv {
             RL_TRY(forward_slice(f0, nf));
             void* ws = (char*)slice_ws + (size_t)sl * slice_ws_stride;   // this slice's Poisson work list
             TimedScope t(this, TK_POISSON, false);
-            // (rl_batch_submit: a Philox key per frame, device arrays of B entries)
             hipError_t e = aux_poisson(dtype, off(noiseless, (size_t)f0 * V * n_img()), off(meas, (size_t)f0 * V * n_img()),
-                                       (unsigned)n_img(), (unsigned)(nf * V), (unsigned)(f0 * V), seed, rng_kind, ws, cur(),
-                                       run_key_seeds ? run_key_seeds + f0 : nullptr, run_key_ids ? run_key_ids + f0 : nullptr, (unsigned)V);
+                                       (unsigned)n_img(), (unsigned)(nf * V), (unsigned)(f0 * V), draw->seed, draw->rng_kind, ws, cur(),
+                                       draw->key_seeds ? draw->key_seeds + f0 : nullptr, draw->key_ids ? draw->key_ids + f0 : nullptr, (unsigned)V);
             if (e != hipSuccess) return fail(RL_ERR_HIP, std::string("Poisson kernels: ") + hipGetErrorString(e));
             return RL_OK;
         };
@@ -930,21 +933,16 @@ struct rl_deconv {
         for (int sl = 0, f0 = 0; f0 < B && rc == RL_OK; f0 += cf, ++sl) {
             const int nf = f0 + cf <= B ? cf : B - f0;
             active = nl > 1 ? lane_stream[sl % nl] : nullptr;
-            if (simulate) rc = simulate_slice(sl, f0, nf);
-            const bool shortcut = restart && ones_shortcut && spec_ones && k > 0 && !sep;
+            if (draw) rc = simulate_slice(sl, f0, nf);
+            const bool shortcut = restart && opt.ones_shortcut && spec_ones && k > 0 && !sep;
             if (restart && rc == RL_OK) rc = start_estimate_chunk(f0, nf, !shortcut);
             // Frame pairs: the last iteration of a run of >= 4 does not transform its estimate forward again (1 of 2 row
             // transforms of that launch, the spectrum store); an rl_deconv_iterate that continues rebuilds it with one ROW_FWD.
-            const bool drop = pair && k >= 4 && !keep_last_spectrum;
+            const bool drop = pair && k >= 4;
             for (int i = 0; i < k && rc == RL_OK; ++i) {
-                if (accel) {
-                    rc = accel_step(f0, nf, acc_steps + i, shortcut && i == 0, restart && i == 0);
-                    continue;
-                }
-                drop_last_spectrum = drop && i == k - 1;
-                rc = iterate_chunk(f0, nf, shortcut && i == 0, restart && i == 0);
+                if (accel) rc = accel_step(f0, nf, acc_steps + i, shortcut && i == 0, restart && i == 0);
+                else rc = iterate_chunk({f0, nf, shortcut && i == 0, restart && i == 0, drop && i == k - 1});
             }
-            drop_last_spectrum = false;
         }
         active = nullptr;
         if (nl > 1 && (!keep_open || rc != RL_OK)) {   // join, also on errors: the context's stream continues after every lane
@@ -962,7 +960,7 @@ struct rl_deconv {
             spec_valid = true;
             iterations = 0;
         }
-        if (pair && k >= 4 && !keep_last_spectrum) spec_valid = false;   // the last iteration left no spectrum behind
+        if (pair && k >= 4) spec_valid = false;   // the last iteration left no spectrum behind
         if (accel) {
             spec_valid = false;   // (a plain iterate after a change of mode rebuilds it; an accelerated one transforms y)
             acc_steps += k;
@@ -1052,33 +1050,61 @@ int rl_ctx_synchronize(rl_ctx* c) {
 int rl_deconv_destroy(rl_deconv* h) {
     if (!h) return RL_OK;
     (void)hipSetDevice(h->ctx->device);
-    // nothing of this plan may still be running when its buffers go away (slice streams included)
+    // nothing of this plan may still be running when its buffers go away (slice and copy streams included)
     (void)hipStreamSynchronize(h->ctx->stream);
-    for (int l = 0; l < rl_deconv::kMaxLanes; ++l)
-        if (h->lane_stream[l]) (void)hipStreamSynchronize(h->lane_stream[l]);
-    void* bufs[] = {h->psf_hat_pair, h->psf_hat_pair_re, h->spec_ones_pair, h->sep_u, h->sep_v, h->sep_uf, h->sep_vf, h->spec_ones, h->psf_hat_re, h->psf_hat, h->spec_a, h->spec_b, h->spec_x, h->obj, h->noiseless, h->meas, h->est, h->norm, h->scratch,
-                    h->stage_dev, h->stage_aux, h->stage_sums, h->slice_ws, h->key_seeds, h->key_ids, h->unresolved,
-                    h->acc_x, h->acc_y, h->acc_g, h->acc_part, h->acc_alpha};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
+    for (hipStream_t s : h->lane_stream)
+        if (s) (void)hipStreamSynchronize(s);
     if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
+    for (const rl_deconv::Owned& o : h->owned) (void)hipFree(o.p);
     for (rl_deconv::BatchSlot& sl : h->bslot) {
         if (sl.host) (void)hipHostFree(sl.host);
-        if (sl.dev) (void)hipFree(sl.dev);
         if (sl.uploaded) (void)hipEventDestroy(sl.uploaded);
         if (sl.freed) (void)hipEventDestroy(sl.freed);
     }
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    if (h->batch_out) (void)hipFree(h->batch_out);
     for (hipEvent_t e : h->event_pool) (void)hipEventDestroy(e);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->fork) (void)hipEventDestroy(h->fork);
-    for (int l = 0; l < rl_deconv::kMaxLanes; ++l) {
+    for (int l = 0; l < kMaxLanes; ++l) {
         if (h->lane_done[l]) (void)hipEventDestroy(h->lane_done[l]);
         if (h->lane_stream[l]) (void)hipStreamDestroy(h->lane_stream[l]);
     }
     delete h;
+    return RL_OK;
+}
+
+// PSF spectra by direct DFT of the (py x px) support in float64 on the device: `width` spectrum columns at row pitch `pitch` into
+// `hat` (transposed: [view][width][ly]).  re != nullptr: also their real parts, in a buffer of the plan's, and
+// *imag_ratio = max |im| / max |z| of the spectrum.
+static int build_psf_hat(rl_deconv* h, const double* psfs, void* hat, int width, int pitch, int transposed, void** re, double* imag_ratio) {
+    rl_ctx* ctx = h->ctx;
+    const size_t V = (size_t)h->V, np = V * h->py * h->px;
+    {
+        TempBuffers tmp;
+        void *wy = nullptr, *wx = nullptr, *psf_dev = nullptr, *s1 = nullptr;
+        RL_TRY(ctx->plain_twiddles(h->ly, &wy));
+        RL_TRY(ctx->plain_twiddles(h->lx, &wx));
+        RL_TRY(tmp.get(&psf_dev, np * 8));
+        RL_TRY(tmp.get(&s1, V * h->py * width * 16));
+        HIP_TRY(hipMemcpyAsync(psf_dev, psfs, np * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(aux_psf_spectrum(h->dtype, (const double*)psf_dev, wx, wy, s1, hat, h->V, h->py, h->px, h->ly, h->lx, width, pitch,
+                                 transposed, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    if (!re) return RL_OK;
+    // (the real parts are allocated once the transform's temporaries are gone: the order decides where the plan's large buffers land in
+    // device memory -- 4 % of a 2048^2 x 4 views cycle, profiles/r06/refactor_ab.log)
+    TempBuffers tmp;
+    const size_t nz = V * (size_t)width * h->ly;
+    double* stats = nullptr;
+    double hs[2] = {1.0, 1.0};
+    RL_TRY(h->alloc(re, nz * esize(h->dtype), rl_deconv::SLACK));
+    RL_TRY(tmp.get((void**)&stats, sizeof(hs)));
+    HIP_TRY(aux_split_real(h->dtype, hat, nz, *re, stats, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(hs, stats, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *imag_ratio = hs[1] > 0 ? hs[0] / hs[1] : 0.0;
     return RL_OK;
 }
 
@@ -1101,7 +1127,7 @@ static int deconv_build(rl_deconv* h, const double* psfs) {
     RL_TRY(ctx->twiddles(h->tx, h->dtype, &h->twx));
     const size_t es = esize(h->dtype), B = (size_t)h->B, V = (size_t)h->V;
     // (measured, pitch lx against lx + 32: 512^2 18.7 k against 18.1 k frames/s, 2048^2 690 against 716, 4096^2 K = 100 28.0 against 28.6)
-    h->pair_pitch = h->lx + (getenv("RLSTED_PAIR_PAD") ? std::max(0, atoi(getenv("RLSTED_PAIR_PAD"))) / 8 * 8 : (h->lx >= 1152 ? 32 : 0));
+    h->pair_pitch = h->lx + (h->lx >= 1152 ? 32 : 0);
     struct Req { void** p; size_t n; };
     const Req reqs[] = {
         {&h->psf_hat, V * h->ly * h->pitch * 2 * es},   // (spec_a: the frames' half spectra or the pairs' full ones)
@@ -1110,74 +1136,29 @@ static int deconv_build(rl_deconv* h, const double* psfs) {
         {&h->noiseless, B * V * h->n_img() * es},     {&h->meas, B * V * h->n_img() * es},
         {&h->est, B * h->n_img() * es},               {&h->norm, h->n_img() * es},
         {&h->scratch, std::max(B * V * h->n_img() * es, aux_poisson_workspace_bytes(B * V * h->n_img()))}};   // also the Poisson work list
-    for (const Req& r : reqs) {
-        // RL_STREAM_SLACK: the streaming row kernels load whole 64-lane segments without clamping;
-        // lanes past the end of the last row of a buffer read (and discard) these bytes
-        HIP_TRY(hipMalloc(r.p, r.n + RL_STREAM_SLACK));
-        HIP_TRY(hipMemsetAsync(static_cast<char*>(*r.p) + r.n, 0, RL_STREAM_SLACK, ctx->stream));
-        h->bytes += r.n + RL_STREAM_SLACK;
-    }
-    HIP_TRY(hipMalloc((void**)&h->unresolved, sizeof(unsigned long long)));
+    for (const Req& r : reqs) RL_TRY(h->alloc(r.p, r.n, rl_deconv::SLACK));
+    RL_TRY(h->alloc(&h->unresolved, sizeof(unsigned long long), rl_deconv::UNCOUNTED));
     HIP_TRY(hipMemsetAsync(h->unresolved, 0, sizeof(unsigned long long), ctx->stream));
     HIP_TRY(hipEventCreate(&h->ev0));
     HIP_TRY(hipEventCreate(&h->ev1));
 
-    // PSF spectra: direct DFT of the (py x px) support in float64 on the device
-    {
-        void *wy = nullptr, *wx = nullptr, *psf_dev = nullptr, *s1 = nullptr;
-        RL_TRY(ctx->plain_twiddles(h->ly, &wy));
-        RL_TRY(ctx->plain_twiddles(h->lx, &wx));
-        const size_t np = V * h->py * h->px;
-        HIP_TRY(hipMalloc(&psf_dev, np * 8));
-        HIP_TRY(hipMalloc(&s1, V * h->py * h->kx * 16));
-        HIP_TRY(hipMemcpyAsync(psf_dev, psfs, np * 8, hipMemcpyHostToDevice, ctx->stream));
-        hipError_t e = aux_psf_spectrum(h->dtype, (const double*)psf_dev, wx, wy, s1, h->psf_hat, h->V, h->py, h->px,
-                                        h->ly, h->lx, h->kx, h->pitch, h->ty->psf_transposed[h->dtype], ctx->stream);
-        hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        (void)hipFree(psf_dev);
-        (void)hipFree(s1);
-        HIP_TRY(e);
-        HIP_TRY(e2);
-    }
     // A point-symmetric PSF (every PSF of the reference: symmetric "to 1e-15") has a real spectrum.
     // Where the imaginary parts are rounding noise (<= 1e-12 of the largest value; in f32 they vanish against
     // the real parts' own rounding) the wave-private column kernels multiply by the real parts alone: half the
     // multiplier bytes per column launch.  RLSTED_REAL_PSF=0 keeps the complex multiplier.
-    if (h->psf_transposed() && !(getenv("RLSTED_REAL_PSF") && atoi(getenv("RLSTED_REAL_PSF")) == 0)) {
-        const size_t nz = V * (size_t)h->kx * h->ly;
-        void* re = nullptr;
-        double* stats = nullptr;
-        HIP_TRY(hipMalloc(&re, nz * es + RL_STREAM_SLACK));
-        hipError_t e = hipMalloc((void**)&stats, 2 * sizeof(double));
-        double hs[2] = {1.0, 1.0};
-        if (e == hipSuccess) e = aux_split_real(h->dtype, h->psf_hat, nz, re, stats, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(hs, stats, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (stats) (void)hipFree(stats);
-        if (e != hipSuccess) {
-            (void)hipFree(re);
-            HIP_TRY(e);
-        }
-        h->psf_hat_imag_ratio = hs[1] > 0 ? hs[0] / hs[1] : 0.0;
-        if (h->psf_hat_imag_ratio <= 1e-12) {
-            h->psf_hat_re = re;
-            h->bytes += nz * es + RL_STREAM_SLACK;
-        } else {
-            (void)hipFree(re);
-        }
-    }
+    RL_TRY(build_psf_hat(h, psfs, h->psf_hat, h->kx, h->pitch, h->ty->psf_transposed[h->dtype],
+                         h->psf_transposed() && h->opt.real_psf ? &h->psf_hat_re : nullptr, &h->psf_hat_imag_ratio));
+    if (h->psf_hat_imag_ratio > 1e-12) RL_TRY(h->release(&h->psf_hat_re));
     // The split column pass parks B * V column spectra (24 MB per 2048^2 image).  The set-up below runs it on ONE frame (H(1)); the
     // full allocation follows the strategy selection further down: a plan that ends on the separable stencils never touches it.
     if (h->col_split()) {
         const size_t n = V * h->n_spec_x() * 2 * es;
-        HIP_TRY(hipMalloc(&h->spec_x, n));
+        RL_TRY(h->alloc(&h->spec_x, n, rl_deconv::UNCOUNTED));
         HIP_TRY(hipMemsetAsync(h->spec_x, 0, n, ctx->stream));
     }
     // H_t(ones), line_sted_tools.py:589-592: sum_v clamp(conv(ones, psf_v))
     HIP_TRY(aux_fill(h->dtype, h->est, h->n_img(), 1.0, ctx->stream));
     {
-        const int keepB = h->B;
-        h->B = 1;
         // (study builds: the spectra of a frame of ones have DC = pixels x sum(psf), not the data's)
         const float keep_q = h->q_est;
         double psf_sum = 1.0;
@@ -1186,23 +1167,19 @@ static int deconv_build(rl_deconv* h, const double* psfs) {
             for (size_t i = 0; i < (size_t)h->py * h->px; ++i) t += psfs[v * h->py * h->px + i];
             psf_sum = std::max(psf_sum, t);
         }
-        if (getenv("RLSTED_Q_EXP_EST")) h->q_est = std::ldexp(1.0f, 14 - (int)std::ceil(std::log2((double)h->n_img() * psf_sum)) - 1);
-        int r = h->row(ROW_FWD, 1, nullptr, h->spec_a, h->est, nullptr, nullptr);
-        if (r == RL_OK) r = h->col(h->spec_a, h->spec_b, 1, true);
-        if (r == RL_OK) r = h->row(ROW_ADJ, 1, h->spec_b, nullptr, nullptr, h->norm, nullptr);
-        h->B = keepB;
+        if (h->opt.q_exp_est_set) h->q_est = std::ldexp(1.0f, 14 - (int)std::ceil(std::log2((double)h->n_img() * psf_sum)) - 1);
+        RL_TRY(h->row(ROW_FWD, 1, nullptr, h->spec_a, h->est, nullptr, nullptr));
+        RL_TRY(h->col(h->spec_a, h->spec_b, 1, rl_deconv::COL_H));
+        RL_TRY(h->row(ROW_ADJ, 1, h->spec_b, nullptr, nullptr, h->norm, nullptr));
         h->q_est = keep_q;
-        RL_TRY(r);
         // spec_b now holds the column-transformed spectra of H(1), one per view: every frame's first iteration
         const size_t ones_bytes = V * h->n_spec() * 2 * es;
-        HIP_TRY(hipMalloc(&h->spec_ones, ones_bytes + RL_STREAM_SLACK));
-        HIP_TRY(hipMemsetAsync(static_cast<char*>(h->spec_ones) + ones_bytes, 0, RL_STREAM_SLACK, ctx->stream));
+        RL_TRY(h->alloc(&h->spec_ones, ones_bytes, rl_deconv::SLACK));
         HIP_TRY(hipMemcpyAsync(h->spec_ones, h->spec_b, ones_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        h->bytes += ones_bytes + RL_STREAM_SLACK;
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     // ---- f32 plans: the normaliser to float64 rounding from the PSFs' integral images (aux_box_norm) ----
-    if (h->exact_norm) {
+    if (h->dtype == RL_F32) {
         const size_t py = h->py, px = h->px, stride = (py + 1) * (px + 1);
         std::vector<double> integ(V * stride, 0.0);
         for (size_t v = 0; v < V; ++v)
@@ -1213,19 +1190,17 @@ static int deconv_build(rl_deconv* h, const double* psfs) {
                     integ[v * stride + (a + 1) * (px + 1) + (b + 1)] = integ[v * stride + a * (px + 1) + (b + 1)] + row;
                 }
             }
+        TempBuffers tmp;
         double* integ_dev = nullptr;
-        HIP_TRY(hipMalloc((void**)&integ_dev, integ.size() * sizeof(double)));
-        hipError_t e = hipMemcpyAsync(integ_dev, integ.data(), integ.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = aux_box_norm(h->dtype, integ_dev, h->norm, h->V, h->py, h->px, h->ny, h->nx, ctx->stream);
-        hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        (void)hipFree(integ_dev);
-        HIP_TRY(e);
-        HIP_TRY(e2);
+        RL_TRY(tmp.get((void**)&integ_dev, integ.size() * sizeof(double)));
+        HIP_TRY(hipMemcpyAsync(integ_dev, integ.data(), integ.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(aux_box_norm(h->dtype, integ_dev, h->norm, h->V, h->py, h->px, h->ny, h->nx, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
-    // ---- strategy selection: direct separable stencils when every view is rank 1 and small ----
-    const int sep_mode = getenv("RLSTED_SEP") ? atoi(getenv("RLSTED_SEP")) : 1;
-    const int max_taps = getenv("RLSTED_SEP_MAX_TAPS") ? atoi(getenv("RLSTED_SEP_MAX_TAPS")) : 16;
-    if (sep_mode > 0 && (sep_mode > 1 || h->py + h->px <= max_taps) && sep_two_pass_fits(h->dtype, h->py, h->px)) {
+    // ---- strategy selection: direct separable stencils when every view is rank 1 and small (py + px <= 16: the measured
+    // crossover, profiles/r02/separable_vs_fft.json) ----
+    const int sep_mode = h->opt.sep;
+    if (sep_mode > 0 && (sep_mode > 1 || h->py + h->px <= 16) && sep_two_pass_fits(h->dtype, h->py, h->px)) {
         const size_t py = h->py, px = h->px;
         std::vector<double> u(V * py), vv(V * px);
         bool rank1 = true;
@@ -1245,21 +1220,12 @@ static int deconv_build(rl_deconv* h, const double* psfs) {
                     if (std::fabs(p[a * px + b] - u[v * py + a] * vv[v * px + b]) > 1e-12 * pmax) { rank1 = false; break; }
         }
         if (rank1) {
-            HIP_TRY(hipMalloc(&h->sep_u, V * py * es));
-            HIP_TRY(hipMalloc(&h->sep_v, V * px * es));
-            if (h->dtype == RL_F64) {
-                HIP_TRY(hipMemcpy(h->sep_u, u.data(), V * py * 8, hipMemcpyHostToDevice));
-                HIP_TRY(hipMemcpy(h->sep_v, vv.data(), V * px * 8, hipMemcpyHostToDevice));
-            } else {
-                std::vector<float> uf(u.begin(), u.end()), vf(vv.begin(), vv.end());
-                HIP_TRY(hipMemcpy(h->sep_u, uf.data(), V * py * 4, hipMemcpyHostToDevice));
-                HIP_TRY(hipMemcpy(h->sep_v, vf.data(), V * px * 4, hipMemcpyHostToDevice));
-            }
+            RL_TRY(h->upload_taps(&h->sep_u, u));
+            RL_TRY(h->upload_taps(&h->sep_v, vv));
             h->sep = true;
             // RLSTED_SEP_ONE: 0 two passes, 1 (default) one kernel up to 24 taps a side (beyond, the two-pass form is
             // faster: profiles/r02/separable_vs_fft.json), 2 one kernel whenever the tile fits LDS
-            const int one_mode = getenv("RLSTED_SEP_ONE") ? atoi(getenv("RLSTED_SEP_ONE")) : 1;
-            const bool want_one = one_mode >= 2 || (one_mode == 1 && std::max(py, px) <= 24);
+            const bool want_one = h->opt.sep_one >= 2 || (h->opt.sep_one == 1 && std::max(py, px) <= 24);
             if (want_one && sep2d_fits(h->dtype, h->py, h->px, (int)V)) {
                 const size_t pyp = (py + 7) / 8 * 8, pxp = (px + 7) / 8 * 8;
                 std::vector<double> uf(V * pyp, 0.0), vf(V * pxp, 0.0);
@@ -1267,16 +1233,8 @@ static int deconv_build(rl_deconv* h, const double* psfs) {
                     for (size_t k = 0; k < py; ++k) uf[v * pyp + k] = u[v * py + (py - 1 - k)];
                     for (size_t k = 0; k < px; ++k) vf[v * pxp + k] = vv[v * px + (px - 1 - k)];
                 }
-                HIP_TRY(hipMalloc(&h->sep_uf, V * pyp * es));
-                HIP_TRY(hipMalloc(&h->sep_vf, V * pxp * es));
-                if (h->dtype == RL_F64) {
-                    HIP_TRY(hipMemcpy(h->sep_uf, uf.data(), V * pyp * 8, hipMemcpyHostToDevice));
-                    HIP_TRY(hipMemcpy(h->sep_vf, vf.data(), V * pxp * 8, hipMemcpyHostToDevice));
-                } else {
-                    std::vector<float> a(uf.begin(), uf.end()), b(vf.begin(), vf.end());
-                    HIP_TRY(hipMemcpy(h->sep_uf, a.data(), V * pyp * 4, hipMemcpyHostToDevice));
-                    HIP_TRY(hipMemcpy(h->sep_vf, b.data(), V * pxp * 4, hipMemcpyHostToDevice));
-                }
+                RL_TRY(h->upload_taps(&h->sep_uf, uf));
+                RL_TRY(h->upload_taps(&h->sep_vf, vf));
                 h->sep_one = true;
             }
             // H_t(ones) through the same stencils (ref:589-592); the V copies of ones live in scratch
@@ -1292,25 +1250,18 @@ static int deconv_build(rl_deconv* h, const double* psfs) {
     }
     // ---- ... or a direct 2-D stencil when the views are small but not rank 1 (sep_kernels.hip k_sep2d DIRECT): py * px multiply-adds per
     // pixel and view, all of one sign for a non-negative PSF -- the relative accuracy an FFT convolution cannot give a dark region
-    // (DESIGN.md section 3b).  RLSTED_DIRECT: 0 never, 1 (default) up to RLSTED_DIRECT_MAX_TAPS = 49 taps (where it is also the faster
+    // (DESIGN.md section 3b).  RLSTED_DIRECT: 0 never, 1 (default) up to 49 taps (where it is also the faster
     // path), 2 whenever the tile fits LDS (f32 plans on sparse samples with PSFs up to ~15 x 15: 2x the FFT path's time at 11 x 11).
     {
-        const int direct_mode = getenv("RLSTED_DIRECT") ? atoi(getenv("RLSTED_DIRECT")) : 1;
-        const int direct_max = getenv("RLSTED_DIRECT_MAX_TAPS") ? atoi(getenv("RLSTED_DIRECT_MAX_TAPS")) : 49;
-        if (!h->sep && sep_mode > 0 && direct_mode > 0 && (direct_mode > 1 || h->py * h->px <= direct_max) && h->py * h->px <= 1024 &&
+        const int direct_mode = h->opt.direct;
+        if (!h->sep && sep_mode > 0 && direct_mode > 0 && (direct_mode > 1 || h->py * h->px <= 49) && h->py * h->px <= 1024 &&
             direct2d_fits(h->dtype, h->py, h->px, (int)V)) {
             const size_t py = h->py, px = h->px, pyp = (py + 7) / 8 * 8;
             std::vector<double> f(V * px * pyp, 0.0);
             for (size_t v = 0; v < V; ++v)
                 for (size_t l = 0; l < px; ++l)
                     for (size_t k = 0; k < py; ++k) f[(v * px + l) * pyp + k] = psfs[(v * py + (py - 1 - k)) * px + (px - 1 - l)];
-            HIP_TRY(hipMalloc(&h->sep_uf, f.size() * es));
-            if (h->dtype == RL_F64) {
-                HIP_TRY(hipMemcpy(h->sep_uf, f.data(), f.size() * 8, hipMemcpyHostToDevice));
-            } else {
-                std::vector<float> ff(f.begin(), f.end());
-                HIP_TRY(hipMemcpy(h->sep_uf, ff.data(), ff.size() * 4, hipMemcpyHostToDevice));
-            }
+            RL_TRY(h->upload_taps(&h->sep_uf, f));
             h->sep = h->sep_one = h->sep_direct = true;      // (sep_vf stays null: that is how sep2d tells the two forms apart)
             HIP_TRY(aux_fill(h->dtype, h->scratch, V * h->n_img(), 1.0, ctx->stream));
             RL_TRY(h->sep2d_(SEP_SUM_, h->scratch, nullptr, nullptr, h->norm, 1));      // H_t(ones) through the same stencil (ref:589-592)
@@ -1319,13 +1270,11 @@ static int deconv_build(rl_deconv* h, const double* psfs) {
     }
     if (h->col_split()) {   // (the one-frame parking space of the set-up -> the plan's, unless the stencils took over)
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        HIP_TRY(hipFree(h->spec_x));
-        h->spec_x = nullptr;
+        RL_TRY(h->release(&h->spec_x));
         if (!h->sep) {
             const size_t n = B * V * h->n_spec_x() * 2 * es;
-            HIP_TRY(hipMalloc(&h->spec_x, n));
+            RL_TRY(h->alloc(&h->spec_x, n));
             HIP_TRY(hipMemsetAsync(h->spec_x, 0, n, ctx->stream));
-            h->bytes += n;
         }
     }
     // ---- frame pairs for the Richardson-Lucy loop (single view, even batch, wave-private lengths) ----
@@ -1337,49 +1286,22 @@ static int deconv_build(rl_deconv* h, const double* psfs) {
     // 4096^2 -12 % time per iteration -- but the per-frame loop's Hermitian split averages the two mirrored halves of every
     // row spectrum, the pair loop does not, and where f32 has no margin left that shows: white noise at 2048^2, K = 20,
     // 8.8e-6 -> 1.05e-5 against the f64 plan.  Default there: per frame (RLSTED_PAIR=1 pairs them).
-    const bool want_pair = getenv("RLSTED_PAIR") ? atoi(getenv("RLSTED_PAIR")) != 0 : (h->dtype == RL_F32 && V == 1);
-    const bool pair_views_ok = V == 1 && h->inplace && h->B >= 2;   // (a single frame has no partner -- and the set-up below fills two frames of ones)
+    const bool pair_views_ok = V == 1 && h->opt.inplace && h->B >= 2;   // (a single frame has no partner -- and the set-up below fills two frames of ones)
     // an odd batch leaves its last pair half empty: allowed where the pair spectra still fit the per-frame buffers
-    if (want_pair && !h->sep && pair_views_ok && h->tx->launch_row_pair && h->psf_transposed()) {
-        const size_t nz = V * (size_t)h->lx * h->ly;
-        void *wy = nullptr, *wx = nullptr, *psf_dev = nullptr, *s1 = nullptr;
-        RL_TRY(ctx->plain_twiddles(h->ly, &wy));
-        RL_TRY(ctx->plain_twiddles(h->lx, &wx));
-        HIP_TRY(hipMalloc(&h->psf_hat_pair, nz * 2 * es + RL_STREAM_SLACK));
-        HIP_TRY(hipMalloc(&psf_dev, V * (size_t)h->py * h->px * 8));
-        HIP_TRY(hipMalloc(&s1, V * (size_t)h->py * h->lx * 16));
-        HIP_TRY(hipMemcpyAsync(psf_dev, psfs, V * (size_t)h->py * h->px * 8, hipMemcpyHostToDevice, ctx->stream));
-        hipError_t e = aux_psf_spectrum(h->dtype, (const double*)psf_dev, wx, wy, s1, h->psf_hat_pair, h->V, h->py, h->px, h->ly, h->lx,
-                                        h->lx, h->lx, 1, ctx->stream);
-        hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        (void)hipFree(psf_dev);
-        (void)hipFree(s1);
-        HIP_TRY(e);
-        HIP_TRY(e2);
-        h->bytes += nz * 2 * es + RL_STREAM_SLACK;
-        if (h->psf_hat_re) {   // the half-width spectra are real: so are the full ones
-            double* stats = nullptr;
-            HIP_TRY(hipMalloc(&h->psf_hat_pair_re, nz * es + RL_STREAM_SLACK));
-            HIP_TRY(hipMalloc((void**)&stats, 2 * sizeof(double)));
-            e = aux_split_real(h->dtype, h->psf_hat_pair, nz, h->psf_hat_pair_re, stats, ctx->stream);
-            e2 = hipStreamSynchronize(ctx->stream);
-            (void)hipFree(stats);
-            HIP_TRY(e);
-            HIP_TRY(e2);
-            h->bytes += nz * es + RL_STREAM_SLACK;
-        }
+    if (h->opt.pair && !h->sep && pair_views_ok && h->tx->launch_row_pair && h->psf_transposed()) {
+        double imag_ratio = 0;
+        RL_TRY(h->alloc(&h->psf_hat_pair, V * (size_t)h->lx * h->ly * 2 * es, rl_deconv::SLACK));
+        // (the half-width spectra are real: so are the full ones)
+        RL_TRY(build_psf_hat(h, psfs, h->psf_hat_pair, h->lx, h->lx, 1, h->psf_hat_re ? &h->psf_hat_pair_re : nullptr, &imag_ratio));
         h->pair = h->pair_layout = true;
-        if (getenv("RLSTED_PAIR_MAX_RATIO")) h->pair_max_ratio = atof(getenv("RLSTED_PAIR_MAX_RATIO"));
         // H(1 + i) of a pair of ones frames, column part (one spectrum per view): what every pair's first iteration reads
         const size_t ones_bytes = V * h->n_spec_pair() * 2 * es;
-        HIP_TRY(hipMalloc(&h->spec_ones_pair, ones_bytes + RL_STREAM_SLACK));
+        RL_TRY(h->alloc(&h->spec_ones_pair, ones_bytes, rl_deconv::SLACK));
         HIP_TRY(aux_fill(h->dtype, h->est, 2 * h->n_img(), 1.0, ctx->stream));
         RL_TRY(h->row_pair(ROW_FWD, 2, nullptr, h->spec_a, h->est, nullptr, nullptr));
         RL_TRY(h->col_pair(h->spec_a, V == 1 ? h->spec_a : h->spec_b, 1, rl_deconv::COL_H));
         HIP_TRY(hipMemcpyAsync(h->spec_ones_pair, V == 1 ? h->spec_a : h->spec_b, ones_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        HIP_TRY(hipMemsetAsync(static_cast<char*>(h->spec_ones_pair) + ones_bytes, 0, RL_STREAM_SLACK, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        h->bytes += ones_bytes + RL_STREAM_SLACK;
     }
     return RL_OK;
 }
@@ -1395,32 +1317,16 @@ int rl_deconv_create(rl_ctx* ctx, const double* psfs, int n_psf, int py, int px,
     rl_deconv* h = new rl_deconv;
     h->ctx = ctx;
     h->V = n_psf; h->py = py; h->px = px; h->B = batch; h->ny = ny; h->nx = nx; h->dtype = dtype;
-    if (getenv("RLSTED_INPLACE")) h->inplace = atoi(getenv("RLSTED_INPLACE")) != 0;
-    if (getenv("RLSTED_COL_ORDER")) h->col_order = atoi(getenv("RLSTED_COL_ORDER")) < 1 ? 1 : atoi(getenv("RLSTED_COL_ORDER"));
-    if (getenv("RLSTED_Q_EXP_EST")) h->q_est = std::ldexp(1.0f, 14 - atoi(getenv("RLSTED_Q_EXP_EST")));
-    if (getenv("RLSTED_Q_EXP_RATIO")) h->q_ratio = std::ldexp(1.0f, 14 - atoi(getenv("RLSTED_Q_EXP_RATIO")));
-    if (getenv("RLSTED_ONES_SHORTCUT")) h->ones_shortcut = atoi(getenv("RLSTED_ONES_SHORTCUT")) != 0;
-    if (getenv("RLSTED_KEEP_LAST_SPECTRUM")) h->keep_last_spectrum = atoi(getenv("RLSTED_KEEP_LAST_SPECTRUM")) != 0;
-    if (getenv("RLSTED_LANES")) {
-        h->lanes = atoi(getenv("RLSTED_LANES"));
-        if (h->lanes < 1) h->lanes = 1;
-        if (h->lanes > rl_deconv::kMaxLanes) h->lanes = rl_deconv::kMaxLanes;
-    }
-    if (getenv("RLSTED_COL_SPLIT")) h->split_wanted = atoi(getenv("RLSTED_COL_SPLIT")) != 0;
-    if (getenv("RLSTED_SPLIT_HT")) h->split_ht = atoi(getenv("RLSTED_SPLIT_HT")) != 0;
-    // H through the split pass from three views on: with two the forward half saved (1 + V against 2 V column transforms) does not pay
-    // for parking the spectrum -- measured, 2048^2: 2 views 429 (split) against 449 frames/s, 4 views 269 against 258
-    h->split_h = getenv("RLSTED_SPLIT_H") ? atoi(getenv("RLSTED_SPLIT_H")) != 0 : n_psf >= 3;
-    if (getenv("RLSTED_COL_MULTI")) h->col_multi = atoi(getenv("RLSTED_COL_MULTI")) != 0;
-    h->fuse_views = getenv("RLSTED_FUSE_VIEWS") ? atoi(getenv("RLSTED_FUSE_VIEWS")) != 0 : (dtype == RL_F32);
-    h->exact_norm = getenv("RLSTED_EXACT_NORM") ? atoi(getenv("RLSTED_EXACT_NORM")) != 0 : (dtype == RL_F32);
+    h->opt = plan_options(dtype, n_psf);
+    if (h->opt.q_exp_est_set) h->q_est = std::ldexp(1.0f, 14 - h->opt.q_exp_est);
+    if (h->opt.q_exp_ratio_set) h->q_ratio = std::ldexp(1.0f, 14 - h->opt.q_exp_ratio);
+    h->fuse_views = h->opt.fuse_views < 0 ? dtype == RL_F32 : h->opt.fuse_views != 0;
     {   // ratio - 1 needs H_t(ones) == the normaliser: every PSF value >= 0 (and not the 16-bit storage study, whose scales assume ratio spectra)
         bool nonneg = true;
         for (size_t i = 0; i < (size_t)n_psf * py * px && nonneg; ++i) nonneg = psfs[i] >= 0.0;
-        const bool want = getenv("RLSTED_SUB_ONE") ? atoi(getenv("RLSTED_SUB_ONE")) != 0 : (dtype == RL_F32 && RL_SPEC_QUANT == 0);
         // (RLSTED_FUSE_VIEWS=0 selects the reference's per-view clamp in H_t: `ratio - 1` clamps the view sum, so it is off then)
-        const bool per_view_clamp = n_psf > 1 && getenv("RLSTED_FUSE_VIEWS") && atoi(getenv("RLSTED_FUSE_VIEWS")) == 0;
-        h->sub_one = want && nonneg && !per_view_clamp;
+        const bool per_view_clamp = n_psf > 1 && h->opt.fuse_views == 0;
+        h->sub_one = h->opt.sub_one && nonneg && !per_view_clamp;
     }
     int r = deconv_build(h, psfs);
     if (r != RL_OK) {
@@ -1483,10 +1389,8 @@ int rl_deconv_simulate_keyed(rl_deconv* h, int rng_kind, const uint64_t* seeds, 
     for (int f = 0; f < h->B; ++f)   // image index = id * V + view must fit the 32-bit Philox counter word
         if ((uint64_t)image_ids[f] * (uint64_t)h->V + (uint64_t)h->V > 0xffffffffull) return fail(RL_ERR_INVALID, "image id too large");
     HIP_TRY(hipSetDevice(h->ctx->device));
-    if (!h->key_seeds) {
-        HIP_TRY(hipMalloc(&h->key_seeds, (size_t)h->B * sizeof(uint64_t)));
-        HIP_TRY(hipMalloc(&h->key_ids, (size_t)h->B * sizeof(uint32_t)));
-    }
+    if (!h->key_seeds) RL_TRY(h->alloc(&h->key_seeds, (size_t)h->B * sizeof(uint64_t), rl_deconv::UNCOUNTED));
+    if (!h->key_ids) RL_TRY(h->alloc(&h->key_ids, (size_t)h->B * sizeof(uint32_t), rl_deconv::UNCOUNTED));
     HIP_TRY(hipMemcpyAsync(h->key_seeds, seeds, (size_t)h->B * sizeof(uint64_t), hipMemcpyHostToDevice, h->ctx->stream));
     HIP_TRY(hipMemcpyAsync(h->key_ids, image_ids, (size_t)h->B * sizeof(uint32_t), hipMemcpyHostToDevice, h->ctx->stream));
     HIP_TRY(aux_poisson(h->dtype, h->noiseless, h->meas, (unsigned)h->n_img(), (unsigned)(h->B * h->V), 0, 0, rng_kind,
@@ -1575,7 +1479,7 @@ int rl_deconv_iterate(rl_deconv* h, int k) {
         RL_TRY(h->row(ROW_FWD, (unsigned)h->B, nullptr, h->spec_a, h->est, nullptr, nullptr));
         h->spec_valid = true;
     }
-    RL_TRY(h->run_iterations(k, restart));
+    RL_TRY(h->run_slices(k, restart));
     HIP_TRY(hipEventRecord(h->ev1, h->ctx->stream));
     HIP_TRY(hipEventSynchronize(h->ev1));
     float ms = 0;
@@ -1607,11 +1511,11 @@ int rl_forward(rl_deconv* h, const double* x, double* out) {
         // xin lives in scratch.  Two passes: the row pass has consumed xin before the column pass writes scratch.
         // One kernel: its workgroups read halos of xin while others store -- the result goes to the (idle) spectrum buffer.
         void* res = h->sep_one ? h->sep_tmp() : h->scratch;
-        RL_TRY(h->sep_forward(xin, res, h->B));
+        RL_TRY(h->sep_forward(xin, res, h->sep_tmp(), h->B));
         return h->download(res, out, (size_t)h->B * h->V * h->n_img());
     }
     RL_TRY(h->row(ROW_FWD, (unsigned)h->B, nullptr, h->spec_a, xin, nullptr, nullptr));
-    RL_TRY(h->col(h->spec_a, h->spec_b, h->B, true));
+    RL_TRY(h->col(h->spec_a, h->spec_b, h->B, rl_deconv::COL_H));
     RL_TRY(h->row(ROW_INV, (unsigned)(h->B * h->V), h->spec_b, nullptr, nullptr, h->scratch, nullptr));
     h->spec_valid = false;
     return h->download(h->scratch, out, (size_t)h->B * h->V * h->n_img());
@@ -1632,7 +1536,7 @@ int rl_adjoint(rl_deconv* h, const double* y, double* out, int normalize) {
     }
     // row transform of every view image: run ROW_FWD with V folded into the frame index
     RL_TRY(h->row(ROW_FWD, (unsigned)(h->B * h->V), nullptr, h->spec_b, h->scratch, nullptr, nullptr));
-    RL_TRY(h->col(h->spec_b, h->spec_b, h->B, false));
+    RL_TRY(h->col(h->spec_b, h->spec_b, h->B, rl_deconv::COL_HT_VIEW));
     RL_TRY(h->row(ROW_ADJ, (unsigned)h->B, h->spec_b, nullptr, nullptr, h->scratch, normalize ? h->norm : nullptr));
     h->spec_valid = false;
     return h->download(h->scratch, out, (size_t)h->B * h->n_img());
@@ -1653,14 +1557,12 @@ int rl_deconv_bench_cycles(rl_deconv* h, int k, int reps, int rng_kind, uint64_t
     hipStream_t s = h->ctx->stream;
     h->meas_level = h->obj_level;   // every cycle draws its measurement from the object
     h->choose_loop(h->meas_level);
-    const auto t_start = std::chrono::steady_clock::now();
     HIP_TRY(hipEventRecord(h->ev0, s));
     for (int r = 0; r < reps; ++r) {
         // per slice of the batch: noiseless = H(obj), noisy = Poisson(noiseless) + 1e-9, est = 1,
         // k iterations -- the same values as rl_deconv_simulate + rl_deconv_iterate over the batch
-        h->defer_join = r + 1 < reps;
-        const int rc = h->run_cycle(k, rng_kind, seed + (uint64_t)r);
-        h->defer_join = false;
+        const rl_deconv::Draw draw{rng_kind, seed + (uint64_t)r, nullptr, nullptr};
+        const int rc = h->run_slices(k, true, &draw, r + 1 < reps);
         if (rc != RL_OK) {
             const std::string keep = rl::last_error();
             h->join_open_lanes();
@@ -1670,14 +1572,10 @@ int rl_deconv_bench_cycles(rl_deconv* h, int k, int reps, int rng_kind, uint64_t
         h->have_meas = true;
     }
     HIP_TRY(hipEventRecord(h->ev1, s));
-    const auto t_enq = std::chrono::steady_clock::now();
     HIP_TRY(hipEventSynchronize(h->ev1));
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
     *total_ms = ms;
-    if (getenv("RLSTED_DEBUG_ENQUEUE"))   // how far the host runs ahead of the device: enqueue time against device time
-        fprintf(stderr, "rl_deconv_bench_cycles: host enqueue %.3f ms, device %.3f ms\n",
-                std::chrono::duration<double, std::milli>(t_enq - t_start).count(), (double)ms);
     return RL_OK;
 }
 
@@ -1776,11 +1674,8 @@ int rl_batch_submit(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_iters
         h->meas_level = level;
         h->choose_loop(h->meas_level);
         h->have_obj = true;
-        h->run_key_seeds = d_seeds;
-        h->run_key_ids = d_ids;
-        const int rc = h->run_cycle(k_iters, rng_kind, 0);   // per slice: H(obj), keyed Poisson draws, estimate = 1, k iterations
-        h->run_key_seeds = nullptr;
-        h->run_key_ids = nullptr;
+        const rl_deconv::Draw draw{rng_kind, 0, d_seeds, d_ids};
+        const int rc = h->run_slices(k_iters, true, &draw);   // per slice: H(obj), keyed Poisson draws, estimate = 1, k iterations
         HIP_TRY(hipEventRecord(sl.freed, s));
         sl.used = true;
         RL_TRY(rc);
@@ -1798,10 +1693,9 @@ int rl_batch_run(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_iters, i
     const size_t need = (size_t)n_tasks * h->n_img() * esize(h->dtype);
     if (estimates_out && need > h->batch_out_bytes) {
         HIP_TRY(hipStreamSynchronize(h->ctx->stream));
-        if (h->batch_out) HIP_TRY(hipFree(h->batch_out));
-        h->batch_out = nullptr;
         h->batch_out_bytes = 0;
-        HIP_TRY(hipMalloc(&h->batch_out, need));
+        RL_TRY(h->release(&h->batch_out));
+        RL_TRY(h->alloc(&h->batch_out, need, rl_deconv::UNCOUNTED));
         h->batch_out_bytes = need;
     }
     RL_TRY(rl_batch_submit(h, tasks, n_tasks, k_iters, rng_kind, estimates_out ? h->batch_out : nullptr, h->dtype));
@@ -1906,7 +1800,8 @@ int rl_deconv_time_cycle(rl_deconv* h, int k, int rng_kind, uint64_t seed, doubl
     h->timed.clear();
     h->events_used = 0;
     h->timing = true;
-    int rc = h->run_cycle(k, rng_kind, seed);
+    const rl_deconv::Draw draw{rng_kind, seed, nullptr, nullptr};
+    int rc = h->run_slices(k, true, &draw);
     h->timing = false;
     hipError_t e = hipDeviceSynchronize();
     RL_TRY(rc);
@@ -1936,37 +1831,26 @@ int rl_deconv_time_kernels(rl_deconv* h, int reps, double* avg_ms) {
     if (h->sep) return fail(RL_ERR_UNSUPPORTED, "per-kernel timing covers the FFT strategy; this plan runs the separable stencils");
     HIP_TRY(hipSetDevice(h->ctx->device));
     hipStream_t s = h->ctx->stream;
-    if (!h->est_ready) RL_TRY(h->start_estimate());
+    if (!h->est_ready) {
+        RL_TRY(h->start_estimate_chunk(0, h->B));
+        h->est_ready = true;
+        h->spec_valid = true;
+        h->iterations = 0;
+    }
     // one untimed iteration so that every buffer holds realistic data
-    RL_TRY(h->iterate_once());
-    // the RL kernels are timed on the launch shape the RL loop uses: one slice of the batch
-    const int nf = h->chunk_frames();
-    avg_ms[6] = (double)nf;
+    RL_TRY(h->iterate_chunk({0, h->B, false, false, false}));
+    ++h->iterations;
+    // the RL kernels are timed on the launch shape the RL loop uses: one slice of the batch, and through the loop's own four passes
+    const rl_deconv::Iter it{0, h->chunk_frames(), false, false, false};
+    avg_ms[6] = (double)it.nf;
     for (int which = 0; which < 6; ++which) {
         HIP_TRY(hipEventRecord(h->ev0, s));
         for (int r = 0; r < reps; ++r) {
-            const bool one_buffer = h->V == 1 && h->inplace;   // as iterate_chunk(): everything in spec_a
             switch (which) {
-                case 0:
-                    if (h->col_split()) RL_TRY(h->col_split_pass(h->spec_a, h->spec_b, h->spec_x, nf, rl_deconv::COL_H));
-                    else RL_TRY(h->col(h->spec_a, one_buffer ? h->spec_a : h->spec_b, nf, true));
-                    break;
-                case 1:
-                    if (one_buffer) RL_TRY(h->row(ROW_RATIO, (unsigned)nf, h->spec_a, h->spec_a, h->meas, nullptr, nullptr));
-                    else RL_TRY(h->row(ROW_RATIO, (unsigned)(nf * h->V), h->spec_b, h->spec_b, h->meas, nullptr, nullptr));
-                    break;
-                case 2:   // as iterate_chunk(): in place, fused (Fourier-domain view sum) or per view
-                    if (one_buffer) RL_TRY(h->col(h->spec_a, h->spec_a, nf, false));
-                    else if (h->col_split() && h->fuse_views) RL_TRY(h->col_split_pass(h->spec_b, h->spec_a, h->spec_x, nf, rl_deconv::COL_HT_FUSED));
-                    else if (h->fuse_views && h->V > 1 && h->wave_private_y()) RL_TRY(h->col(h->spec_b, h->spec_a, nf, rl_deconv::COL_HT_FUSED));
-                    else RL_TRY(h->col(h->spec_b, h->spec_b, nf, false));
-                    break;
-                case 3:
-                    if (one_buffer) RL_TRY(h->row(ROW_UPDATE, (unsigned)nf, h->spec_a, h->spec_a, nullptr, h->est, h->norm));
-                    else if (h->fuse_views && h->V > 1 && (h->wave_private_y() || h->col_split()))
-                        RL_TRY(h->row(ROW_UPDATE, (unsigned)nf, h->spec_a, h->spec_a, nullptr, h->est, h->norm, nullptr, 1));
-                    else RL_TRY(h->row(ROW_UPDATE, (unsigned)nf, h->spec_b, h->spec_a, nullptr, h->est, h->norm));
-                    break;
+                case 0: RL_TRY(h->pass_h(it)); break;
+                case 1: RL_TRY(h->pass_ratio(it)); break;
+                case 2: RL_TRY(h->pass_ht(it)); break;
+                case 3: RL_TRY(h->pass_update(it)); break;
                 case 4: RL_TRY(h->row(ROW_FWD, (unsigned)h->B, nullptr, h->spec_a, h->obj, nullptr, nullptr)); break;
                 case 5: HIP_TRY(aux_poisson(h->dtype, h->noiseless, h->meas, (unsigned)h->n_img(), (unsigned)(h->B * h->V), 0, 1, RL_RNG_PHILOX, h->scratch, s)); break;
             }
