@@ -125,6 +125,47 @@ int rl_deconv_set_acceleration(rl_deconv* h, int mode);
 /* out [batch]: the a that formed each frame's last extrapolated point (0 before one). */
 int rl_deconv_get_alpha(rl_deconv* h, double* out);
 
+/* How well the current estimate explains the data: the Poisson I-divergence D(m || p) = sum m log(m / p) - m + p of every frame,
+ * out [batch], with m the stored measurement and p = H(estimate) -- the quantity Richardson-Lucy minimises.  Computed on the
+ * device: p is what rl_forward returns for the current estimate (the same launches, reading the estimate where it is), nothing
+ * but the batch's doubles crosses PCIe.  Per frame over the N = n_psf * ny * nx stored values of its views, each converted to
+ * float64 before any arithmetic, a pixel's term is
+ *     p > 0          :  ((m > 0 ? m * log(m / p) : 0) - m) + p          (log: the float64 device log)
+ *     p <= 0 or nan  :  m > 0 ? 0 : -m     a prediction the plan could not resolve is a neutral pixel, as in the iteration's ratio
+ *                                          (rl_deconv_unresolved: ratio 1 means m = p, whose term is 0)
+ * summed in float64 in a fixed order (no atomics): the frame's values are vectors of 16 bytes dealt to workgroups of 256 threads
+ * in equal runs (the split depends on N and the element type alone); a thread adds its terms in increasing order, a workgroup
+ * its threads' sums in a binary tree, the frame its workgroups' sums in increasing order (csrc/stop_kernels.hpp).  A frame's D in
+ * a float64 plan does not depend on its batch.  Needs a measurement and an estimate (RL_ERR_STATE otherwise).  Leaves the
+ * estimate, the measurement and the Biggs-Andrews history alone: iterate(a), divergence, iterate(b) gives the estimate of
+ * iterate(a), forward(x), iterate(b) bit for bit.  Works on every plan type; its buffers (the partial sums) are allocated on
+ * first use and counted in device_bytes.  Synchronises the plan's stream. */
+int rl_deconv_divergence(rl_deconv* h, double* out);
+
+/* Richardson-Lucy with a stopping rule per frame.  DEFINED as this sequence of the calls above, and equal to it bit for bit:
+ * starting like rl_deconv_iterate (from ones if the plan holds no estimate), repeat { c = min(check_every, k_max - done)
+ * iterations on the whole batch; D of every frame as rl_deconv_divergence forms it; the rule } until every frame has stopped
+ * or done == k_max.  With N = n_psf * ny * nx and the threshold t, evaluated in float64 exactly as written:
+ *     RL_STOP_DISCREPANCY :  2 * D / N <= t                 (t = 1: the discrepancy principle for Poisson data; Bertero et al.,
+ *                                                            Inverse Problems 26, 105004, 2010)
+ *     RL_STOP_RELATIVE    :  a previous check of this call exists and D_prev - D <= t * D_prev    (also stops a D that rose)
+ * A D -- or a D_prev -- that is nan or infinite never meets a rule.  A frame stops at the first check that meets the rule: its
+ * estimate, D and iteration count (counted from the start of this call) of that check are kept on the device; a frame that never
+ * stops ends with those of the last check and stopped == 0.  All frames keep iterating until the loop ends (a frame pair's
+ * partner does not change under it); stopping only freezes what is reported.  After each check the host reads the batch's
+ * stopped flags (one small copy) to end early.  At the end the kept estimates become the plan's estimate (rl_deconv_get_estimate,
+ * rl_deconv_device_ptr which = 0), as after rl_deconv_set_estimate: a following rl_deconv_iterate continues from them and the
+ * Biggs-Andrews history restarts.  iterations_out, divergence_out, stopped_out: [batch] each, any may be NULL.  k_max < 1,
+ * check_every < 1, an unknown rule or a nan threshold: RL_ERR_INVALID; no measurement: RL_ERR_STATE.  rl_deconv_last_ms covers
+ * the whole call.  The first call allocates one more image per frame and the frames' state (counted in device_bytes).
+ * At fewer than about one photon per pixel the expectation of 2 D / N at the true object falls below 1: the discrepancy rule at
+ * t = 1 then stops at the first check -- the threshold is the caller's to choose.
+ * Not covered: rl_batch_run / rl_batch_submit take a fixed iteration count (enqueued work, no host in the loop). */
+#define RL_STOP_DISCREPANCY 1
+#define RL_STOP_RELATIVE 2
+int rl_deconv_iterate_until(rl_deconv* h, int k_max, int check_every, int rule, double threshold, int* iterations_out,
+                            double* divergence_out, int* stopped_out);
+
 int rl_deconv_get_object(rl_deconv* h, double* out);        /* [batch][ny][nx]        */
 int rl_deconv_get_noiseless(rl_deconv* h, double* out);     /* [batch][n_psf][ny][nx] */
 int rl_deconv_get_measurement(rl_deconv* h, double* out);   /* [batch][n_psf][ny][nx] */

@@ -16,6 +16,8 @@ RNG_NONE, RNG_PHILOX = 0, 1
 DTYPES = {'f32': RL_F32, 'float32': RL_F32, 'f64': RL_F64, 'float64': RL_F64}
 RL_ACCEL_NONE, RL_ACCEL_BIGGS_ANDREWS = 0, 1
 ACCELERATIONS = {None: RL_ACCEL_NONE, 'none': RL_ACCEL_NONE, 'biggs-andrews': RL_ACCEL_BIGGS_ANDREWS}
+RL_STOP_DISCREPANCY, RL_STOP_RELATIVE = 1, 2
+STOP_RULES = {'discrepancy': RL_STOP_DISCREPANCY, 'relative': RL_STOP_RELATIVE}
 
 
 def accel_mode(acceleration):
@@ -48,6 +50,8 @@ PROTOTYPES = {
     'rl_deconv_set_estimate': (_i, [_vp, _dp]),
     'rl_deconv_set_acceleration': (_i, [_vp, _i]),
     'rl_deconv_get_alpha': (_i, [_vp, _dp]),
+    'rl_deconv_divergence': (_i, [_vp, _dp]),
+    'rl_deconv_iterate_until': (_i, [_vp, _i, _i, _i, _c.c_double, _c.POINTER(_i), _dp, _c.POINTER(_i)]),
     'rl_deconv_get_object': (_i, [_vp, _dp]),
     'rl_deconv_get_noiseless': (_i, [_vp, _dp]),
     'rl_deconv_get_measurement': (_i, [_vp, _dp]),
@@ -288,6 +292,28 @@ class DeconvPlan:
         out = np.zeros(self.B, dtype=np.float64)
         check(lib.rl_deconv_get_alpha(self.handle, ptr(out)))
         return out
+
+    def divergence(self):
+        """(B,) float64: the Poisson I-divergence D(measurement || H(estimate)) of every frame, formed on the device
+        (include/rlsted.h rl_deconv_divergence).  The estimate and the acceleration history stay as they are."""
+        out = np.empty(self.B, dtype=np.float64)
+        check(lib.rl_deconv_divergence(self.handle, ptr(out)))
+        return out
+
+    def iterate_until(self, max_iterations, rule='discrepancy', threshold=1.0, check_every=1):
+        """Richardson-Lucy with a stopping rule per frame (include/rlsted.h rl_deconv_iterate_until): 'discrepancy' stops a frame at
+        the first check with 2 D / N <= threshold, 'relative' at the first with D_prev - D <= threshold * D_prev; checks every
+        `check_every` iterations, `max_iterations` at most.  Returns {'iterations', 'divergence', 'stopped'}: (B,) arrays of each
+        frame's iteration count and D at the point that was kept -- the plan's estimate() afterwards -- and whether the rule was met."""
+        try:
+            code = STOP_RULES[rule]
+        except (KeyError, TypeError):
+            raise ValueError("rule must be 'discrepancy' or 'relative'; got %r" % (rule,)) from None
+        its, stopped = np.zeros(self.B, dtype=np.intc), np.zeros(self.B, dtype=np.intc)
+        div = np.empty(self.B, dtype=np.float64)
+        check(lib.rl_deconv_iterate_until(self.handle, int(max_iterations), int(check_every), code, float(threshold),
+                                          its.ctypes.data_as(_c.POINTER(_i)), ptr(div), stopped.ctypes.data_as(_c.POINTER(_i))))
+        return {'iterations': its.astype(np.int64), 'divergence': div, 'stopped': stopped.astype(bool)}
 
     def _get(self, fn, shape, out=None):
         if out is None:

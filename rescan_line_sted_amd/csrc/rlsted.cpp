@@ -21,6 +21,7 @@
 #include "kernel_table.hpp"
 #include "ctx.hpp"
 #include "sep_kernels.hpp"
+#include "stop_kernels.hpp"
 
 using namespace rl;
 
@@ -306,6 +307,36 @@ struct rl_deconv {
         RL_TRY(iterate_chunk({f0, nf, first, from_ones, /* drop_spectrum */ pair}));
         HIP_TRY(accel_reduce(dtype, off(est, o), off(acc_y, o), off(acc_g, o), part, n_img(), nf,
                              (from_ones ? ACC_Y_ONES : 0) | (s > 0 ? ACC_HAVE_PREV : 0), cur()));
+        return RL_OK;
+    }
+    // ---- Poisson I-divergence and the stopping rule (stop_kernels.hpp; rl_deconv_divergence, rl_deconv_iterate_until).  Allocated on
+    // first use: the divergence's per-workgroup partials and the frames' D, and -- iterate_until -- the latched estimates and the
+    // frames' state, double buffered by check parity.
+    double *stop_part = nullptr, *stop_d = nullptr;   // [B][stop_blocks(n_frame)], [B]
+    void* stop_result = nullptr;                       // [B][ny][nx]
+    StopFrame* stop_state = nullptr;                   // [2][B]
+    size_t n_frame() const { return (size_t)V * n_img(); }   // values of one frame's measurement: all its views
+    int ensure_divergence() {
+        if (!stop_part) RL_TRY(alloc(&stop_part, (size_t)B * stop_blocks(n_frame(), esize(dtype)) * sizeof(double)));
+        if (!stop_d) RL_TRY(alloc(&stop_d, (size_t)B * sizeof(double)));
+        return RL_OK;
+    }
+    int ensure_latch() {
+        if (!stop_result) RL_TRY(alloc(&stop_result, (size_t)B * n_img() * esize(dtype)));
+        if (!stop_state) RL_TRY(alloc(&stop_state, 2 * (size_t)B * sizeof(StopFrame)));
+        return RL_OK;
+    }
+    // scratch = H(est) -- rl_forward's launches, reading the estimate where it is -- and the partials of D(meas || scratch) of every frame
+    int divergence_partials() {
+        if (sep) {
+            RL_TRY(sep_forward(est, scratch, sep_tmp(), B));
+        } else {
+            RL_TRY(row(ROW_FWD, (unsigned)B, nullptr, spec_a, est, nullptr, nullptr));
+            RL_TRY(col(spec_a, spec_b, B, COL_H));
+            RL_TRY(row(ROW_INV, (unsigned)(B * V), spec_b, nullptr, nullptr, scratch, nullptr));
+            spec_valid = false;
+        }
+        HIP_TRY(stop_divergence(dtype, meas, scratch, stop_part, n_frame(), B, cur()));
         return RL_OK;
     }
     bool spec_valid = false;   // spec_a holds rowFFT(est)
@@ -1462,13 +1493,8 @@ int rl_deconv_reset_estimate(rl_deconv* h) {
     return RL_OK;
 }
 
-int rl_deconv_iterate(rl_deconv* h, int k) {
-    if (!h) return fail(RL_ERR_INVALID, "handle is NULL");
-    if (k < 0) return fail(RL_ERR_INVALID, "k < 0");
-    if (!h->have_meas) return fail(RL_ERR_STATE, "no measurement: call rl_deconv_simulate or rl_deconv_set_measurement");
-    HIP_TRY(hipSetDevice(h->ctx->device));
-    RL_TRY(h->refresh_meas_levels());
-    HIP_TRY(hipEventRecord(h->ev0, h->ctx->stream));
+// rl_deconv_iterate between its events: k iterations on the whole batch, from ones if the plan holds no estimate
+static int iterate_batch(rl_deconv* h, int k) {
     bool restart = !h->est_ready;
     // (an accelerated plan transforms the extrapolated point inside the loop instead)
     if (!restart && !h->spec_valid && h->pair && !h->accel) {
@@ -1479,13 +1505,82 @@ int rl_deconv_iterate(rl_deconv* h, int k) {
         RL_TRY(h->row(ROW_FWD, (unsigned)h->B, nullptr, h->spec_a, h->est, nullptr, nullptr));
         h->spec_valid = true;
     }
-    RL_TRY(h->run_slices(k, restart));
+    return h->run_slices(k, restart);
+}
+
+static int finish_timed(rl_deconv* h) {
     HIP_TRY(hipEventRecord(h->ev1, h->ctx->stream));
     HIP_TRY(hipEventSynchronize(h->ev1));
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
     h->last_iter_ms = ms;
     return RL_OK;
+}
+
+int rl_deconv_iterate(rl_deconv* h, int k) {
+    if (!h) return fail(RL_ERR_INVALID, "handle is NULL");
+    if (k < 0) return fail(RL_ERR_INVALID, "k < 0");
+    if (!h->have_meas) return fail(RL_ERR_STATE, "no measurement: call rl_deconv_simulate or rl_deconv_set_measurement");
+    HIP_TRY(hipSetDevice(h->ctx->device));
+    RL_TRY(h->refresh_meas_levels());
+    HIP_TRY(hipEventRecord(h->ev0, h->ctx->stream));
+    RL_TRY(iterate_batch(h, k));
+    return finish_timed(h);
+}
+
+int rl_deconv_divergence(rl_deconv* h, double* out) {
+    if (!h || !out) return fail(RL_ERR_INVALID, "NULL argument");
+    if (!h->have_meas) return fail(RL_ERR_STATE, "no measurement: call rl_deconv_simulate or rl_deconv_set_measurement");
+    if (!h->est_ready) return fail(RL_ERR_STATE, "no estimate: call rl_deconv_iterate or rl_deconv_set_estimate");
+    HIP_TRY(hipSetDevice(h->ctx->device));
+    RL_TRY(h->ensure_divergence());
+    RL_TRY(h->divergence_partials());
+    HIP_TRY(stop_totals(h->dtype, h->stop_part, h->n_frame(), h->B, h->stop_d, h->ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out, h->stop_d, (size_t)h->B * sizeof(double), hipMemcpyDeviceToHost, h->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(h->ctx->stream));
+    return RL_OK;
+}
+
+int rl_deconv_iterate_until(rl_deconv* h, int k_max, int check_every, int rule, double threshold, int* iterations_out,
+                            double* divergence_out, int* stopped_out) {
+    if (!h) return fail(RL_ERR_INVALID, "handle is NULL");
+    if (k_max < 1 || check_every < 1) return fail(RL_ERR_INVALID, "k_max and check_every must be at least 1");
+    if (rule != RL_STOP_DISCREPANCY && rule != RL_STOP_RELATIVE) return fail(RL_ERR_INVALID, "unknown stopping rule");
+    if (threshold != threshold) return fail(RL_ERR_INVALID, "threshold is nan");
+    if (!h->have_meas) return fail(RL_ERR_STATE, "no measurement: call rl_deconv_simulate or rl_deconv_set_measurement");
+    HIP_TRY(hipSetDevice(h->ctx->device));
+    RL_TRY(h->ensure_divergence());
+    RL_TRY(h->ensure_latch());
+    RL_TRY(h->refresh_meas_levels());
+    hipStream_t s = h->ctx->stream;
+    HIP_TRY(hipEventRecord(h->ev0, s));
+    std::vector<StopFrame> state((size_t)h->B);
+    for (int done = 0, check = 0; done < k_max; ++check) {
+        const int c = std::min(check_every, k_max - done);
+        RL_TRY(iterate_batch(h, c));   // (every lane has joined the context's stream when it returns)
+        done += c;
+        RL_TRY(h->divergence_partials());
+        const StopFrame* prev = h->stop_state + (size_t)(check & 1) * h->B;
+        StopFrame* next = h->stop_state + (size_t)((check + 1) & 1) * h->B;
+        HIP_TRY(stop_latch(h->dtype, h->est, h->stop_result, h->stop_part, prev, next, h->n_img(), h->n_frame(), h->B, rule, threshold, done,
+                           check > 0 ? 1 : 0, s));
+        HIP_TRY(hipMemcpyAsync(state.data(), next, state.size() * sizeof(StopFrame), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        bool all = true;
+        for (const StopFrame& f : state) all = all && f.stopped != 0;
+        if (all) break;
+    }
+    // the latched estimates become the plan's estimate, as a set estimate does: a point without history
+    HIP_TRY(hipMemcpyAsync(h->est, h->stop_result, (size_t)h->B * h->n_img() * esize(h->dtype), hipMemcpyDeviceToDevice, s));
+    h->est_ready = true;
+    h->spec_valid = false;
+    RL_TRY(h->accel_reset());
+    for (int f = 0; f < h->B; ++f) {
+        if (iterations_out) iterations_out[f] = state[f].iterations;
+        if (divergence_out) divergence_out[f] = state[f].d_latched;
+        if (stopped_out) stopped_out[f] = state[f].stopped;
+    }
+    return finish_timed(h);
 }
 
 #define RL_GETTER(name, buf, count, need, what)                                   \

@@ -9,7 +9,8 @@ work runs in hand-written HIP kernels on an MI355X through librlsted.so.
     logarithmic_progress
 
 plus batch-oriented helpers that the reference lacks (`simulate`,
-`deconvolve`), which process many independent frames per launch.
+`deconvolve`, `deconvolve_until`), which process many independent frames per
+launch.
 
 Precision: the reference computes in float64.  `Deconvolver(dtype=...)` picks
 the device arithmetic: 'f64' (default for this class: bit-level agreement with
@@ -22,6 +23,9 @@ Acceleration: `Deconvolver(acceleration='biggs-andrews')` and
 extrapolated Richardson-Lucy -- fewer iterations for the same fit to the data,
 by design not the reference's sequence of estimates.
 The default, None, is the reference's iteration.
+
+Stopping: `deconvolve_until` stops every frame of a batch by its own Poisson
+I-divergence, formed on the device.
 """
 import os
 import time
@@ -359,6 +363,25 @@ def deconvolve(measurement, psfs, iterations, dtype='f32', device=None, plan=Non
     plan.reset_estimate()
     plan.iterate(iterations)
     return plan.estimate()
+
+
+def deconvolve_until(measurement, psfs, max_iterations, rule='discrepancy', threshold=1.0, check_every=1, dtype='f32',
+                     device=None, plan=None, acceleration=None):
+    """Richardson-Lucy from ones with a stopping rule per frame (DeconvPlan.iterate_until): measurement (B, V, ny, nx).
+    rule 'discrepancy': a frame stops at the first check with 2 D / N <= threshold, D its Poisson I-divergence and N its
+    V * ny * nx pixels; 'relative': at the first check with D_prev - D <= threshold * D_prev.  Checks every `check_every`
+    iterations, `max_iterations` at most.  Returns (estimates (B, ny, nx), info) with info['iterations'], info['divergence'],
+    info['stopped']: (B,) arrays for the kept estimates."""
+    measurement = np.asarray(measurement, dtype=np.float64)
+    B, V, ny, nx = measurement.shape
+    if plan is None:
+        plan = DeconvPlan(psfs, B, ny, nx, dtype=dtype,
+                          device=_DEFAULT_DEVICE if device is None else device)
+    plan.set_acceleration(acceleration)
+    plan.set_measurement(measurement)
+    plan.reset_estimate()
+    info = plan.iterate_until(max_iterations, rule=rule, threshold=threshold, check_every=check_every)
+    return plan.estimate(), info
 
 
 def _save_points(n):

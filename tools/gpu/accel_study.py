@@ -3,7 +3,7 @@
 
   * device ms per frame-iteration, plain and accelerated (rl_deconv_last_ms of one rl_deconv_iterate over a batch)
   * the iterations and device time each mode needs to reach plain Richardson-Lucy's K = 128 I-divergence
-    sum m log(m / Hx) - m + Hx (summed over views; Hx through the plan's own H)
+    sum m log(m / Hx) - m + Hx (summed over views; formed on the device: DeconvPlan.divergence)
 
 for 512^2 x 1 view (the 1.5x point PSF) and 512^2 x 4 views (the 2.0x line set), f32 and f64.  Object: the astronaut,
 each pixel repeated 4 x 4, 5e10 photons per 128^2, Philox noise.
@@ -37,13 +37,6 @@ def inputs(psf_name):
     return list(g[psf_name]), np.kron(o, np.ones((N // 128, N // 128)))
 
 
-def i_divergence(plan, est):
-    meas, pred = plan.measurement(), plan.forward(est)
-    with np.errstate(divide='ignore', invalid='ignore'):
-        t = np.where(meas > 0, meas * np.log(meas / pred), 0.0) - meas + pred
-    return float(np.sum(t))
-
-
 def ms_per_frame_iteration(psfs, obj, dtype, accel, B, K=20):
     plan = DeconvPlan(psfs, B, N, N, dtype=dtype, acceleration=accel)
     plan.set_object(np.repeat(obj[None], B, axis=0), 5e10 * (N / 128) ** 2)
@@ -65,12 +58,12 @@ def to_quality(psfs, obj, dtype):
         plan.simulate(seed=1)
         if accel is None:
             plan.iterate(128)
-            out['target'] = i_divergence(plan, plan.estimate())
+            out['target'] = float(plan.divergence()[0])
             continue
         out['accel_k'] = None
         for k in range(1, 129):
             plan.iterate(1)
-            if i_divergence(plan, plan.estimate()) <= out['target']:
+            if plan.divergence()[0] <= out['target']:
                 out['accel_k'] = k
                 break
     return out
