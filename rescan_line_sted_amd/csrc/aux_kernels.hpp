@@ -1,9 +1,41 @@
-// aux_kernels.hpp -- host-callable launchers of aux_kernels.hip
+// aux_kernels.hpp -- host-callable launchers of aux_kernels.hip, and the per-pixel arithmetic of the box normaliser as a
+// host-compilable function (the CPU tests run it through tests/emu/sep_emu.cpp; the header includes without HIP for that)
 #pragma once
+#include "fft_core.hpp"
+
+#include <cstddef>
+
+#if defined(__HIPCC__) || defined(__HIP_PLATFORM_AMD__)
 #include <hip/hip_runtime.h>
 #include "kernel_table.hpp"
+#endif
 
 namespace rl {
+
+// H_t(ones) without a transform (line_sted_tools.py:589-592): the 'same' convolution of an image of ones with a PSF is
+// the sum of the PSF over the rectangle of taps that still meet the image,
+//     conv(1, p)[i][j] = sum over a in [i + cy - ny + 1, i + cy], b in [j + cx - nx + 1, j + cx] (inside the PSF) of p[a][b],
+// i.e. four reads of the PSF's float64 integral image I[a][b] = sum_{a' < a, b' < b} p[a'][b'] per view (sep_taps.hpp
+// box_integral_images: integ [V][py+1][px+1]); each view's sum is clamped at 0 as the reference clamps each view's convolution
+// (:587).  Exact to float64 rounding, where the transform path of an f32 plan carries ~2e-7 of white rounding noise -- an error
+// every iteration multiplies into the estimate again.  Pixel (i, j) of the [ny][nx] normaliser:
+template <typename T>
+RL_HD T box_norm_pixel(const double* __restrict__ integ, int V, int py, int px, int ny, int nx, int i, int j) {
+    const int cy = (py - 1) / 2, cx = (px - 1) / 2;
+    const int a0 = i + cy - ny + 1 > 0 ? i + cy - ny + 1 : 0, a1 = (i + cy < py - 1 ? i + cy : py - 1) + 1;
+    const int b0 = j + cx - nx + 1 > 0 ? j + cx - nx + 1 : 0, b1 = (j + cx < px - 1 ? j + cx : px - 1) + 1;
+    double acc = 0.0;
+    if (a1 > a0 && b1 > b0) {
+        for (int v = 0; v < V; ++v) {
+            const double* I = integ + (size_t)v * (py + 1) * (px + 1);
+            const double s = (I[(size_t)a1 * (px + 1) + b1] - I[(size_t)a0 * (px + 1) + b1]) - (I[(size_t)a1 * (px + 1) + b0] - I[(size_t)a0 * (px + 1) + b0]);
+            acc += s > 0.0 ? s : 0.0;
+        }
+    }
+    return (T)acc;
+}
+
+#if defined(__HIPCC__) || defined(__HIP_PLATFORM_AMD__)
 hipError_t aux_fill(int dtype, void* p, size_t n, double value, hipStream_t s);
 // psf_dev: [n_psf][py][px] float64 on the device.  wx/wy: float64 twiddle tables
 // exp(-2 pi i m / L).  s1_dev: scratch [n_psf][py][kx] complex128.
@@ -44,4 +76,5 @@ hipError_t aux_split_real(int dtype, const void* z, size_t n, void* re, double* 
 // out [ny][nx] (plan dtype) = sum_v max(conv_same(ones, psf_v), 0) from the PSFs' float64 integral images
 // integral_dev [V][py+1][px+1] (I[a][b] = sum of psf[a' < a][b' < b]): H_t(ones) to float64 rounding, no transform
 hipError_t aux_box_norm(int dtype, const double* integral_dev, void* out, int V, int py, int px, int ny, int nx, hipStream_t s);
+#endif
 }  // namespace rl

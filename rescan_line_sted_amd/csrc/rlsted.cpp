@@ -21,6 +21,7 @@
 #include "kernel_table.hpp"
 #include "ctx.hpp"
 #include "sep_kernels.hpp"
+#include "sep_taps.hpp"
 #include "stop_kernels.hpp"
 
 using namespace rl;
@@ -1211,16 +1212,8 @@ static int deconv_build(rl_deconv* h, const double* psfs) {
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     // ---- f32 plans: the normaliser to float64 rounding from the PSFs' integral images (aux_box_norm) ----
     if (h->dtype == RL_F32) {
-        const size_t py = h->py, px = h->px, stride = (py + 1) * (px + 1);
-        std::vector<double> integ(V * stride, 0.0);
-        for (size_t v = 0; v < V; ++v)
-            for (size_t a = 0; a < py; ++a) {
-                double row = 0.0;   // running sum of PSF row a
-                for (size_t b = 0; b < px; ++b) {
-                    row += psfs[(v * py + a) * px + b];
-                    integ[v * stride + (a + 1) * (px + 1) + (b + 1)] = integ[v * stride + a * (px + 1) + (b + 1)] + row;
-                }
-            }
+        std::vector<double> integ;
+        box_integral_images(psfs, V, h->py, h->px, integ);   // sep_taps.hpp
         TempBuffers tmp;
         double* integ_dev = nullptr;
         RL_TRY(tmp.get((void**)&integ_dev, integ.size() * sizeof(double)));
@@ -1233,23 +1226,8 @@ static int deconv_build(rl_deconv* h, const double* psfs) {
     const int sep_mode = h->opt.sep;
     if (sep_mode > 0 && (sep_mode > 1 || h->py + h->px <= 16) && sep_two_pass_fits(h->dtype, h->py, h->px)) {
         const size_t py = h->py, px = h->px;
-        std::vector<double> u(V * py), vv(V * px);
-        bool rank1 = true;
-        for (size_t v = 0; v < V && rank1; ++v) {
-            const double* p = psfs + v * py * px;
-            size_t a0 = 0, b0 = 0;
-            double pmax = 0.0;
-            for (size_t a = 0; a < py; ++a)
-                for (size_t b = 0; b < px; ++b)
-                    if (std::fabs(p[a * px + b]) > pmax) { pmax = std::fabs(p[a * px + b]); a0 = a; b0 = b; }
-            if (!(pmax > 0.0)) { rank1 = false; break; }
-            // cross approximation through the largest element: exact for a rank-1 matrix
-            for (size_t a = 0; a < py; ++a) u[v * py + a] = p[a * px + b0];
-            for (size_t b = 0; b < px; ++b) vv[v * px + b] = p[a0 * px + b] / p[a0 * px + b0];
-            for (size_t a = 0; a < py && rank1; ++a)
-                for (size_t b = 0; b < px; ++b)
-                    if (std::fabs(p[a * px + b] - u[v * py + a] * vv[v * px + b]) > 1e-12 * pmax) { rank1 = false; break; }
-        }
+        std::vector<double> u, vv;
+        const bool rank1 = sep_rank1_factors(psfs, V, py, px, u, vv);   // sep_taps.hpp
         if (rank1) {
             RL_TRY(h->upload_taps(&h->sep_u, u));
             RL_TRY(h->upload_taps(&h->sep_v, vv));
@@ -1258,12 +1236,8 @@ static int deconv_build(rl_deconv* h, const double* psfs) {
             // faster: profiles/r02/separable_vs_fft.json), 2 one kernel whenever the tile fits LDS
             const bool want_one = h->opt.sep_one >= 2 || (h->opt.sep_one == 1 && std::max(py, px) <= 24);
             if (want_one && sep2d_fits(h->dtype, h->py, h->px, (int)V)) {
-                const size_t pyp = (py + 7) / 8 * 8, pxp = (px + 7) / 8 * 8;
-                std::vector<double> uf(V * pyp, 0.0), vf(V * pxp, 0.0);
-                for (size_t v = 0; v < V; ++v) {
-                    for (size_t k = 0; k < py; ++k) uf[v * pyp + k] = u[v * py + (py - 1 - k)];
-                    for (size_t k = 0; k < px; ++k) vf[v * pxp + k] = vv[v * px + (px - 1 - k)];
-                }
+                std::vector<double> uf, vf;
+                sep_flipped_taps(u, vv, V, py, px, uf, vf);
                 RL_TRY(h->upload_taps(&h->sep_uf, uf));
                 RL_TRY(h->upload_taps(&h->sep_vf, vf));
                 h->sep_one = true;
@@ -1287,11 +1261,8 @@ static int deconv_build(rl_deconv* h, const double* psfs) {
         const int direct_mode = h->opt.direct;
         if (!h->sep && sep_mode > 0 && direct_mode > 0 && (direct_mode > 1 || h->py * h->px <= 49) && h->py * h->px <= 1024 &&
             direct2d_fits(h->dtype, h->py, h->px, (int)V)) {
-            const size_t py = h->py, px = h->px, pyp = (py + 7) / 8 * 8;
-            std::vector<double> f(V * px * pyp, 0.0);
-            for (size_t v = 0; v < V; ++v)
-                for (size_t l = 0; l < px; ++l)
-                    for (size_t k = 0; k < py; ++k) f[(v * px + l) * pyp + k] = psfs[(v * py + (py - 1 - k)) * px + (px - 1 - l)];
+            std::vector<double> f;
+            sep_direct_taps(psfs, V, h->py, h->px, f);
             RL_TRY(h->upload_taps(&h->sep_uf, f));
             h->sep = h->sep_one = h->sep_direct = true;      // (sep_vf stays null: that is how sep2d tells the two forms apart)
             HIP_TRY(aux_fill(h->dtype, h->scratch, V * h->n_img(), 1.0, ctx->stream));

@@ -1,11 +1,15 @@
 """The separable strategy (sep_kernels.hip): plans whose views are all rank 1 and small run H / H_t as row +
 column stencils.  Checked against the FFT strategy of the same library (RLSTED_SEP=0) and against the oracle;
 the strategy choice itself is checked through rl_deconv_strategy."""
+import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 
+import sep_reference as sr
 from conftest import max_rel, fuzz_seeds
 from oracle import line_sted_oracle as orc
 
@@ -260,3 +264,182 @@ def test_direct_stencil_keeps_f32_plans_accurate_on_dark_backgrounds(lib, monkey
         err[mode] = max_rel(e, ref)
     print('f32 against float64, 12 iterations: FFT path %.2e, direct stencil %.2e' % (err[0], err[2]))
     assert err[2] < 3e-6 and err[2] < 0.3 * err[0]
+
+
+# ------------------------------------------------------------------ per pixel, against the plain long-double reference (tests/sep_reference.py)
+FORM_KNOBS = {'two': {'RLSTED_SEP': '2', 'RLSTED_SEP_ONE': '0'}, 'one': {'RLSTED_SEP': '2', 'RLSTED_SEP_ONE': '2'},
+              'direct': {'RLSTED_SEP': '1', 'RLSTED_DIRECT': '2'}}
+
+
+@pytest.fixture(scope='module')
+def emu():
+    e = sr.Emulator()
+    yield e
+    print()
+    for line in sr.WORST.lines():
+        print(line)
+
+
+def forced_plan(lib, form, psfs, B, ny, nx, dtype):
+    """A plan made to run `form` of the stencils: RLSTED_SEP=2 with RLSTED_SEP_ONE=0 / 2, or RLSTED_DIRECT=2."""
+    knobs = FORM_KNOBS[form]
+    old = {k: os.environ.get(k) for k in knobs}
+    os.environ.update(knobs)
+    try:
+        plan = lib.DeconvPlan([p[None] for p in psfs], B, ny, nx, dtype=dtype)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+    s = plan.strategy()
+    assert (s['direct_stencil'] and not s['separable']) if form == 'direct' else s['separable'], (form, s)
+    return plan
+
+
+def plan_taps(c):
+    """What a plan hands to a form: up to 128 taps a side here (the plan also builds its FFT strategy: lengths up to 4608); the direct
+    stencil takes PSFs that are not rank 1 -- at least 2 x 2 -- of at most 1024 taps."""
+    py, px = min(c.py, 128), min(c.px, 128)
+    if c.form == 'direct':
+        py, px = max(py, 2), max(px, 2)
+        while py * px > 1024:
+            py, px = (py // 2, px) if py >= px else (py, px // 2)
+    return py, px
+
+
+def plan_case(emu, seed, dtype):
+    """Case `seed` of the CPU tests' generator at plan level: (case, the float64 PSFs the plan is given, the views as the plan uploads
+    them in its element type).  Objects and taps are values of the element type, so the plan's upload conversion adds nothing; the
+    rank-1 factors are the plan's own (sep_taps.hpp sep_rank1_factors, through the emulator library), converted as the upload converts."""
+    T = np.float32 if dtype == 'f32' else np.float64
+    c = sr.draw_data(sr.draw_geometry(seed, emu.fits_for, dtypes=(T,), allow_th64=False, max_taps=plan_taps))
+    if c.form == 'direct':
+        psfs = c.views.p.astype(np.float64)
+        views = c.views
+    else:
+        psfs = np.stack([np.outer(c.views.u[w].astype(np.float64), c.views.v[w].astype(np.float64)) for w in range(c.V)])
+        ok, fu, fv = emu.rank1(psfs)
+        assert ok
+        views = sr.Views(False, u=fu.astype(T), v=fv.astype(T))
+    return c, psfs, views
+
+
+def check_forward_and_adjoint(emu, plan, c, views, key):
+    """forward / adjoint of `plan` on case c against the reference per pixel within the derived bounds, and against the emulator
+    within twice the bound (both sides obey it).  NOT bit for bit, f64 STORE included: the device build contracts (every multiply-add
+    of k_sep2d<double, STORE> is a v_fma_f64 in the ISA of HEAD), the emulator is built with -ffp-contract=off."""
+    T, V, F, ny, nx = c.dtype, c.V, c.frames, c.ny, c.nx
+    u = sr.unit(T)
+    conv, e, A = sr.forward_ref(c.x, views, T)
+    h = plan.forward(c.x)
+    sr.check_store(h, conv, e, key, c)
+    tab = emu.tables(views, T)
+    dst, buf = sr.guarded((F, V, ny, nx), T)
+    assert emu.run(c.form, 32, sr.STORE, c.x, tab, views, dst, F, ny, nx) == 0 and sr.guards_intact(buf)
+    assert np.all(np.abs(h.astype(sr.LD) - dst.astype(sr.LD)) <= 2 * e), ('device against emulator, STORE', c)
+    cv, ev, _ = sr.forward_views_ref(c.y, views, T)
+    S = np.maximum(cv, 0).sum(axis=1)
+    E = sr.sum_bound(S, ev.sum(axis=1), V, T)
+    ht = plan.adjoint(c.y, False)
+    sr.check_sum(ht, S, E, None, T, key, c)
+    dst, buf = sr.guarded((F, ny, nx), T)
+    assert emu.run(c.form, 32, sr.SUM, c.y.reshape(F * V, ny, nx), tab, views, dst, F, ny, nx) == 0 and sr.guards_intact(buf)
+    assert np.all(np.abs(ht.astype(sr.LD) - dst.astype(sr.LD)) <= 2 * E), ('device against emulator, SUM', c)
+    # with the normaliser (the plan's own: SUM of ones through the same stencil): its bound is added, S En / n^2
+    n, cn, An = sr.norm_ref(views, ny, nx)
+    En = sr.sum_bound(n, (sr.gamma(views.depth(), u) * An).sum(axis=0), V, T)
+    sr.check_sum(plan.normalization()[None], n[None], En[None], None, T, key + ('normaliser',), c)
+    ok = n > 2 * En
+    # (signed taps: where every view's convolution of ones is negative beyond its bound the normaliser is exactly 0 in reference and
+    # plan alike and the quotient is x / 0 in both -- nothing to bound; only pixels near the clamp's kink count against the cap)
+    dead = np.all(cn < -sr.gamma(views.depth(), u) * An, axis=0)
+    assert np.all(plan.normalization()[dead] == 0) and not (c.signed is False and dead.any())
+    assert 1 - (ok | dead).mean() <= (sr.MAX_EXCLUDED if c.signed else 0.0), c
+    ref = S[:, ok] / n[ok]
+    b = E[:, ok] / n[ok] + S[:, ok] * En[ok] / n[ok] ** 2 + u * np.abs(ref)
+    err = np.abs(plan.adjoint(c.y, True)[:, ok].astype(sr.LD) - ref)
+    r = float(np.max(err[b > 0] / b[b > 0])) if np.any(b > 0) else 0.0
+    assert np.all(err[b == 0] == 0)
+    sr.WORST.note(key + ('SUM/normaliser',), r)
+    assert r <= 1, ('adjoint with the normaliser', c, r)
+
+
+@pytest.mark.parametrize('seed', fuzz_seeds(24))
+def test_random_forced_stencils_per_pixel_f64(lib, emu, seed):
+    """The generator of tests/test_sep_cpu.py at plan level (two-pass, one-kernel, DIRECT by seed), float64: forward and adjoint with
+    and without the normaliser per pixel within the derived bounds; three iterations against the oracle at 1e-11 normwise (cases
+    with non-negative taps: Richardson-Lucy's domain)."""
+    c, psfs, views = plan_case(emu, seed, 'f64')
+    print(c)
+    plan = forced_plan(lib, c.form, psfs, c.frames, c.ny, c.nx, 'f64')
+    check_forward_and_adjoint(emu, plan, c, views, (c.form, 'f64', 'plan'))
+    if not c.signed:
+        plan.set_measurement(c.aux)
+        plan.iterate(3)
+        for f in range(c.frames):
+            d = orc.Deconvolver([p[None] for p in psfs])
+            d.create_data_from_object(np.ones((1, c.ny, c.nx)), noisy_measurement=[c.aux[f, v][None].astype(np.float64) for v in range(c.V)])
+            for _ in range(3):
+                d.iterate()
+            assert max_rel(plan.estimate()[f], d.estimate[0]) < 1e-11, c
+
+
+@pytest.mark.parametrize('seed', fuzz_seeds(24))
+def test_random_forced_stencils_per_pixel_f32(lib, emu, seed):
+    """... float32: the same per-pixel bounds with u = 2^-24 (a dark pixel as accurate as a bright one); three iterations within the
+    f32 contract of 1e-5 normwise from the float64 plan of the same form."""
+    c, psfs, views = plan_case(emu, seed, 'f32')
+    print(c)
+    plan = forced_plan(lib, c.form, psfs, c.frames, c.ny, c.nx, 'f32')
+    check_forward_and_adjoint(emu, plan, c, views, (c.form, 'f32', 'plan'))
+    if not c.signed:
+        p64 = forced_plan(lib, c.form, psfs, c.frames, c.ny, c.nx, 'f64')
+        for p in (plan, p64):
+            p.set_measurement(c.aux)
+            p.iterate(3)
+        assert max_rel(plan.estimate(), p64.estimate()) < 1e-5, c
+
+
+def test_tile_height_64_per_pixel_in_a_fresh_process(lib):
+    """RLSTED_SEP_TH is read once per process: a fresh child (tests/sep_th64_child.py) creates f32 plans under RLSTED_SEP_TH=64, runs the
+    one-kernel and DIRECT forms on cases of the shared generator, compares forward and adjoint with the reference per pixel and
+    prints error / bound per case; asserted here."""
+    env = dict(os.environ, RLSTED_SEP_TH='64')
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'sep_th64_child.py')], env=env, capture_output=True,
+                       text=True, timeout=600)
+    print(r.stdout[-4000:], r.stderr[-2000:])
+    assert r.returncode == 0
+    rows = [json.loads(l) for l in r.stdout.splitlines() if l.startswith('{')]
+    assert {row['form'] for row in rows} == {'one', 'direct'} and len(rows) >= 8
+    for row in rows:
+        assert row['tile_height_env'] == '64' and row['stencil']
+        assert not row['nan'] and row['forward'] <= 1 and row['adjoint'] <= 1, row
+
+
+def test_direct_stencil_dark_background_per_pixel(lib, monkeypatch):
+    """test_direct_stencil_keeps_f32_plans_accurate_on_dark_backgrounds per pixel, on `forward`: every pixel the PSF can reach from an
+    emitter is within gamma(py * px + 2) RELATIVE of the reference (all terms are non-negative: A equals the value), every other pixel
+    is exactly 0 -- which a normwise max_rel cannot see."""
+    rng = np.random.default_rng(77)
+    ny = nx = 256
+    for dtype, T in (('f32', np.float32), ('f64', np.float64)):
+        obj = np.zeros((2, ny, nx), T)
+        for b in range(2):
+            obj[b, rng.integers(8, ny - 8, 30), rng.integers(8, nx - 8, 30)] = (rng.random(30) + 0.5).astype(T)
+        yy, xx = np.mgrid[-4:5, -4:5]
+        u, w = 0.866 * xx + 0.5 * yy, -0.5 * xx + 0.866 * yy
+        psf = np.exp(-0.5 * ((u / 1.6) ** 2 + (w / 0.8) ** 2)).astype(T)
+        plan = _direct_plan(lib, 2, [psf[None].astype(np.float64)], 2, ny, nx, dtype, monkeypatch)
+        assert plan.strategy()['direct_stencil']
+        views = sr.Views(True, p=psf[None])
+        conv, e, A = sr.forward_ref(obj, views, T)
+        h = plan.forward(obj)
+        assert np.mean(A == 0) > 0.5 and np.all(h[A == 0] == 0)
+        lit = A > 0
+        rel = np.abs(h[lit].astype(sr.LD) - conv[lit]) / conv[lit]
+        g = sr.gamma(9 * 9 + 2, sr.unit(T))
+        print('%s: largest relative error of a lit pixel %.3g, bound %.3g; smallest lit value %.3g of the maximum' %
+              (dtype, float(rel.max()), float(g), float(conv[lit].min() / conv.max())))
+        assert rel.max() <= g
