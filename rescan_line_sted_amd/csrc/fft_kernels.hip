@@ -6,6 +6,7 @@
 #include "kernel_table.hpp"
 #include "conv_kernels.hpp"
 #include "fft_configs.hpp"
+#include "outer_lds.hpp"
 #include "dev_sync.hpp"
 
 // waves/SIMD requested for the f32 ROW_RATIO kernel (needs <= 96 VGPRs, which it has
@@ -118,15 +119,7 @@ __global__ void __launch_bounds__(ColCfgFor<L>::type::T* C, (sizeof(T) == 4 && M
 // ---- long column transforms on the wave-private core (conv_kernels.hpp colconv_outer_body) ----
 // L = 2304 = 4 x 576 and 4608 = 8 x 576, f32: fft_configs.hpp OuterCol<L>.  The f64 kernels of these lengths stay
 // the workgroup-synchronous ones (4 x 9 complex doubles per lane would not fit the register file).
-// complex LDS entries of the twiddle copy (conv_kernels.hpp colconv_outer_body TWLDS)
-template <class OC>
-constexpr size_t outer_tw_lds_elems(int twlds) {
-    return (twlds > 0 ? PassTw<typename OC::Core, false, 0>::TOTAL : 0) + (twlds > 1 ? (OC::M - 1) * OC::Core::L : 0);
-}
-template <class OC>
-constexpr size_t outer_whole_lds_bytes() {
-    return ((size_t)OC::CW * LdsSlots<typename OC::Core>::value + (size_t)OC::PARK * 64 * OC::CW + outer_tw_lds_elems<OC>(OC::TWLDS)) * sizeof(cx<float>);
-}
+// (LDS byte counts of these kernels: outer_lds.hpp, shared with the host emulator)
 // NYC: the image's row count at compile time (conv_kernels.hpp colconv_outer_body): instantiated for M x 512 rows -- the
 // 1024 / 2048 / 4096-row images whose residue classes are the 512-of-576 case of the core
 template <int L, int C, bool REALP, int MODE = COL_PER_IMAGE, typename T = float, int NYC = 0>
@@ -168,10 +161,6 @@ static hipError_t allow_outer(size_t lds) {
     hipError_t e = allow_lds(k_colconv_outer<L, C, REALP, MODE, T>, lds);
     if (e == hipSuccess) e = allow_lds(k_colconv_outer<L, C, REALP, MODE, T, 512 * OuterCol<L>::M>, lds);
     return e;
-}
-template <class OC>
-constexpr size_t outer_whole_lds_bytes_f64() {
-    return ((size_t)OC::C64 * LdsSlots<typename OC::Core>::value + (size_t)OC::PARK64 * 64 * OC::C64) * sizeof(cx<double>);
 }
 template <int L>
 static void fill_outer_twiddles(double* out) {
@@ -357,9 +346,8 @@ static hipError_t launch_col(int dtype, const void* params, unsigned gx, unsigne
         if (dtype == DT_F32) {
             using OC = OuterCol<RL_CFG_L>;
             const ColParams<float>& p = *static_cast<const ColParams<float>*>(params);
-            constexpr size_t lds = (size_t)OC::C * LdsSlots<typename OC::Core>::value * sizeof(cx<float>);
             const dim3 grid((unsigned)((p.kx + OC::C - 1) / OC::C), gy), block(64 * OC::C);
-            constexpr size_t lds_split = lds + outer_tw_lds_elems<OC>(OC::TWLDS_SPLIT) * sizeof(cx<float>);
+            constexpr size_t lds_split = outer_split_lds_bytes<OC>();
             if (p.mode == COL_SPLIT_FWD) {
                 launch_outer<RL_CFG_L, OC::C, false, COL_SPLIT_FWD, float>(p, grid, block, lds_split, s);
                 return hipGetLastError();
@@ -425,6 +413,7 @@ static hipError_t prepare_rows() {
     if ((e = allow_lds(k_rowpass<RL_CFG_L, Q, ROW_RATIO, false, T>, b)) != hipSuccess) return e;
     if ((e = allow_lds(k_rowpass<RL_CFG_L, Q, ROW_UPDATE, false, T>, b)) != hipSuccess) return e;
     if ((e = allow_lds(k_rowpass<RL_CFG_L, Q, ROW_UPDATE, true, T>, b)) != hipSuccess) return e;
+    if ((e = allow_lds(k_rowpass<RL_CFG_L, Q, ROW_UPDATE, true, T, true>, b)) != hipSuccess) return e;   // PRESUM (launch_row_m)
     if ((e = allow_lds(k_rowpass<RL_CFG_L, Q, ROW_ADJ, false, T>, b)) != hipSuccess) return e;
     if ((e = allow_lds(k_rowpass<RL_CFG_L, Q, ROW_ADJ, true, T>, b)) != hipSuccess) return e;
     if constexpr (kColN512<T>) {
@@ -465,12 +454,11 @@ static hipError_t prepare() {
     }
     if constexpr (OuterCol<RL_CFG_L>::value) {
         using OC = OuterCol<RL_CFG_L>;
-        constexpr size_t lds = (size_t)OC::C * LdsSlots<typename OC::Core>::value * sizeof(cx<float>);
         constexpr size_t lds_whole = outer_whole_lds_bytes<OC>();
         static_assert(lds_whole <= 160 * 1024, "LDS of a CU");
         if ((e = allow_outer<RL_CFG_L, OC::CW, true, COL_PER_IMAGE, float>(lds_whole)) != hipSuccess) return e;
         if ((e = allow_outer<RL_CFG_L, OC::CW, false, COL_PER_IMAGE, float>(lds_whole)) != hipSuccess) return e;
-        constexpr size_t lds_split = lds + outer_tw_lds_elems<OC>(OC::TWLDS_SPLIT) * sizeof(cx<float>);
+        constexpr size_t lds_split = outer_split_lds_bytes<OC>();
         if ((e = allow_outer<RL_CFG_L, OC::C, false, COL_SPLIT_FWD, float>(lds_split)) != hipSuccess) return e;
         if ((e = allow_outer<RL_CFG_L, OC::C, true, COL_SPLIT_INV, float>(lds_split)) != hipSuccess) return e;
         if ((e = allow_outer<RL_CFG_L, OC::C, false, COL_SPLIT_INV, float>(lds_split)) != hipSuccess) return e;

@@ -14,75 +14,9 @@
 #include <vector>
 
 #define RL_TILE_WIDE_F64 1   // the device runs the two-column tile I/O in float only; here its index logic is tested in double
-#include "../../rescan_line_sted_amd/csrc/conv_kernels.hpp"
-#include "../../rescan_line_sted_amd/csrc/fft_configs.hpp"
+#include "emu_common.hpp"
 #include "../../rescan_line_sted_amd/csrc/philox_poisson.hpp"
 
-using namespace rl;
-
-struct EmuSync {
-    pthread_barrier_t* bar;        // whole workgroup
-    pthread_barrier_t* wave_bar;   // the 64 threads of this thread's wavefront
-    double* xchg;                  // 64 slots shared by the wavefront (cross-lane shuffles)
-    int lane;
-    void wg() const { pthread_barrier_wait(bar); }
-    void wave() const { pthread_barrier_wait(wave_bar); }
-    template <int MASK>
-    double shfl_xor(double v) const {
-        xchg[lane] = v;
-        pthread_barrier_wait(wave_bar);
-        const double o = xchg[lane ^ MASK];
-        pthread_barrier_wait(wave_bar);
-        return o;
-    }
-    template <int MASK>
-    float shfl_xor(float v) const { return (float)shfl_xor<MASK>((double)v); }
-    // radix-2 exchange stage (DevSync::bfly): MASK bit clear -> x + partner, set -> partner - x
-    template <int MASK, typename T>
-    void bfly(cx<T>& x, int l) const {
-        const T pr = shfl_xor<MASK>(x.re), pi = shfl_xor<MASK>(x.im);
-        if (l & MASK) x = mk<T>(pr - x.re, pi - x.im);
-        else x = mk<T>(x.re + pr, x.im + pi);
-    }
-};
-
-template <class Body>
-static void run_grid(int gx, int gy, int nthreads, size_t lds_bytes, Body body) {
-    std::vector<unsigned char> lds(lds_bytes + 64);
-    pthread_barrier_t bar;
-    pthread_barrier_init(&bar, nullptr, nthreads);
-    const int nwaves = (nthreads + 63) / 64;
-    std::vector<pthread_barrier_t> wbar(nwaves);
-    std::vector<double> xchg((size_t)nwaves * 64);
-    for (int w = 0; w < nwaves; ++w) {
-        const int n = (w + 1) * 64 <= nthreads ? 64 : nthreads - w * 64;
-        pthread_barrier_init(&wbar[w], nullptr, n);
-    }
-    for (int by = 0; by < gy; ++by)
-        for (int bx = 0; bx < gx; ++bx) {
-            std::memset(lds.data(), 0xff, lds.size());   // poison: NaNs if read before written
-            std::vector<std::thread> th;
-            th.reserve(nthreads);
-            for (int tid = 0; tid < nthreads; ++tid)
-                th.emplace_back([&, tid]() {
-                    EmuSync s{&bar, &wbar[tid / 64], &xchg[(size_t)(tid / 64) * 64], tid % 64};
-                    body(tid, bx, by, lds.data(), s);
-                });
-            for (auto& t : th) t.join();
-        }
-    pthread_barrier_destroy(&bar);
-    for (auto& b : wbar) pthread_barrier_destroy(&b);
-}
-
-template <class Cfg, typename T>
-static std::vector<cx<T>> twiddles_of() {   // the per-pass table the device plan uploads for one geometry
-    constexpr int n = PassTw<Cfg, false, 0>::TOTAL;
-    std::vector<double> h(2 * (size_t)(n > 0 ? n : 1), 0.0);
-    if (n > 0) fill_pass_twiddles<Cfg>(h.data());
-    std::vector<cx<T>> tw(n > 0 ? n : 1);
-    for (size_t i = 0; i < tw.size(); ++i) tw[i] = mk<T>((T)h[2 * i], (T)h[2 * i + 1]);
-    return tw;
-}
 template <int L, typename T>
 static std::vector<cx<T>> twiddles(bool column = false) {   // rows: CfgFor<L>::Cfg, columns: ColCfgFor<L>
     if (column) return twiddles_of<typename ColCfgFor<L>::type, T>();
@@ -237,6 +171,21 @@ int emu_row_pair_f32(int L, int mode, const float* spec_in, float* spec_out, con
 }  // extern "C"
 // ColParams-independent: waiting core results per lane kept in LDS by the whole pass (conv_kernels.hpp PARK); 0 = none
 static int g_park = 0;
+// Settings of the outer pass.  On the product's core (576) they ARE the product's, read from OuterCol<M * 576>; the 256 core
+// is a stand-in for speed with settings of its own.  (The instantiations exactly as launch_col makes them -- tile widths and
+// LDS byte counts included -- are in long_outer_emu.cpp.)
+template <class Core, int M, int C>
+struct OuterSet {
+    static constexpr int PARK = M == 4 ? 3 : M == 8 ? 14 : 5, PARK64 = M == 4 ? 10 : M == 8 ? 24 : 4;
+    static constexpr int TWLDS = (M == 8 || C == 16) ? 2 : 1, TWLDS_SPLIT = M == 8 ? 2 : M == 4 ? 1 : 0;
+};
+template <int M, int C>
+struct OuterSet<CfgFor<576>::Cfg, M, C> {
+    using OC = OuterCol<M * 576>;
+    static_assert(OC::value && OC::M == M, "an outer pass the product has");
+    static constexpr int PARK = OC::PARK > 0 ? OC::PARK : 5, PARK64 = OC::PARK64 > 0 ? OC::PARK64 : 4;   // (1152 parks nothing: the test's values)
+    static constexpr int TWLDS = OC::TWLDS, TWLDS_SPLIT = OC::TWLDS_SPLIT;
+};
 template <class Core, int M, typename T, int C = 8>
 static int col_outer_t(const T* in, T* out, const T* psf_hat, int real_psf, int ny, int kx, int pitch, int V, int frames,
                        int in_sb, int in_sv, int mode = COL_PER_IMAGE) {
@@ -260,11 +209,10 @@ static int col_outer_t(const T* in, T* out, const T* psf_hat, int real_psf, int 
     p.tw = tw.data();
     p.ny = ny; p.kx = kx; p.pitch = pitch; p.V = V; p.in_sb = in_sb; p.in_sv = in_sv;
     p.mode = mode; p.images = mode == COL_PER_IMAGE ? frames * V : frames; p.order = 1;
-    // the device's choices: f32 3 of the 4 x 10 values (L = 2304), 14 of the 8 x 10 (L = 4608); float64 (g_park == 2) 10 and 24;
-    // M = 2: 5 (for the test)
+    // parked values: OuterSet (g_park == 1: the f32 kernels' count, 2: the float64 kernels')
     auto parked = [&](auto park_c) {
         constexpr int PARK = decltype(park_c)::value;
-        constexpr int TWLDS = (M == 8 || C == 16) ? 2 : 1;     // the twiddles from an LDS copy (L = 4608 and the 16-column tiles of 2304: the outer table too)
+        constexpr int TWLDS = OuterSet<Core, M, C>::TWLDS;     // the twiddles from an LDS copy (the core's; 2: the outer table too)
         run_grid((kx + C - 1) / C, p.images, 64 * C,
                  ((size_t)C * LdsSlots<Core>::value + (size_t)PARK * 64 * C + (TWLDS > 0 ? PassTw<Core, false, 0>::TOTAL : 0) + (TWLDS > 1 ? (M - 1) * Core::L : 0)) * sizeof(cx<T>),
                  [&](int tid, int bx, int by, unsigned char* lds, EmuSync& s) {
@@ -274,11 +222,11 @@ static int col_outer_t(const T* in, T* out, const T* psf_hat, int real_psf, int 
                  });
     };
     if (g_park == 1) {
-        parked(std::integral_constant<int, M == 4 ? 3 : M == 8 ? 14 : 5>{});
+        parked(std::integral_constant<int, OuterSet<Core, M, C>::PARK>{});
         return 0;
     }
     if (g_park == 2) {
-        parked(std::integral_constant<int, M == 4 ? 10 : M == 8 ? 24 : 4>{});
+        parked(std::integral_constant<int, OuterSet<Core, M, C>::PARK64>{});
         return 0;
     }
     run_grid((kx + C - 1) / C, p.images, 64 * C, (size_t)C * LdsSlots<Core>::value * sizeof(cx<T>),
@@ -331,7 +279,7 @@ static int col_outer_split_t(const T* in, T* out, const T* psf_hat, int real_psf
     p.ny = ny; p.kx = kx; p.pitch = pitch; p.V = V; p.in_sb = 1; p.in_sv = 0; p.order = 1;
     p.xs_out = xs.data();
     p.xs_in = xs.data();
-    constexpr int TWS = M == 8 ? 2 : M == 4 ? 1 : 0;      // the device's OuterCol<L>::TWLDS_SPLIT
+    constexpr int TWS = OuterSet<Core, M, C>::TWLDS_SPLIT;
     constexpr size_t lds_split = ((size_t)C * LdsSlots<Core>::value + (TWS > 0 ? PassTw<Core, false, 0>::TOTAL : 0) + (TWS > 1 ? (M - 1) * Core::L : 0)) * sizeof(cx<T>);
     p.mode = COL_SPLIT_FWD; p.images = n_in;
     run_grid((kx + C - 1) / C, p.images, 64 * C, lds_split,

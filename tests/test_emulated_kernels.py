@@ -25,8 +25,8 @@ def emu():
         return ctypes.CDLL(os.environ['RLSTED_EMU_LIB'])
     so = os.path.join(EMU_DIR, 'libemu.so')
     src = os.path.join(EMU_DIR, 'emu.cpp')
-    deps = [src] + [os.path.join(ROOT, 'rescan_line_sted_amd', 'csrc', f)
-                    for f in ('conv_kernels.hpp', 'fft_core.hpp', 'fft_configs.hpp', 'philox_poisson.hpp')]
+    deps = [src, os.path.join(EMU_DIR, 'emu_common.hpp')] + [os.path.join(ROOT, 'rescan_line_sted_amd', 'csrc', f)
+                                                             for f in ('conv_kernels.hpp', 'fft_core.hpp', 'fft_configs.hpp', 'philox_poisson.hpp')]
     if (not os.path.exists(so) or
             os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps)):
         subprocess.check_call(['g++', '-O2', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=off',
@@ -393,7 +393,10 @@ def test_outer_decimation_column_pass(emu, Li, M, ny, kx, real_psf, park):
     """colconv_outer_body: L = M * Li as M core transforms plus one radix-M step in registers (the f32
     column kernel of L = 1152 = 2 x 576, 2304 = 4 x 576 and 4608 = 8 x 576).  Against numpy: IFFT_y(FFT_y(x zero padded to L) * psf_hat),
     rows < ny.  park: some of the waiting core results per lane wait in LDS instead of registers (PARK: 3 of 4 x 10 used in place
-    during the radix-4 steps, 14 of 8 x 10 brought back for them; park = 2: the float64 kernels' 10 and 24) and the twiddles are read from an LDS copy -- the same values either way."""
+    during the radix-4 steps, 14 of 8 x 10 brought back for them; park = 2: the float64 kernels' counts, read from OuterCol<L>) and the twiddles are read from an LDS copy -- the same values either way.
+    This is the ARITHMETIC of the body in double on this emulator's own tile widths and LDS layout, PARK / TWLDS from OuterCol<L>; the
+    instantiations launch_col makes -- float on CW columns, float64 on C64, the launcher's LDS byte count -- run in
+    tests/test_long_rows_cpu.py (tests/emu/long_outer_emu.cpp)."""
     emu.emu_set_park.argtypes = [ctypes.c_int]
     L, V, frames = (4 if M == 16 else M) * Li, 2, 1
     pitch = (kx + 7) // 8 * 8

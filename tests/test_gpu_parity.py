@@ -809,3 +809,140 @@ def test_512_point_sted_100_iterations_f32_inside_the_contract(lib, golden, astr
         errs[k] = max(max_rel(p32.estimate()[f], p64.estimate()[f]) for f in range(2))
     print('f32 vs f64, astronaut 512^2:', errs)
     assert errs[20] < 3e-6 and errs[100] < F32_TOL, errs
+
+
+# ------------------------------------------------- the long row lengths, per pixel against a long-double reference
+def _long_row_radices():
+    """radix lists of the row kernels of 1152 / 2304 / 4608 and of the 64-row column kernel, read from fft_configs.hpp"""
+    import re
+    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'rescan_line_sted_amd', 'csrc', 'fft_configs.hpp')).read()
+    out = {}
+    for L in (64, 1152, 2304, 4608):
+        m = re.search(r'struct CfgFor<%d> \{.*?using Cfg = FftCfg<%d, \d+, ([\d, ]+)>;' % (L, L), text, flags=re.S)
+        out[L] = tuple(int(r) for r in m.group(1).split(','))
+    return out
+
+
+@pytest.mark.parametrize('L', [1152, 2304, 4608])
+def test_long_rows_per_pixel_against_long_double(lib, L):
+    """The edge table of tests/test_long_rows_cpu.py at plan level: a one-row PSF of 61 taps (no stencil strategy takes it, the
+    column transforms stay at 64), so that H and one Richardson-Lucy iteration have an affordable long-double reference -- the
+    convolution sums themselves.  f64 and f32 plans (frame pairs with a phantom partner, `ratio - 1`), every pixel within the
+    bound propagated as tests/fft_reference.py derives it; no tolerance is a literal.  The bound is K x (L1 of what shares the
+    transforms) x (L1 of the PSF), a worst case met only where one pixel and one tap carry those sums: the one-pixel edges under the
+    PSF with 95 % in its centre tap are the sharp cases (H of the lit pixel: error / bound 0.011-0.020 on the device, the bound
+    ~1e-5 of the peak in float, ~1e-14 in float64 -- finer than the plan tolerances of the other tests).  The dense edges and the
+    iteration are structural at this level (error / bound < 1e-3): an iteration's prediction is dense whatever the estimate -- a
+    dim floor under a lit pixel is known only to K x L1 absolutely, 1e-5 / floor relatively, and 60 such neighbours reach every
+    pixel of `ratio` through the PSF -- so its sharp check is the CPU module's row chain."""
+    import fft_reference as fr
+    LD = fr.LD
+    radices = _long_row_radices()
+    px, hx = 61, 30
+    rng = np.random.default_rng(L)
+    taps_flat = (rng.random(px) + 0.05)
+    taps_flat /= taps_flat.sum()
+    hi = L - hx
+    lo = hi
+    while lib.lib.rl_fft_length_for(lo - 1 + hx) == L:
+        lo -= 1
+    table = fr.edge_rows(lo, hi)          # the CPU module's table, at the image widths that select L with this PSF
+    assert lib.lib.rl_fft_length_for(1 + hx) != L
+    for edge, (ny, nx, kind) in table.items():
+        if nx == 1:             # a plan of one-pixel rows selects the shortest length (asserted above; test_edge_cases runs it): the
+            assert edge in ('one pixel wide', 'one column')      # long row bodies meet nx = 1 in the CPU module alone
+            continue
+        B = 3
+        obj = (rng.random((B, ny, nx)) * 3 + 0.5).astype(np.float32).astype(np.float64)
+        meas = (rng.random((B, 1, ny, nx)) * 5).astype(np.float32).astype(np.float64)
+        if kind == 'one_pixel':
+            o2 = np.zeros_like(obj)
+            o2[:, ny // 2, 2 * nx // 3] = 100.0
+            obj = o2
+            m2 = np.zeros_like(meas)
+            m2[:, :, ny // 2, nx // 3] = 7.0
+            meas = m2
+        if kind == 'zero_row':
+            obj[:, :2] = 0
+            meas[:, :, :2] = 0
+        if kind == 'negative':
+            meas[rng.random(meas.shape) < 0.2] *= -1
+        # The bound is (L1 of the frame) x (L1 of the PSF): met only where one pixel AND one tap carry the sums.  The one-pixel edges
+        # therefore run a second PSF too, 95 % of it in the centre tap: H of the lit pixel is then the sharp case of this test.
+        variants = [('', taps_flat)]
+        if kind == 'one_pixel':
+            peaked = 0.05 * taps_flat
+            peaked[hx] += 0.95
+            variants.append((', peaked PSF', peaked))
+        for pname, taps in variants:
+            psf = taps.reshape(1, 1, px)
+            h1 = LD(np.abs(taps).sum())
+            for dtype in ('f64', 'f32'):
+                T = np.float32 if dtype == 'f32' else np.float64
+                plan = lib.DeconvPlan([psf], B, ny, nx, dtype=dtype)
+                st_ = plan.strategy()
+                assert plan.info()['lx'] == L and plan.info()['ly'] == 64 and not st_['separable'] and not st_['direct_stencil'], (edge, st_)
+                pairs = dtype == 'f32'        # (frame pairs are the f32 single-view loop; where a launch is per frame the partner's share only widens the bound)
+                sub_one = dtype == 'f32'
+                K = fr.plan_conv_growth(radices[L], radices[64], T, px) * h1
+                ar = fr.Arith(T, radices[L], div=3 if dtype == 'f32' else 1)
+
+                def shared_l1(x):          # L1 norm of what shares a frame's transforms: the frame, and its partner in a frame pair
+                    s = np.abs(np.asarray(x, dtype=LD)).reshape(B, -1).sum(axis=1)
+                    if not pairs:
+                        return s
+                    partner = [b + 1 if b % 2 == 0 else b - 1 for b in range(B)]
+                    return s + np.array([s[p] if p < B else s[b] for b, p in enumerate(partner)], dtype=LD)
+                key = ('plan', dtype, L, ('one pixel lit' if kind == 'one_pixel' else 'dense rows') + pname)
+                ctx = (edge, ny, nx, kind, dtype, pname)
+                # H (the sharp case: frame 0 alone carries its pair's sum -- its partner is dark)
+                x = obj.copy()
+                if pname:
+                    x[1] = 0
+                got = plan.forward(x)[:, 0]
+                ref = fr.conv_same_x(x, taps)
+                e = (K * shared_l1(x))[:, None, None]
+                fr.check(got, np.maximum(ref, 0), np.broadcast_to(e, ref.shape), key + ('H',), ctx)
+                # one iteration from estimate = 1
+                plan.set_measurement(meas)
+                plan.reset_estimate()
+                plan.iterate(1)
+                est = plan.estimate()
+                norm = plan.normalization().astype(LD)
+                ones = np.ones((B, ny, nx), dtype=LD)
+                pred = fr.conv_same_x(ones, taps)
+                e_pred = (K * shared_l1(ones))[:, None, None]
+                r, dr, undecided = ar.ratio(meas[:, 0], pred, np.broadcast_to(e_pred, pred.shape), sub_one)
+                assert not undecided.any(), ctx
+                a = fr.conv_same_x(r, taps)
+                da = fr.conv_same_x(dr, np.abs(taps)) + (K * (shared_l1(r) + shared_l1(dr)))[:, None, None]
+                fac, dfac = ar.factor(a if sub_one else np.maximum(a, 0), da, norm, sub_one)
+                new, dnew = ar.product(ones, fac, dfac)
+                fr.check(est, new, dnew, key + ('iteration',), ctx)
+                assert plan.unresolved() == 0
+                del plan
+    for line in fr.WORST.lines():
+        if "plan" in line and str(L) in line:
+            print(line)
+
+
+def test_float64_multi_view_ratio_minus_one_on_the_longest_rows(lib, monkeypatch):
+    """A float64 row transform of 4608 needs more than the default 64 KB of dynamic LDS.  The multi-view `ratio - 1` update
+    (rowpass_body PRESUM; float64 plans run it with RLSTED_SUB_ONE=1) was missing from the kernels prepare() raises the limit of
+    (tests/test_long_rows_cpu.py::test_every_launchable_row_kernel_may_use_its_lds): the launch must succeed and agree with the
+    plain float64 iteration, which is the same iteration in exact arithmetic."""
+    rng = np.random.default_rng(4608)
+    ny, nx, B, px = 4, 2400, 1, 61
+    psfs = [(rng.random((1, 1, px)) + 0.05) for _ in range(2)]
+    meas = rng.random((B, 2, ny, nx)) * 5 + 0.5
+    est = []
+    for sub in ('0', '1'):
+        monkeypatch.setenv('RLSTED_SUB_ONE', sub)
+        plan = lib.DeconvPlan(psfs, B, ny, nx, dtype='f64')
+        assert plan.info()['lx'] == 4608 and not plan.strategy()['separable'] and not plan.strategy()['direct_stencil']
+        plan.set_measurement(meas)
+        plan.iterate(3)
+        est.append(plan.estimate())
+        del plan
+    assert np.isfinite(est[1]).all()
+    assert max_rel(est[1], est[0]) < F64_TOL
