@@ -1,6 +1,6 @@
 // conv_kernels.hpp -- workgroup bodies of the FFT-convolution / Richardson-Lucy
-// kernels.  Shared by the HIP kernels (rlsted_kernels.hip) and by the host
-// emulator used in the CPU tests (tests/emu/emu.cpp).
+// kernels.  Shared by the HIP kernels (fft_kernels.hip) and by the host
+// emulators used in the CPU tests (tests/emu).
 //
 // Reference semantics implemented here (figure_generation/line_sted_tools.py):
 //   H   :567-577  per PSF: zero padded 'same' convolution, clamp negatives to 0
@@ -140,7 +140,7 @@ struct ColParams {
     int V;                  // views per frame; blockIdx.y = frame*V + view
     int in_sb, in_sv;       // COL_PER_IMAGE: input image index = frame*in_sb + view*in_sv
     int mode;               // ColMode (wave-private column kernel only; others: per image)
-    int images;             // streaming kernel: output images covered by the launch (grid.y of the tiled kernel)
+    int images;             // output images covered by the launch (grid.y)
     int order;              // tiled kernel's work order: images per block of the tile order (1 = image-major)
     // A point-symmetric PSF has a real spectrum: its real parts alone, same indexing as the transposed
     // psf_hat ([view][kx][L]); used by the REALP instantiations of the wave-private column kernel
@@ -878,7 +878,7 @@ struct RowParams {
     const T* scale;         // ROW_FWD: per-frame multiplier or nullptr
     const cx<T>* tw;        // [Lx]
     int ny, nx, pitch, V;
-    int frames;             // streaming kernels: images covered by the launch (grid.y of the tiled kernels)
+    int frames;             // images covered by the launch (grid.y)
     // > 0: image i reads input spectrum i % in_mod (single-spectrum modes).  The first RL iteration starts
     // from estimate = 1 (ref:522), whose H(est) is the same for every frame: its V column-transformed
     // spectra are computed once per plan and every frame's ROW_RATIO reads them.

@@ -4,8 +4,7 @@
 // convolution path; bodies in conv_kernels.hpp.
 #include <hip/hip_ext.h>
 #include "kernel_table.hpp"
-#include "conv_kernels.hpp"
-#include "fft_configs.hpp"
+#include "kernel_variants.hpp"
 #include "outer_lds.hpp"
 #include "dev_sync.hpp"
 
@@ -60,16 +59,8 @@ constexpr int kC32 = CF::C32, kC64 = CF::C64, kQ32 = CF::Q32, kQ64 = CF::Q64;
 #define RL_CAT(a, b) RL_CAT_(a, b)
 #define RL_TABLE_FN RL_CAT(table_, RL_CFG_L)
 
-// Kernels specialised for the 512 x 512 frames of the BASELINE headline (L = 576, f32): row / column counts at compile time.
-#ifndef RL_N512
-#define RL_N512 1
-#endif
 template <typename T>
-constexpr bool kColN512 = RL_N512 != 0 && RL_CFG_L == 576 && sizeof(T) == 4;
-// ... and the frame-pair row kernels of L = 2304 for 2048-pixel rows (register slots of 256 pixels: 8 of 9 hold pixels)
-template <typename T>
-constexpr bool kRowN2048 = RL_N512 != 0 && RL_CFG_L == 2304 && sizeof(T) == 4;
-
+using Special = DeviceSpecial<RL_CFG_L, T>;   // the image sizes some variants are compiled for (kernel_variants.hpp)
 
 // NOTE: the transform length is a template parameter of the kernels so that the
 // kernels of different lengths (built in separate translation units) have
@@ -149,19 +140,6 @@ __global__ void __launch_bounds__(64 * C, (sizeof(T) == 4 ? OuterCol<L>::MIN_WAV
     else
         colconv_outer_body<typename OC::Core, OC::M, C, double, REALP, COL_PER_IMAGE, OC::PARK64, 0, NYC>(p, (int)threadIdx.x, (int)bx, (int)by, reinterpret_cast<cx<double>*>(smem), s);
 }
-// launch either the generic kernel or -- M x 512 rows, pitch a multiple of the tile width -- the one with the row count at compile time
-template <int L, int C, bool REALP, int MODE, typename T>
-static void launch_outer(const ColParams<T>& p, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
-    constexpr int NY = 512 * OuterCol<L>::M;
-    if (RL_N512 != 0 && p.ny == NY && p.pitch % C == 0) rl_launch(k_colconv_outer<L, C, REALP, MODE, T, NY>, grid, block, lds, s, p);
-    else rl_launch(k_colconv_outer<L, C, REALP, MODE, T>, grid, block, lds, s, p);
-}
-template <int L, int C, bool REALP, int MODE, typename T>
-static hipError_t allow_outer(size_t lds) {
-    hipError_t e = allow_lds(k_colconv_outer<L, C, REALP, MODE, T>, lds);
-    if (e == hipSuccess) e = allow_lds(k_colconv_outer<L, C, REALP, MODE, T, 512 * OuterCol<L>::M>, lds);
-    return e;
-}
 template <int L>
 static void fill_outer_twiddles(double* out) {
     using OC = OuterCol<L>;
@@ -179,12 +157,7 @@ static void fill_outer_twiddles(double* out) {
 // waves per SIMD requested from the register allocator (f32, wave-private lengths)
 template <int L, int MODE, bool ONEV, typename T>
 constexpr int row_min_waves() {
-    if (sizeof(T) == 4 && !WavePrivate<typename CfgFor<L>::Cfg>::value) {   // the long lengths (256 threads per transform)
-        if (MODE == ROW_RATIO) return 1;
-        if (MODE == ROW_UPDATE && ONEV) return 1;
-        return 1;
-    }
-    if (sizeof(T) != 4) return 1;
+    if (sizeof(T) != 4 || !WavePrivate<typename CfgFor<L>::Cfg>::value) return 1;   // float64; the long lengths (256 threads per transform)
     if (MODE == ROW_RATIO) return RL_ROW_MIN_WAVES;
     if (MODE == ROW_UPDATE && ONEV) return RL_UPD_MIN_WAVES;
     return 1;
@@ -199,9 +172,7 @@ __global__ void __launch_bounds__(CfgFor<L>::Cfg::T* Q, (row_min_waves<L, MODE, 
     // (An XCD-consistent remap of (image, row group) items like k_colconv's measured neutral on time and cost traffic -- every
     // XCD's L2 then streams the whole normaliser instead of the eighth its row groups touch: removed.)
     const unsigned bx = blockIdx.x, by = blockIdx.y;
-    // single-view RL modes of the wave-private lengths: the lean item code (scalar row bases,
-    // unconditional loads).  RATIO treats every (frame, view) image on its own, so it always qualifies.
-    constexpr bool LEAN = !PRESUM && WavePrivate<KCfg>::value && (MODE == ROW_RATIO || (MODE == ROW_UPDATE && ONEV));
+    constexpr bool LEAN = kRowLean<KCfg, MODE, ONEV, PRESUM>;
     static_assert(NXC == 0 || LEAN, "the compile-time row length exists for the lean bodies");
     if constexpr (LEAN)
         rowlean_body<KCfg, Q, MODE, T, NXC, SUBC>(p, (int)threadIdx.x, (int)bx, (int)by, reinterpret_cast<cx<T>*>(smem), s);
@@ -218,53 +189,6 @@ static constexpr size_t col_lds_bytes() {
     return (size_t)C * LdsSlots<CCfg>::value * sizeof(cx<T>);
 }
 
-template <int C, typename T>
-static hipError_t launch_col_t(const void* params, unsigned gx, unsigned gy, hipStream_t s) {
-    const ColParams<T>& p = *static_cast<const ColParams<T>*>(params);
-    const dim3 grid(gx, gy), block(CCfg::T * C);
-    constexpr size_t lds = col_lds_bytes<C, T>();
-    if constexpr (WavePrivate<CCfg>::value) {
-        if constexpr (kColN512<T>) {   // 512 rows exactly, one view: the specialised kernels (conv_kernels.hpp colconv_wave_body NYC)
-            if (p.mode == COL_PER_IMAGE && p.ny == 512 && p.V == 1 && p.pitch % C == 0) {
-                if (p.residual && RL_CT_RESIDUAL) {   // the spectrum is that of `ratio - 1`: compact twiddles
-                    if (p.psf_hat_re) rl_launch(k_colconv<RL_CFG_L, C, COL_PER_IMAGE, T, true, 512, 1>, grid, block, lds, s, p);
-                    else rl_launch(k_colconv<RL_CFG_L, C, COL_PER_IMAGE, T, false, 512, 1>, grid, block, lds, s, p);
-                    return hipGetLastError();
-                }
-                if (p.psf_hat_re) rl_launch(k_colconv<RL_CFG_L, C, COL_PER_IMAGE, T, true, 512>, grid, block, lds, s, p);
-                else rl_launch(k_colconv<RL_CFG_L, C, COL_PER_IMAGE, T, false, 512>, grid, block, lds, s, p);
-                return hipGetLastError();
-            }
-        }
-        if constexpr (kColN512<T>) {   // the fused multi-view modes on 512-row images (real multiplier: what the reference's PSFs run)
-            if (p.psf_hat_re && p.ny == 512 && p.pitch % C == 0 && (p.mode == COL_H_MULTI || p.mode == COL_HT_SUM)) {
-                if (p.mode == COL_H_MULTI) rl_launch(k_colconv<RL_CFG_L, C, COL_H_MULTI, T, true, 512>, grid, block, lds, s, p);
-                else if (p.residual && RL_CT_RESIDUAL) rl_launch(k_colconv<RL_CFG_L, C, COL_HT_SUM, T, true, 512, 1>, grid, block, lds, s, p);   // spectra of `ratio - 1`
-                else rl_launch(k_colconv<RL_CFG_L, C, COL_HT_SUM, T, true, 512>, grid, block, lds, s, p);
-                return hipGetLastError();
-            }
-        }
-        if (p.psf_hat_re) {   // real PSF spectrum
-            if (p.mode == COL_H_MULTI) rl_launch(k_colconv<RL_CFG_L, C, COL_H_MULTI, T, true>, grid, block, lds, s, p);
-            else if (p.mode == COL_HT_SUM) rl_launch(k_colconv<RL_CFG_L, C, COL_HT_SUM, T, true>, grid, block, lds, s, p);
-            else if (p.mode == COL_PER_IMAGE) rl_launch(k_colconv<RL_CFG_L, C, COL_PER_IMAGE, T, true>, grid, block, lds, s, p);
-            else return hipErrorInvalidValue;
-            return hipGetLastError();
-        }
-        if (p.mode == COL_H_MULTI) {
-            rl_launch(k_colconv<RL_CFG_L, C, COL_H_MULTI, T>, grid, block, lds, s, p);
-            return hipGetLastError();
-        }
-        if (p.mode == COL_HT_SUM) {
-            rl_launch(k_colconv<RL_CFG_L, C, COL_HT_SUM, T>, grid, block, lds, s, p);
-            return hipGetLastError();
-        }
-    }
-    if (p.mode != COL_PER_IMAGE) return hipErrorInvalidValue;
-    rl_launch(k_colconv<RL_CFG_L, C, COL_PER_IMAGE, T>, grid, block, lds, s, p);
-    return hipGetLastError();
-}
-
 // frame-pair row kernels (rowpair_body)
 template <int L, int Q, int MODE, typename T, int NXC = 0, int SUBC = -1>
 __global__ void __launch_bounds__(CfgFor<L>::Cfg::T * Q, (row_min_waves<L, MODE == ROW_FWD ? ROW_RATIO : MODE, true, T>())) k_rowpair(const RowParams<T> p) {
@@ -274,206 +198,109 @@ __global__ void __launch_bounds__(CfgFor<L>::Cfg::T * Q, (row_min_waves<L, MODE 
     if constexpr (WavePrivate<KCfg>::value || Q == 1)
         rowpair_body<KCfg, Q, MODE, T, NXC, SUBC>(p, (int)threadIdx.x, (int)blockIdx.x, (int)blockIdx.y, reinterpret_cast<cx<T>*>(smem), s);
 }
-template <int Q, typename T>
-static hipError_t launch_row_pair_t(int mode, const void* params, unsigned gy, hipStream_t s) {
-    if constexpr (WavePrivate<Cfg>::value || Q == 1) {
-        const RowParams<T>& p = *static_cast<const RowParams<T>*>(params);
-        const dim3 grid((unsigned)((p.ny + Q - 1) / Q), gy), block(Cfg::T * Q);
-        const size_t lds = lds_bytes<Q, T>();
-        if constexpr (kColN512<T>) {   // 512-pixel rows, one view, `ratio - 1`: the specialised kernels (rowpair_body NXC / SUBC)
-            if (p.nx == 512 && p.V == 1 && p.sub_one != 0 && mode != ROW_FWD) {
-                if (mode == ROW_RATIO) rl_launch(k_rowpair<RL_CFG_L, Q, ROW_RATIO, T, 512, 1>, grid, block, lds, s, p);
-                else if (mode == ROW_UPDATE) rl_launch(k_rowpair<RL_CFG_L, Q, ROW_UPDATE, T, 512, 1>, grid, block, lds, s, p);
-                else return hipErrorInvalidValue;
-                return hipGetLastError();
-            }
-        }
-        if constexpr (kRowN2048<T>) {
-            if (p.nx == 2048 && p.V == 1 && p.sub_one != 0 && mode != ROW_FWD) {
-                if (mode == ROW_RATIO) rl_launch(k_rowpair<RL_CFG_L, Q, ROW_RATIO, T, 2048, 1>, grid, block, lds, s, p);
-                else if (mode == ROW_UPDATE) rl_launch(k_rowpair<RL_CFG_L, Q, ROW_UPDATE, T, 2048, 1>, grid, block, lds, s, p);
-                else return hipErrorInvalidValue;
-                return hipGetLastError();
-            }
-        }
-        if (mode == ROW_FWD) rl_launch(k_rowpair<RL_CFG_L, Q, ROW_FWD, T>, grid, block, lds, s, p);
-        else if (mode == ROW_RATIO) rl_launch(k_rowpair<RL_CFG_L, Q, ROW_RATIO, T>, grid, block, lds, s, p);
-        else if (mode == ROW_UPDATE) rl_launch(k_rowpair<RL_CFG_L, Q, ROW_UPDATE, T>, grid, block, lds, s, p);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
-    } else {
-        return hipErrorInvalidValue;
-    }
-}
-
-template <int Q, int MODE, typename T>
-static hipError_t launch_row_m(const void* params, unsigned gx, unsigned gy, hipStream_t s) {
-    const RowParams<T>& p = *static_cast<const RowParams<T>*>(params);
-    constexpr bool MULTI = (MODE == ROW_UPDATE || MODE == ROW_ADJ);
-    if constexpr (MODE == ROW_UPDATE) {
-        if (p.V > 1 && p.sub_one) {   // the views' residual spectra are summed on their way in: one inverse transform (rowpass_body PRESUM)
-            rl_launch(k_rowpass<RL_CFG_L, Q, MODE, true, T, true>, dim3(gx, gy), dim3(Cfg::T * Q), lds_bytes<Q, T>(), s, p);
-            return hipGetLastError();
-        }
-    }
-    if constexpr (kColN512<T> && (MODE == ROW_RATIO || MODE == ROW_UPDATE)) {   // per-frame lean bodies on 512-pixel rows (multi-view plans' RATIO,
-        if (p.nx == 512 && p.sub_one != 0 && (MODE == ROW_RATIO || p.V == 1)) {   // the single-spectrum UPDATE behind the column view sum, f32)
-            rl_launch(k_rowpass<RL_CFG_L, Q, MODE, MODE == ROW_UPDATE, T, false, 512, 1>, dim3(gx, gy), dim3(Cfg::T * Q), lds_bytes<Q, T>(), s, p);
-            return hipGetLastError();
-        }
-    }
-    if (MULTI && p.V == 1)   // single view: variant without accumulator registers
-        rl_launch(k_rowpass<RL_CFG_L, Q, MODE, MULTI, T>, dim3(gx, gy), dim3(Cfg::T * Q), lds_bytes<Q, T>(), s, p);
-    else
-        rl_launch(k_rowpass<RL_CFG_L, Q, MODE, false, T>, dim3(gx, gy), dim3(Cfg::T * Q), lds_bytes<Q, T>(), s, p);
-    return hipGetLastError();
-}
-
-template <int Q, typename T>
-static hipError_t launch_row_t(int mode, const void* params, unsigned gx, unsigned gy, hipStream_t s) {
-    switch (mode) {
-        case ROW_FWD: return launch_row_m<Q, ROW_FWD, T>(params, gx, gy, s);
-        case ROW_INV: return launch_row_m<Q, ROW_INV, T>(params, gx, gy, s);
-        case ROW_RATIO: return launch_row_m<Q, ROW_RATIO, T>(params, gx, gy, s);
-        case ROW_UPDATE: return launch_row_m<Q, ROW_UPDATE, T>(params, gx, gy, s);
-        case ROW_ADJ: return launch_row_m<Q, ROW_ADJ, T>(params, gx, gy, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-static hipError_t launch_col(int dtype, const void* params, unsigned gx, unsigned gy, hipStream_t s) {
-    if constexpr (OuterCol<RL_CFG_L>::value) {
-        if (dtype == DT_F32) {
-            using OC = OuterCol<RL_CFG_L>;
-            const ColParams<float>& p = *static_cast<const ColParams<float>*>(params);
-            const dim3 grid((unsigned)((p.kx + OC::C - 1) / OC::C), gy), block(64 * OC::C);
-            constexpr size_t lds_split = outer_split_lds_bytes<OC>();
-            if (p.mode == COL_SPLIT_FWD) {
-                launch_outer<RL_CFG_L, OC::C, false, COL_SPLIT_FWD, float>(p, grid, block, lds_split, s);
-                return hipGetLastError();
-            }
-            if (p.mode == COL_SPLIT_INV) {
-                if (p.psf_hat_re) launch_outer<RL_CFG_L, OC::C, true, COL_SPLIT_INV, float>(p, grid, block, lds_split, s);
-                else launch_outer<RL_CFG_L, OC::C, false, COL_SPLIT_INV, float>(p, grid, block, lds_split, s);
-                return hipGetLastError();
-            }
-            if (p.mode == COL_SPLIT_INV_SUM) {
-                if (p.psf_hat_re) launch_outer<RL_CFG_L, OC::C, true, COL_SPLIT_INV_SUM, float>(p, grid, block, lds_split, s);
-                else launch_outer<RL_CFG_L, OC::C, false, COL_SPLIT_INV_SUM, float>(p, grid, block, lds_split, s);
-                return hipGetLastError();
-            }
-            if (p.mode != COL_PER_IMAGE) return hipErrorInvalidValue;
-            // the whole pass has a tile width of its own (OC::CW), its transform regions + parking space + twiddle copies
-            constexpr size_t lds_whole = outer_whole_lds_bytes<OC>();
-            const dim3 grid_w((unsigned)((p.kx + OC::CW - 1) / OC::CW), gy), block_w(64 * OC::CW);
-            if (p.psf_hat_re) launch_outer<RL_CFG_L, OC::CW, true, COL_PER_IMAGE, float>(p, grid_w, block_w, lds_whole, s);
-            else launch_outer<RL_CFG_L, OC::CW, false, COL_PER_IMAGE, float>(p, grid_w, block_w, lds_whole, s);
-            return hipGetLastError();
-        }
-    }
-    if constexpr (OuterCol<RL_CFG_L>::value64) {
-        if (dtype != DT_F32) {   // float64: the whole pass on the outer-decimation body (per image; multi-view plans launch it per view)
-            using OC = OuterCol<RL_CFG_L>;
-            const ColParams<double>& p = *static_cast<const ColParams<double>*>(params);
-            if (p.mode != COL_PER_IMAGE) return hipErrorInvalidValue;
-            constexpr size_t lds = outer_whole_lds_bytes_f64<OC>();
-            const dim3 grid((unsigned)((p.kx + OC::C64 - 1) / OC::C64), gy), block(64 * OC::C64);
-            if (p.psf_hat_re) launch_outer<RL_CFG_L, OC::C64, true, COL_PER_IMAGE, double>(p, grid, block, lds, s);
-            else launch_outer<RL_CFG_L, OC::C64, false, COL_PER_IMAGE, double>(p, grid, block, lds, s);
-            return hipGetLastError();
-        }
-    }
-    return dtype == DT_F32 ? launch_col_t<kC32, float>(params, gx, gy, s)
-                           : launch_col_t<kC64, double>(params, gx, gy, s);
-}
-
-static hipError_t launch_row(int dtype, int mode, const void* params, unsigned gx, unsigned gy, hipStream_t s) {
-    return dtype == DT_F32 ? launch_row_t<kQ32, float>(mode, params, gx, gy, s)
-                           : launch_row_t<kQ64, double>(mode, params, gx, gy, s);
-}
 // rows (= waves) per workgroup of the frame-pair row kernels, f32 (RL_PAIR_Q32; measured at 512^2: 2 / 4 / 8 / 16 rows
 // 18.4 / 18.8 / 19.1 / ... k frames/s)
 #ifndef RL_PAIR_Q32
 #define RL_PAIR_Q32 8
 #endif
 constexpr int kPairQ32 = WavePrivate<Cfg>::value ? RL_PAIR_Q32 : kQ32;
-// frame-pair row kernels exist for one transform per wave and for one workgroup-synchronous transform per workgroup
-constexpr bool kPairRows = WavePrivate<Cfg>::value || (kQ32 == 1 && kQ64 == 1);
+
+// The launchers: the selector of kernel_variants.hpp names a variant, one walk over the family's list turns the name into
+// the instantiation.  A request no variant serves is hipErrorInvalidValue.
+template <int C, typename T>
+static hipError_t launch_col_t(const void* params, unsigned gx, unsigned gy, hipStream_t s) {
+    const ColParams<T>& p = *static_cast<const ColParams<T>*>(params);
+    ColKey k;
+    if (!select_colconv(WavePrivate<CCfg>::value, Special<T>::col_ny, p.mode, p.ny, p.V, p.pitch % C == 0, p.psf_hat_re != nullptr, p.residual != 0, k))
+        return hipErrorInvalidValue;
+    const bool found = for_each_colconv<RL_CFG_L, Special<T>>([&](auto v) {
+        using V = decltype(v);
+        if (!(V::key() == k)) return false;
+        rl_launch(k_colconv<RL_CFG_L, C, V::MODE, T, V::REALP, V::NYC, V::CT>, dim3(gx, gy), dim3(CCfg::T * C), col_lds_bytes<C, T>(), s, p);
+        return true;
+    });
+    return found ? hipGetLastError() : hipErrorInvalidValue;
+}
+template <typename T>
+static hipError_t launch_outer_t(const void* params, unsigned gy, hipStream_t s) {
+    const ColParams<T>& p = *static_cast<const ColParams<T>*>(params);
+    OuterKey k;
+    if (!select_outer<RL_CFG_L>(sizeof(T) == 4, Special<T>::outer_ny, p.mode, p.ny, p.pitch, p.psf_hat_re != nullptr, k)) return hipErrorInvalidValue;
+    const bool found = for_each_outer<RL_CFG_L, T, Special<T>>([&](auto v) {
+        using V = decltype(v);
+        if (!(V::key() == k)) return false;
+        rl_launch(k_colconv_outer<RL_CFG_L, V::C, V::REALP, V::MODE, T, V::NYC>, dim3((unsigned)((p.kx + V::C - 1) / V::C), gy), dim3(64 * V::C), outer_lds_bytes<OuterCol<RL_CFG_L>, T, V::MODE>(), s, p);
+        return true;
+    });
+    return found ? hipGetLastError() : hipErrorInvalidValue;
+}
+template <int Q, typename T>
+static hipError_t launch_row_t(int mode, const void* params, unsigned gx, unsigned gy, hipStream_t s) {
+    const RowParams<T>& p = *static_cast<const RowParams<T>*>(params);
+    RowKey k;
+    if (!select_rowpass(Special<T>::row_nx, mode, p.nx, p.V, p.sub_one != 0, k)) return hipErrorInvalidValue;
+    const bool found = for_each_rowpass<RL_CFG_L, Special<T>>([&](auto v) {
+        using V = decltype(v);
+        if (!(V::key() == k)) return false;
+        rl_launch(k_rowpass<RL_CFG_L, Q, V::MODE, V::ONEV, T, V::PRESUM, V::NXC, V::SUBC>, dim3(gx, gy), dim3(Cfg::T * Q), lds_bytes<Q, T>(), s, p);
+        return true;
+    });
+    return found ? hipGetLastError() : hipErrorInvalidValue;
+}
+template <int Q, typename T>
+static hipError_t launch_row_pair_t(int mode, const void* params, unsigned gy, hipStream_t s) {
+    const RowParams<T>& p = *static_cast<const RowParams<T>*>(params);
+    PairKey k;
+    if (!select_rowpair(Special<T>::pair_nx, mode, p.nx, p.V, p.sub_one != 0, k)) return hipErrorInvalidValue;
+    const bool found = for_each_rowpair<RL_CFG_L, Special<T>>([&](auto v) {
+        using V = decltype(v);
+        if (!(V::key() == k)) return false;
+        rl_launch(k_rowpair<RL_CFG_L, Q, V::MODE, T, V::NXC, V::SUBC>, dim3((unsigned)((p.ny + Q - 1) / Q), gy), dim3(Cfg::T * Q), lds_bytes<Q, T>(), s, p);
+        return true;
+    });
+    return found ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+// float64 column passes of the outer lengths run the outer-decimation body too (per image; multi-view plans launch it per view)
+static hipError_t launch_col(int dtype, const void* params, unsigned gx, unsigned gy, hipStream_t s) {
+    if (dtype == DT_F32) return kOuterCol<RL_CFG_L, float> ? launch_outer_t<float>(params, gy, s) : launch_col_t<kC32, float>(params, gx, gy, s);
+    return kOuterCol<RL_CFG_L, double> ? launch_outer_t<double>(params, gy, s) : launch_col_t<kC64, double>(params, gx, gy, s);
+}
+static hipError_t launch_row(int dtype, int mode, const void* params, unsigned gx, unsigned gy, hipStream_t s) {
+    return dtype == DT_F32 ? launch_row_t<kQ32, float>(mode, params, gx, gy, s)
+                           : launch_row_t<kQ64, double>(mode, params, gx, gy, s);
+}
 static hipError_t launch_row_pair(int dtype, int mode, const void* params, unsigned gy, hipStream_t s) {
     return dtype == DT_F32 ? launch_row_pair_t<kPairQ32, float>(mode, params, gy, s)
                            : launch_row_pair_t<kQ64, double>(mode, params, gy, s);
 }
 
-template <int Q, typename T>
-static hipError_t prepare_rows() {
-    hipError_t e;
-    const size_t b = lds_bytes<Q, T>();
-    if ((e = allow_lds(k_rowpass<RL_CFG_L, Q, ROW_FWD, false, T>, b)) != hipSuccess) return e;
-    if ((e = allow_lds(k_rowpass<RL_CFG_L, Q, ROW_INV, false, T>, b)) != hipSuccess) return e;
-    if ((e = allow_lds(k_rowpass<RL_CFG_L, Q, ROW_RATIO, false, T>, b)) != hipSuccess) return e;
-    if ((e = allow_lds(k_rowpass<RL_CFG_L, Q, ROW_UPDATE, false, T>, b)) != hipSuccess) return e;
-    if ((e = allow_lds(k_rowpass<RL_CFG_L, Q, ROW_UPDATE, true, T>, b)) != hipSuccess) return e;
-    if ((e = allow_lds(k_rowpass<RL_CFG_L, Q, ROW_UPDATE, true, T, true>, b)) != hipSuccess) return e;   // PRESUM (launch_row_m)
-    if ((e = allow_lds(k_rowpass<RL_CFG_L, Q, ROW_ADJ, false, T>, b)) != hipSuccess) return e;
-    if ((e = allow_lds(k_rowpass<RL_CFG_L, Q, ROW_ADJ, true, T>, b)) != hipSuccess) return e;
-    if constexpr (kColN512<T>) {
-        if ((e = allow_lds(k_rowpass<RL_CFG_L, Q, ROW_RATIO, false, T, false, 512, 1>, b)) != hipSuccess) return e;
-        if ((e = allow_lds(k_rowpass<RL_CFG_L, Q, ROW_UPDATE, true, T, false, 512, 1>, b)) != hipSuccess) return e;
-    }
-    if constexpr (kPairRows) {
-        constexpr int QP = sizeof(T) == 4 ? kPairQ32 : Q;
-        const size_t bp = lds_bytes<QP, T>();
-        if ((e = allow_lds(k_rowpair<RL_CFG_L, QP, ROW_FWD, T>, bp)) != hipSuccess) return e;
-        if ((e = allow_lds(k_rowpair<RL_CFG_L, QP, ROW_RATIO, T>, bp)) != hipSuccess) return e;
-        if ((e = allow_lds(k_rowpair<RL_CFG_L, QP, ROW_UPDATE, T>, bp)) != hipSuccess) return e;
-        if constexpr (kColN512<T>) {
-            if ((e = allow_lds(k_rowpair<RL_CFG_L, QP, ROW_RATIO, T, 512, 1>, bp)) != hipSuccess) return e;
-            if ((e = allow_lds(k_rowpair<RL_CFG_L, QP, ROW_UPDATE, T, 512, 1>, bp)) != hipSuccess) return e;
-        }
-        if constexpr (kRowN2048<T>) {
-            if ((e = allow_lds(k_rowpair<RL_CFG_L, QP, ROW_RATIO, T, 2048, 1>, bp)) != hipSuccess) return e;
-            if ((e = allow_lds(k_rowpair<RL_CFG_L, QP, ROW_UPDATE, T, 2048, 1>, bp)) != hipSuccess) return e;
-        }
-    }
-    return hipSuccess;
+// every variant that exists for this length and type may use its dynamic LDS: the walks the launchers take.  (Where the type's
+// column pass is the outer one, launch_col never takes k_colconv: its one workgroup-synchronous instantiation is still walked
+// here, as it always was prepared -- dropping that unreachable kernel is a change of the device code, left for its own commit.)
+template <int C, int Q, int QP, typename T>
+static hipError_t prepare_t() {
+    hipError_t e = hipSuccess;
+    auto failed = [&e](hipError_t r) { return (e = r) != hipSuccess; };
+    (void)(for_each_colconv<RL_CFG_L, Special<T>>([&](auto v) {
+        using V = decltype(v);
+        return failed(allow_lds(k_colconv<RL_CFG_L, C, V::MODE, T, V::REALP, V::NYC, V::CT>, col_lds_bytes<C, T>()));
+    }) || for_each_outer<RL_CFG_L, T, Special<T>>([&](auto v) {
+        using V = decltype(v);
+        static_assert(outer_lds_bytes<OuterCol<RL_CFG_L>, T, V::MODE>() <= 160 * 1024, "LDS of a CU");
+        return failed(allow_lds(k_colconv_outer<RL_CFG_L, V::C, V::REALP, V::MODE, T, V::NYC>, outer_lds_bytes<OuterCol<RL_CFG_L>, T, V::MODE>()));
+    }) || for_each_rowpass<RL_CFG_L, Special<T>>([&](auto v) {
+        using V = decltype(v);
+        return failed(allow_lds(k_rowpass<RL_CFG_L, Q, V::MODE, V::ONEV, T, V::PRESUM, V::NXC, V::SUBC>, lds_bytes<Q, T>()));
+    }) || for_each_rowpair<RL_CFG_L, Special<T>>([&](auto v) {
+        using V = decltype(v);
+        return failed(allow_lds(k_rowpair<RL_CFG_L, QP, V::MODE, T, V::NXC, V::SUBC>, lds_bytes<QP, T>()));
+    }));
+    return e;
 }
-
 static hipError_t prepare() {
-    hipError_t e;
-    if ((e = allow_lds(k_colconv<RL_CFG_L, kC32, COL_PER_IMAGE, float>, col_lds_bytes<kC32, float>())) != hipSuccess) return e;
-    if ((e = allow_lds(k_colconv<RL_CFG_L, kC64, COL_PER_IMAGE, double>, col_lds_bytes<kC64, double>())) != hipSuccess) return e;
-    if constexpr (kColN512<float>) {
-        if ((e = allow_lds(k_colconv<RL_CFG_L, kC32, COL_PER_IMAGE, float, true, 512>, col_lds_bytes<kC32, float>())) != hipSuccess) return e;
-        if ((e = allow_lds(k_colconv<RL_CFG_L, kC32, COL_PER_IMAGE, float, false, 512>, col_lds_bytes<kC32, float>())) != hipSuccess) return e;
-        if ((e = allow_lds(k_colconv<RL_CFG_L, kC32, COL_PER_IMAGE, float, true, 512, 1>, col_lds_bytes<kC32, float>())) != hipSuccess) return e;
-        if ((e = allow_lds(k_colconv<RL_CFG_L, kC32, COL_PER_IMAGE, float, false, 512, 1>, col_lds_bytes<kC32, float>())) != hipSuccess) return e;
-    }
-    if constexpr (WavePrivate<CCfg>::value) {
-        if ((e = allow_lds(k_colconv<RL_CFG_L, kC32, COL_PER_IMAGE, float, true>, col_lds_bytes<kC32, float>())) != hipSuccess) return e;
-        if ((e = allow_lds(k_colconv<RL_CFG_L, kC64, COL_PER_IMAGE, double, true>, col_lds_bytes<kC64, double>())) != hipSuccess) return e;
-    }
-    if constexpr (OuterCol<RL_CFG_L>::value) {
-        using OC = OuterCol<RL_CFG_L>;
-        constexpr size_t lds_whole = outer_whole_lds_bytes<OC>();
-        static_assert(lds_whole <= 160 * 1024, "LDS of a CU");
-        if ((e = allow_outer<RL_CFG_L, OC::CW, true, COL_PER_IMAGE, float>(lds_whole)) != hipSuccess) return e;
-        if ((e = allow_outer<RL_CFG_L, OC::CW, false, COL_PER_IMAGE, float>(lds_whole)) != hipSuccess) return e;
-        constexpr size_t lds_split = outer_split_lds_bytes<OC>();
-        if ((e = allow_outer<RL_CFG_L, OC::C, false, COL_SPLIT_FWD, float>(lds_split)) != hipSuccess) return e;
-        if ((e = allow_outer<RL_CFG_L, OC::C, true, COL_SPLIT_INV, float>(lds_split)) != hipSuccess) return e;
-        if ((e = allow_outer<RL_CFG_L, OC::C, false, COL_SPLIT_INV, float>(lds_split)) != hipSuccess) return e;
-        if ((e = allow_outer<RL_CFG_L, OC::C, true, COL_SPLIT_INV_SUM, float>(lds_split)) != hipSuccess) return e;
-        if ((e = allow_outer<RL_CFG_L, OC::C, false, COL_SPLIT_INV_SUM, float>(lds_split)) != hipSuccess) return e;
-        if constexpr (OC::value64) {
-            constexpr size_t lds64 = outer_whole_lds_bytes_f64<OC>();
-            static_assert(lds64 <= 160 * 1024, "LDS of a CU");
-            if ((e = allow_outer<RL_CFG_L, OC::C64, true, COL_PER_IMAGE, double>(lds64)) != hipSuccess) return e;
-            if ((e = allow_outer<RL_CFG_L, OC::C64, false, COL_PER_IMAGE, double>(lds64)) != hipSuccess) return e;
-        }
-    }
-    if ((e = prepare_rows<kQ32, float>()) != hipSuccess) return e;
-    if ((e = prepare_rows<kQ64, double>()) != hipSuccess) return e;
-    return hipSuccess;
+    const hipError_t e = prepare_t<kC32, kQ32, kPairQ32, float>();
+    return e != hipSuccess ? e : prepare_t<kC64, kQ64, kQ64, double>();
 }
 
 // (the length is a template parameter: this file is compiled once per length, and equally named entities of
@@ -501,7 +328,7 @@ const KernelTable* RL_TABLE_FN() {
                                   PassTw<Cfg, false, 0>::TOTAL, fill_pass_twiddles<Cfg>,
                                   {OuterTw<RL_CFG_L, OUTER>::count, OUTER64 ? OuterTw<RL_CFG_L, OUTER64>::count : PassTw<CCfg, false, 0>::TOTAL},
                                   {OuterTw<RL_CFG_L, OUTER>::fill, OUTER64 ? OuterTw<RL_CFG_L, OUTER64>::fill : fill_pass_twiddles<CCfg>}, launch_col, launch_row, prepare,
-                                  kPairRows ? launch_row_pair : nullptr, OuterTw<RL_CFG_L, OUTER>::split_tile};
+                                  kPairRows<RL_CFG_L> ? launch_row_pair : nullptr, OuterTw<RL_CFG_L, OUTER>::split_tile};
     return &t;
 }
 

@@ -28,5 +28,12 @@ template <class OC>
 constexpr size_t outer_split_lds_bytes() {
     return ((size_t)OC::C * LdsSlots<typename OC::Core>::value + outer_tw_lds_elems<OC>(OC::TWLDS_SPLIT)) * sizeof(cx<float>);
 }
+// ... of the kernel of one type and mode (float64: the whole pass only)
+template <class OC, typename T, int MODE>
+constexpr size_t outer_lds_bytes() {
+    if constexpr (sizeof(T) != 4) return outer_whole_lds_bytes_f64<OC>();
+    else if constexpr (MODE == COL_PER_IMAGE) return outer_whole_lds_bytes<OC>();
+    else return outer_split_lds_bytes<OC>();
+}
 
 }  // namespace rl

@@ -24,8 +24,14 @@ static std::vector<cx<T>> twiddles(bool column = false) {   // rows: CfgFor<L>::
 }
 
 // emu_set_special(1): the bodies specialised for a compile-time image size (round 4: NYC / NXC / SUBC / CT template arguments,
-// on the device instantiated for the 512 x 512 frames at L = 576) are run in their L = 256, 192-row / 192-pixel instantiation
+// on the device instantiated for the 512 x 512 frames at L = 576) are run in their L = 256 instantiation for 192 pixels and
+// 192 rows -- or NY = 128 rows (a multiple of 128 rows: the 16-byte tile I/O).  The variants come from the lists and the
+// selectors of csrc/kernel_variants.hpp, as on the device, with these sizes in the place of DeviceSpecial's.
 static int g_special = 0;
+template <int L, int NY = 192>
+struct EmuSpecial {
+    static constexpr int col_ny = L == 256 ? NY : 0, row_nx = L == 256 ? 192 : 0, pair_nx = row_nx, outer_ny = 0;
+};
 
 template <int L, typename T>
 static int col_t(const T* in, T* out, const T* psf_hat, int ny, int kx, int pitch, int V, int frames,
@@ -42,57 +48,18 @@ static int col_t(const T* in, T* out, const T* psf_hat, int ny, int kx, int pitc
     p.ny = ny; p.kx = kx; p.pitch = pitch; p.V = V; p.in_sb = in_sb; p.in_sv = in_sv;
     p.mode = mode;
     const int gy = (mode == COL_PER_IMAGE) ? frames * V : frames;   // as rlsted.cpp col_t()
-    if (mode != COL_PER_IMAGE && !WavePrivate<Cfg>::value) return -3;
     p.images = gy; p.order = 1;
+    p.residual = 1;   // (the compile-time sizes run with the compact twiddles)
+    ColKey k;
+    if (!select_colconv(WavePrivate<Cfg>::value, !g_special ? 0 : ny == 128 ? 128 : EmuSpecial<L>::col_ny, mode, ny, V, pitch % C == 0, false, true, k)) return -3;
     run_grid((kx + C - 1) / C, gy, Cfg::T * C, (size_t)C * LdsSlots<Cfg>::value * sizeof(cx<T>),
              [&](int tid, int bx, int by, unsigned char* lds, EmuSync& s) {
-                 if constexpr (L == 256) {
-                     if (g_special && ny == 192 && V == 1 && mode == COL_PER_IMAGE && pitch % C == 0) {
-                         colconv_wave_body<Cfg, C, COL_PER_IMAGE, T, false, 192, 1>(p, tid, bx, by, reinterpret_cast<cx<T>*>(lds), s);
-                         return;
-                     }
-                     if (g_special && ny == 128 && V == 1 && mode == COL_PER_IMAGE && pitch % C == 0) {   // (a multiple of 128 rows: the 16-byte tile I/O)
-                         colconv_wave_body<Cfg, C, COL_PER_IMAGE, T, false, 128, 1>(p, tid, bx, by, reinterpret_cast<cx<T>*>(lds), s);
-                         return;
-                     }
-                 }
-                 if constexpr (WavePrivate<Cfg>::value)
-                     switch (mode) {   // same dispatch as launch_col_t in fft_kernels.hip
-                         case COL_H_MULTI: colconv_wave_body<Cfg, C, COL_H_MULTI, T>(p, tid, bx, by, reinterpret_cast<cx<T>*>(lds), s); break;
-                         case COL_HT_SUM: colconv_wave_body<Cfg, C, COL_HT_SUM, T>(p, tid, bx, by, reinterpret_cast<cx<T>*>(lds), s); break;
-                         default: colconv_wave_body<Cfg, C, COL_PER_IMAGE, T>(p, tid, bx, by, reinterpret_cast<cx<T>*>(lds), s);
-                     }
-                 else
-                     colconv_body<Cfg, C, T>(p, tid, bx, by, reinterpret_cast<cx<T>*>(lds), s);
-             });
-    return 0;
-}
-
-template <int L, int MODE, typename T>
-static int row_m(const RowParams<T>& p, int gy) {
-    using CF = CfgFor<L>;
-    using Cfg = typename CF::Cfg;
-    constexpr int Q = sizeof(T) == 4 ? CF::Q32 : CF::Q64;
-    const int pairs = (p.ny + 1) / 2;
-    run_grid((pairs + Q - 1) / Q, gy, Cfg::T * Q, (size_t)Q * LdsSlots<Cfg>::value * sizeof(cx<T>),
-             [&](int tid, int bx, int by, unsigned char* lds, EmuSync& s) {
-                 constexpr bool MULTI = (MODE == ROW_UPDATE || MODE == ROW_ADJ);
-                 if constexpr (WavePrivate<Cfg>::value && (MODE == ROW_RATIO || MODE == ROW_UPDATE)) {
-                     if (MODE == ROW_RATIO || p.V == 1) {   // same dispatch as k_rowpass (LEAN) in fft_kernels.hip
-                         rowlean_body<Cfg, Q, MODE, T>(p, tid, bx, by, reinterpret_cast<cx<T>*>(lds), s);
-                         return;
-                     }
-                 }
-                 if constexpr (MODE == ROW_UPDATE) {
-                     if (p.V > 1 && p.sub_one) {   // same dispatch as launch_row_m in fft_kernels.hip
-                         rowpass_body<Cfg, Q, MODE, true, T, true>(p, tid, bx, by, reinterpret_cast<cx<T>*>(lds), s);
-                         return;
-                     }
-                 }
-                 if (MULTI && p.V == 1)
-                     rowpass_body<Cfg, Q, MODE, MULTI, T>(p, tid, bx, by, reinterpret_cast<cx<T>*>(lds), s);
-                 else
-                     rowpass_body<Cfg, Q, MODE, false, T>(p, tid, bx, by, reinterpret_cast<cx<T>*>(lds), s);
+                 auto run = [&](auto v) {
+                     if (!(v.key() == k)) return false;
+                     colconv_variant<L, C>(v, p, tid, bx, by, lds, s);
+                     return true;
+                 };
+                 for_each_colconv<L, EmuSpecial<L>>(run) || for_each_colconv<L, EmuSpecial<L, 128>>(run);
              });
     return 0;
 }
@@ -104,6 +71,9 @@ static int g_sub_one = 0;
 template <int L, typename T>
 static int row_t(int mode, const T* spec_in, T* spec_out, const T* src, T* dst, const T* norm, const T* scale,
                  int ny, int nx, int pitch, int V, int gy) {
+    using CF = CfgFor<L>;
+    using Cfg = typename CF::Cfg;
+    constexpr int Q = sizeof(T) == 4 ? CF::Q32 : CF::Q64;
     auto tw = twiddles<L, T>();
     RowParams<T> p;
     p.sub_one = g_sub_one;
@@ -111,14 +81,17 @@ static int row_t(int mode, const T* spec_in, T* spec_out, const T* src, T* dst, 
     p.spec_out = reinterpret_cast<cx<T>*>(spec_out);
     p.src = src; p.dst = dst; p.norm = norm; p.scale = scale; p.tw = tw.data();
     p.ny = ny; p.nx = nx; p.pitch = pitch; p.V = V;
-    switch (mode) {
-        case ROW_FWD: return row_m<L, ROW_FWD, T>(p, gy);
-        case ROW_INV: return row_m<L, ROW_INV, T>(p, gy);
-        case ROW_RATIO: return row_m<L, ROW_RATIO, T>(p, gy);
-        case ROW_UPDATE: return row_m<L, ROW_UPDATE, T>(p, gy);
-        case ROW_ADJ: return row_m<L, ROW_ADJ, T>(p, gy);
-    }
-    return -1;
+    RowKey k;
+    if (!select_rowpass(g_special ? EmuSpecial<L>::row_nx : 0, mode, nx, V, p.sub_one != 0, k)) return -1;
+    run_grid(((ny + 1) / 2 + Q - 1) / Q, gy, Cfg::T * Q, (size_t)Q * LdsSlots<Cfg>::value * sizeof(cx<T>),
+             [&](int tid, int bx, int by, unsigned char* lds, EmuSync& s) {
+                 for_each_rowpass<L, EmuSpecial<L>>([&](auto v) {
+                     if (!(v.key() == k)) return false;
+                     rowpass_variant<L, Q>(v, p, tid, bx, by, lds, s);
+                     return true;
+                 });
+             });
+    return 0;
 }
 
 #define DISPATCH_L(L, call)                         \
@@ -313,23 +286,17 @@ static int row_pair_t(int mode, const T* spec_in, T* spec_out, const T* src, T* 
         p.src = src; p.dst = dst; p.norm = norm; p.scale = nullptr; p.tw = tw.data();
         p.ny = ny; p.nx = nx; p.pitch = L; p.V = 1; p.frames = frames; p.in_mod = in_mod;
         p.sub_one = g_sub_one;
-        auto run = [&](auto mode_tag) {
-            constexpr int MODE = decltype(mode_tag)::value;
-            run_grid((ny + Q - 1) / Q, (frames + 1) / 2, 64 * Q, (size_t)Q * LdsSlots<Cfg>::value * sizeof(cx<T>),
-                     [&](int tid, int bx, int by, unsigned char* lds, EmuSync& s) {
-                         if constexpr (L == 256 && MODE != ROW_FWD) {
-                             if (g_special && nx == 192 && p.sub_one) {
-                                 rowpair_body<Cfg, Q, MODE, T, 192, 1>(p, tid, bx, by, reinterpret_cast<cx<T>*>(lds), s);
-                                 return;
-                             }
-                         }
-                         rowpair_body<Cfg, Q, MODE, T>(p, tid, bx, by, reinterpret_cast<cx<T>*>(lds), s);
+        PairKey k;
+        if (!select_rowpair(g_special ? EmuSpecial<L>::pair_nx : 0, mode, nx, p.V, p.sub_one != 0, k)) return -1;
+        run_grid((ny + Q - 1) / Q, (frames + 1) / 2, 64 * Q, (size_t)Q * LdsSlots<Cfg>::value * sizeof(cx<T>),
+                 [&](int tid, int bx, int by, unsigned char* lds, EmuSync& s) {
+                     for_each_rowpair<L, EmuSpecial<L>>([&](auto v) {
+                         using V = decltype(v);
+                         if (!(v.key() == k)) return false;
+                         rowpair_body<Cfg, Q, V::MODE, T, V::NXC, V::SUBC>(p, tid, bx, by, reinterpret_cast<cx<T>*>(lds), s);
+                         return true;
                      });
-        };
-        if (mode == ROW_FWD) run(std::integral_constant<int, ROW_FWD>{});
-        else if (mode == ROW_RATIO) run(std::integral_constant<int, ROW_RATIO>{});
-        else if (mode == ROW_UPDATE) run(std::integral_constant<int, ROW_UPDATE>{});
-        else return -1;
+                 });
         return 0;
     } else {
         return -3;
@@ -345,6 +312,15 @@ int emu_row_pair_f32(int L, int mode, const float* spec_in, float* spec_out, con
     DISPATCH_L(L, (row_pair_t<LL, float>(mode, spec_in, spec_out, src, dst, norm, ny, nx, frames, in_mod)))
 }
 void emu_set_park(int on) { g_park = on; }
+// every variant of the lists this library can run, one per line (the format of long_emu.cpp emu_long_table; the 128-row
+// column variants are the 192-row rows at another size and are not repeated)
+int emu_table(char* buf, int cap) {
+    std::string s;
+#define ROWS(LL) list_variants<LL, float, EmuSpecial<LL>>(s, true, true); list_variants<LL, double, EmuSpecial<LL>>(s, true, true);
+    ROWS(64) ROWS(192) ROWS(256) ROWS(576)
+#undef ROWS
+    return copy_out(s, buf, cap);
+}
 int emu_col_outer_f64(int Li, int M, const double* in, double* out, const double* psf_hat, int real_psf, int ny, int kx,
                       int pitch, int V, int frames, int in_sb, int in_sv) {
     using C256 = CfgFor<256>::Cfg;

@@ -1,105 +1,46 @@
 // Host emulator of the ROW kernels of the long, workgroup-synchronous lengths (L = 1152, 2304, 4608): rowpass_body in every
-// mode and rowpair_body on the `Q == 1` branch of k_rowpair, instantiated and dispatched as fft_kernels.hip does it
-// (launch_row_m, launch_row_pair_t).  A translation unit of its own -- tests/test_long_rows_cpu.py builds it into
-// liblong_emu.so -- so that libemu.so keeps its build time.  TEST INFRASTRUCTURE ONLY.
-//
-// The instantiations are listed ONCE, in the LONG_ROWPASS / LONG_ROWPAIR tables below: the dispatch runs through them and
-// emu_long_table() prints them, so the test that compares the list with what fft_kernels.hip can launch sees exactly what
-// can run here.
-#include <cstdio>
-#include <string>
-
+// mode and rowpair_body on the `Q == 1` branch of k_rowpair, chosen by the selectors and instantiated from the lists of
+// csrc/kernel_variants.hpp, as fft_kernels.hip does it -- with the device's compile-time sizes (DeviceSpecial).  A translation
+// unit of its own -- tests/test_long_rows_cpu.py builds it into liblong_emu.so -- so that libemu.so keeps its build time.
+// It also lists the DEVICE's variants of any length and runs the device's selectors (tests/test_kernel_variants.py).
+// TEST INFRASTRUCTURE ONLY.
 #include "emu_common.hpp"
-
-//            MODE        ONEV   PRESUM
-#define LONG_ROWPASS(X)           \
-    X(ROW_FWD,    false, false)   \
-    X(ROW_INV,    false, false)   \
-    X(ROW_RATIO,  false, false)   \
-    X(ROW_UPDATE, false, false)   \
-    X(ROW_UPDATE, true,  false)   \
-    X(ROW_UPDATE, true,  true)    \
-    X(ROW_ADJ,    false, false)   \
-    X(ROW_ADJ,    true,  false)
-//            MODE        NXC   SUBC     (NXC > 0: float, L = 2304 only -- fft_kernels.hip kRowN2048)
-#define LONG_ROWPAIR(X)        \
-    X(ROW_FWD,    0,    -1)    \
-    X(ROW_RATIO,  0,    -1)    \
-    X(ROW_UPDATE, 0,    -1)    \
-    X(ROW_RATIO,  2048, 1)     \
-    X(ROW_UPDATE, 2048, 1)
-
-template <int L, typename T>
-constexpr bool pair_inst_exists(int nxc) {
-    return nxc == 0 || (L == 2304 && sizeof(T) == 4);
-}
 
 template <int L, typename T>
 struct LongRow {
     using CF = CfgFor<L>;
     using Cfg = typename CF::Cfg;
+    using Special = DeviceSpecial<L, T>;
     static constexpr int Q = sizeof(T) == 4 ? CF::Q32 : CF::Q64;
-    // fft_kernels.hip: kPairQ32 = WavePrivate ? RL_PAIR_Q32 : kQ32; pairs exist where WavePrivate || (Q32 == 1 && Q64 == 1)
-    static constexpr int QP = Q;
-    static_assert(!WavePrivate<Cfg>::value, "the wave-private lengths are emu.cpp's");
-    static constexpr bool kPairRows = CF::Q32 == 1 && CF::Q64 == 1;
+    static constexpr int QP = Q;   // fft_kernels.hip: kPairQ32 = WavePrivate ? RL_PAIR_Q32 : kQ32
+    static_assert(!WavePrivate<Cfg>::value && kPairRows<L> && QP == 1, "the wave-private lengths are emu.cpp's; k_rowpair: WavePrivate || Q == 1");
     static constexpr size_t lds_bytes(int q) { return (size_t)q * LdsSlots<Cfg>::value * sizeof(cx<T>); }
 
-    template <int MODE, bool ONEV, bool PRESUM>
-    static int rowpass(const RowParams<T>& p, int gy) {
-        const int pairs = (p.ny + 1) / 2;
-        run_grid((pairs + Q - 1) / Q, gy, Cfg::T * Q, lds_bytes(Q), [&](int tid, int bx, int by, unsigned char* lds, EmuSync& s) {
-            rowpass_body<Cfg, Q, MODE, ONEV, T, PRESUM>(p, tid, bx, by, reinterpret_cast<cx<T>*>(lds), s);
-        });
-        return 0;
-    }
-    static int rowpass_inst(int mode, bool onev, bool presum, const RowParams<T>& p, int gy) {
-#define X(M, O, P) if (mode == M && onev == O && presum == P) return rowpass<M, O, P>(p, gy);
-        LONG_ROWPASS(X)
-#undef X
-        return -4;   // launch_row_m would launch an instantiation this emulator does not have
-    }
-    // the choice of launch_row_m
     static int row(int mode, const RowParams<T>& p, int gy) {
-        const bool multi = mode == ROW_UPDATE || mode == ROW_ADJ;
-        if (mode == ROW_UPDATE && p.V > 1 && p.sub_one) return rowpass_inst(mode, true, true, p, gy);
-        return rowpass_inst(mode, multi && p.V == 1, false, p, gy);
-    }
-
-    template <int MODE, int NXC, int SUBC>
-    static int rowpair(const RowParams<T>& p, int gy) {
-        if constexpr (kPairRows && pair_inst_exists<L, T>(NXC)) {
-            static_assert(QP == 1, "k_rowpair: WavePrivate || Q == 1");
-            run_grid((p.ny + QP - 1) / QP, gy, Cfg::T * QP, lds_bytes(QP), [&](int tid, int bx, int by, unsigned char* lds, EmuSync& s) {
-                rowpair_body<Cfg, QP, MODE, T, NXC, SUBC>(p, tid, bx, by, reinterpret_cast<cx<T>*>(lds), s);
+        RowKey k;
+        if (!select_rowpass(Special::row_nx, mode, p.nx, p.V, p.sub_one != 0, k)) return -1;
+        const bool found = for_each_rowpass<L, Special>([&](auto v) {
+            if (!(v.key() == k)) return false;
+            run_grid(((p.ny + 1) / 2 + Q - 1) / Q, gy, Cfg::T * Q, lds_bytes(Q), [&](int tid, int bx, int by, unsigned char* lds, EmuSync& s) {
+                rowpass_variant<L, Q>(v, p, tid, bx, by, lds, s);
             });
-            return 0;
-        } else {
-            return -3;
-        }
+            return true;
+        });
+        return found ? 0 : -4;   // the selector names a row the list does not have
     }
-    static int rowpair_inst(int mode, int nxc, int subc, const RowParams<T>& p, int gy) {
-#define X(M, N, S) if (mode == M && nxc == N && subc == S) return rowpair<M, N, S>(p, gy);
-        LONG_ROWPAIR(X)
-#undef X
-        return -4;
-    }
-    // the choice of launch_row_pair_t; special == 0: the run-time-size bodies whatever the size (what the others are compared with)
+    // special == 0: the run-time-size bodies whatever the size (what the others are compared with)
     static int pair(int mode, const RowParams<T>& p, int gy, int special) {
-        if (special && pair_inst_exists<L, T>(2048) && p.nx == 2048 && p.V == 1 && p.sub_one != 0 && mode != ROW_FWD)
-            return rowpair_inst(mode, 2048, 1, p, gy);
-        return rowpair_inst(mode, 0, -1, p, gy);
-    }
-
-    static void table(std::string& out) {
-        char b[160];
-        const char* t = sizeof(T) == 4 ? "f32" : "f64";
-#define X(M, O, P) std::snprintf(b, sizeof b, "k_rowpass L=%d T=%s MODE=%d ONEV=%d PRESUM=%d NXC=0 SUBC=-1\n", L, t, (int)M, (int)O, (int)P); out += b;
-        LONG_ROWPASS(X)
-#undef X
-#define X(M, N, S) if (kPairRows && pair_inst_exists<L, T>(N)) { std::snprintf(b, sizeof b, "k_rowpair L=%d T=%s MODE=%d NXC=%d SUBC=%d\n", L, t, (int)M, (int)N, (int)S); out += b; }
-        LONG_ROWPAIR(X)
-#undef X
+        PairKey k;
+        if (!select_rowpair(special ? Special::pair_nx : 0, mode, p.nx, p.V, p.sub_one != 0, k)) return -1;
+        const bool found = for_each_rowpair<L, Special>([&](auto v) {
+            using V = decltype(v);
+            if (!(v.key() == k)) return false;
+            run_grid((p.ny + QP - 1) / QP, gy, Cfg::T * QP, lds_bytes(QP), [&](int tid, int bx, int by, unsigned char* lds, EmuSync& s) {
+                rowpair_body<Cfg, QP, V::MODE, T, V::NXC, V::SUBC>(p, tid, bx, by, reinterpret_cast<cx<T>*>(lds), s);
+            });
+            return true;
+        });
+        return found ? 0 : -4;
     }
 };
 
@@ -172,11 +113,62 @@ int emu_long_q(int L, int esize, int pair) {
 // every instantiation this library can run, one per line; returns the length of the text (truncated to cap - 1)
 int emu_long_table(char* buf, int cap) {
     std::string s;
-    LongRow<1152, float>::table(s); LongRow<1152, double>::table(s);
-    LongRow<2304, float>::table(s); LongRow<2304, double>::table(s);
-    LongRow<4608, float>::table(s); LongRow<4608, double>::table(s);
-    std::snprintf(buf, (size_t)cap, "%s", s.c_str());
-    return (int)s.size();
+    list_variants<1152, float, DeviceSpecial<1152, float>>(s, false, true); list_variants<1152, double, DeviceSpecial<1152, double>>(s, false, true);
+    list_variants<2304, float, DeviceSpecial<2304, float>>(s, false, true); list_variants<2304, double, DeviceSpecial<2304, double>>(s, false, true);
+    list_variants<4608, float, DeviceSpecial<4608, float>>(s, false, true); list_variants<4608, double, DeviceSpecial<4608, double>>(s, false, true);
+    return copy_out(s, buf, cap);
+}
+
+}  // extern "C"
+
+// ---- the device's side of kernel_variants.hpp, for any of its seven lengths: no body runs here
+#define DISPATCH_ANY(L, call)                                                                                        \
+    switch (L) {                                                                                                     \
+        case 64: { constexpr int LL = 64; return call; }     case 192: { constexpr int LL = 192; return call; }      \
+        case 256: { constexpr int LL = 256; return call; }   case 576: { constexpr int LL = 576; return call; }      \
+        case 1152: { constexpr int LL = 1152; return call; } case 2304: { constexpr int LL = 2304; return call; }    \
+        case 4608: { constexpr int LL = 4608; return call; } default: return -2;                                     \
+    }
+template <int L, typename T>
+static int device_table(char* buf, int cap) {
+    std::string s;
+    list_variants<L, T, DeviceSpecial<L, T>>(s, true, true);
+    return copy_out(s, buf, cap);
+}
+// family 0: the column pass (launch_col), 1: k_rowpass, 2: k_rowpair.  n: the image's rows (columns) or pixels per row (rows);
+// flag: ColParams::residual or RowParams::sub_one.  Writes the line of the row the device's launcher would take; -1: none.
+template <int L, typename T>
+static int device_select(int family, int mode, int n, int V, int pitch, int realp, int flag, char* buf, int cap) {
+    using S = DeviceSpecial<L, T>;
+    using CF = CfgFor<L>;
+    std::string s;
+    if (family == 0 && kOuterCol<L, T>) {
+        OuterKey k;
+        if (!select_outer<L>(sizeof(T) == 4, S::outer_ny, mode, n, pitch, realp != 0, k)) return -1;
+        s = line_of<L, T>(k);
+    } else if (family == 0) {
+        ColKey k;
+        constexpr int C = sizeof(T) == 4 ? CF::C32 : CF::C64;
+        if (!select_colconv(WavePrivate<typename ColCfgFor<L>::type>::value, S::col_ny, mode, n, V, pitch % C == 0, realp != 0, flag != 0, k)) return -1;
+        s = line_of<L, T>(k);
+    } else if (family == 1) {
+        RowKey k;
+        if (!select_rowpass(S::row_nx, mode, n, V, flag != 0, k)) return -1;
+        s = line_of<L, T>(k);
+    } else {
+        PairKey k;
+        if (!kPairRows<L> || !select_rowpair(S::pair_nx, mode, n, V, flag != 0, k)) return -1;
+        s = line_of<L, T>(k);
+    }
+    return copy_out(s, buf, cap);
+}
+extern "C" {
+int emu_device_table(int L, int esize, char* buf, int cap) {
+    DISPATCH_ANY(L, (esize == 4 ? device_table<LL, float>(buf, cap) : device_table<LL, double>(buf, cap)))
+}
+int emu_device_select(int L, int esize, int family, int mode, int n, int V, int pitch, int realp, int flag, char* buf, int cap) {
+    DISPATCH_ANY(L, (esize == 4 ? device_select<LL, float>(family, mode, n, V, pitch, realp, flag, buf, cap)
+                                : device_select<LL, double>(family, mode, n, V, pitch, realp, flag, buf, cap)))
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@ import pytest
 
 import fft_reference as fr
 from conftest import ROOT, fuzz_seeds
+from test_emulated_kernels import emu  # noqa: F401  (the short lengths' emulator, a fixture)
 from fft_reference import CLD, LD, ROW_ADJ, ROW_FWD, ROW_INV, ROW_RATIO, ROW_UPDATE
 
 EMU_DIR = os.path.join(ROOT, 'tests', 'emu')
@@ -42,7 +43,7 @@ def _build(names):
     """tests/emu/lib<name>.so for each name, rebuilt (side by side) when a source is newer; RLSTED_<NAME>_LIB names a prebuilt
     (sanitized) one instead."""
     out, procs = {}, []
-    hdrs = [os.path.join(CSRC, f) for f in ('conv_kernels.hpp', 'fft_core.hpp', 'fft_configs.hpp', 'outer_lds.hpp')] + \
+    hdrs = [os.path.join(CSRC, f) for f in ('conv_kernels.hpp', 'fft_core.hpp', 'fft_configs.hpp', 'outer_lds.hpp', 'kernel_variants.hpp')] + \
         [os.path.join(EMU_DIR, 'emu_common.hpp')]
     for name in names:
         override = os.environ.get('RLSTED_%s_LIB' % name.upper())
@@ -516,7 +517,7 @@ def test_pair_ratio_with_views_and_shared_first_spectra(lib, L, dtype):
 
 
 def test_pair_bodies_with_the_row_length_at_compile_time(lib):
-    """rowpair_body<..., NXC = 2048, SUBC = 1> on the 2304 geometry (the device's kRowN2048 kernels, float): bit for bit the
+    """rowpair_body<..., NXC = 2048, SUBC = 1> on the 2304 geometry (the device's 2048-pixel frame-pair kernels, DeviceSpecial::pair_nx, float): bit for bit the
     run-time-size body's result, and the reference's within the bound."""
     L, ny, nx, frames = 2304, 3, 2048, 3
     for mode in (ROW_RATIO, ROW_UPDATE):
@@ -804,7 +805,7 @@ def _outer_check(got, ref, scale, G, key):
 def test_outer_whole_pass_as_the_device_runs_it(libs, L, ny, kx, real_psf, dtype):
     """The whole outer pass exactly as launch_col launches it: f32 on CW columns with PARK parked values and TWLDS twiddle
     copies (2304: 16-column tiles, both tables in LDS), float64 on C64 columns with PARK64 parked values, the kernel with the row
-    count at compile time where launch_outer picks it (ny = 512 M, bit for bit the generic kernel's result) -- at the launcher's
+    count at compile time where select_outer picks it (ny = 512 M, bit for bit the generic kernel's result) -- at the launcher's
     LDS byte count.  Against numpy's float64 FFT: IFFT_y(FFT_y(x zero padded) * psf_hat), rows < ny, per element within
     _outer_growth * sum |column| * sum |multiplier|.  Frame 0 is dense and view 0's multiplier Gaussian noise (every row and
     every bin carries weight; the bound is 0.2-1 % of a typical output there in float); frame 1 has one lit row per column and
@@ -898,112 +899,85 @@ def test_outer_split_pass_as_the_device_runs_it(libs, L, ny, kx, real_psf, sum_v
 
 
 # ------------------------------------------------------------------------------------------------ guard against drift
-def _cxx_to_py(expr):
-    expr = re.sub(r'WavePrivate<\w+>::value', 'WP', expr)
-    expr = re.sub(r'(k\w+)<T>', r'\1', expr)
-    expr = expr.replace('sizeof(T)', 'ESIZE').replace('&&', ' and ').replace('||', ' or ')
-    expr = re.sub(r'!(?!=)', ' not ', expr)
-    return expr.replace('true', 'True').replace('false', 'False')
+SHORT_LENGTHS = (64, 192, 256, 576)
+WALK_OF = {'k_colconv': 'for_each_colconv<', 'k_colconv_outer': 'for_each_outer<', 'k_rowpass': 'for_each_rowpass<', 'k_rowpair': 'for_each_rowpair<'}
 
 
-def launchable_row_kernels(L, esize, site='rl_launch'):
-    """Every k_rowpass / k_rowpair instantiation fft_kernels.hip can launch at length L and element size esize, from its
-    rl_launch( sites: template arguments evaluated under the `if constexpr` conditions that enclose each site.
-    site = 'allow_lds': the instantiations prepare() raises the dynamic LDS limit of, from the allow_lds( sites."""
-    text = open(os.path.join(CSRC, 'fft_kernels.hip')).read()
-    text = re.sub(r'//[^\n]*', '', text)
-    env = dict(ROW_FWD=0, ROW_INV=1, ROW_RATIO=2, ROW_UPDATE=3, ROW_ADJ=4, RL_CFG_L=L, ESIZE=esize, WP=False, Q=1, QP=1, T='T',
-               RL_N512=int(re.search(r'#define RL_N512 (\d+)', text).group(1)), RL_CT_RESIDUAL=1)
-    for name in ('kColN512', 'kRowN2048'):
-        m = re.search(r'constexpr bool %s = ([^;]+);' % name, text)
-        env[name] = bool(eval(_cxx_to_py(m.group(1)), {}, env))
-    env['kPairRows'] = True                              # (Q32 == 1 and Q64 == 1 at every long length: fft_configs.hpp; the emulator asserts it)
-    multi_def = re.search(r'constexpr bool MULTI = ([^;]+);', text).group(1)
-    modes_of_row_m = sorted({env[m] for m in re.findall(r'launch_row_m<Q, (ROW_\w+), T>', text)})
-    assert modes_of_row_m == [0, 1, 2, 3, 4]
-    out = set()
-    stack = []                                           # per open brace: the constexpr condition it is under (or None)
-    pos = 0
-    token = re.compile(r'(if constexpr \(((?:[^()]|\([^()]*\))*)\)\s*\{)|(\}\s*else\s*\{)|(\{)|(\})|' + site + r'\((k_rowpass|k_rowpair)<([^;]*?)>,\s*(?:grid|dim3|bp?\))')
-    last_closed = None
-    for m in token.finditer(text):
-        if m.group(1):
-            stack.append(m.group(2))
-        elif m.group(3):
-            cond = stack.pop()
-            stack.append(None if cond is None else 'not (%s)' % cond)
-        elif m.group(4):
-            stack.append(None)
-        elif m.group(5):
-            stack.pop()
-        else:
-            kernel, args = m.group(6), [a.strip() for a in m.group(7).split(',')]
-            for mode in (modes_of_row_m if any(re.search(r'\bMODE\b', a) for a in args) or any(c and 'MODE' in c for c in stack) else [None]):
-                e = dict(env)
-                if mode is not None:
-                    e['MODE'] = mode
-                    e['MULTI'] = bool(eval(_cxx_to_py(multi_def), {}, e))
-                if not all(eval(_cxx_to_py(c), {}, e) for c in stack if c is not None):
-                    continue
-                v = [eval(_cxx_to_py(a), {}, e) for a in args]
-                t = 'f32' if esize == 4 else 'f64'
-                if kernel == 'k_rowpass':
-                    v = v + [False, 0, -1][len(v) - 5:]
-                    out.add('k_rowpass L=%d T=%s MODE=%d ONEV=%d PRESUM=%d NXC=%d SUBC=%d' % (L, t, v[2], v[3], v[5], v[6], v[7]))
-                else:
-                    v = v + [0, -1][len(v) - 4:]
-                    out.add('k_rowpair L=%d T=%s MODE=%d NXC=%d SUBC=%d' % (L, t, v[2], v[4], v[5]))
-    assert not stack
-    return out
-
-
-def launchable_outer_kernels(outer, L):
-    text = re.sub(r'//[^\n]*', '', open(os.path.join(CSRC, 'fft_kernels.hip')).read())
-    st = _settings(outer, L)
-    modes = dict(COL_PER_IMAGE=0, COL_SPLIT_FWD=3, COL_SPLIT_INV=4, COL_SPLIT_INV_SUM=5)
-    out = set()
-    for c, realp, mode, t in re.findall(r'launch_outer<RL_CFG_L, OC::(\w+), (true|false), (COL_\w+), (float|double)>\(p', text):
-        for nyc in (0, 512 * st['M']):                   # launch_outer: the generic kernel and the one with 512 M rows
-            out.add('k_colconv_outer L=%d C=%d REALP=%d MODE=%d T=%s NYC=%d' % (L, st[c], realp == 'true', modes[mode], 'f32' if t == 'float' else 'f64', nyc))
-    assert re.search(r'constexpr int NY = 512 \* OuterCol<L>::M;', text)
-    return out
-
-
-def _table(fn):
+def _table(fn, *args):
     buf = ctypes.create_string_buffer(1 << 16)
-    n = fn(buf, len(buf))
+    n = fn(*args, buf, len(buf))
     assert 0 < n < len(buf)
     return set(buf.value.decode().split('\n')) - {''}
 
 
-def test_every_launchable_instantiation_has_an_emulated_counterpart(libs):
-    """What fft_kernels.hip can launch at the long lengths (parsed from its launch sites) against what the emulators can run
-    (printed from the tables their dispatch runs through): a launchable instantiation with no emulated counterpart fails."""
+def launchable(rows, L, esize):
+    """The device's variants for a length and element size: the rows of csrc/kernel_variants.hpp that exist with the device's
+    compile-time sizes, in the column family launch_col takes -- printed by the walk the launchers and prepare() take."""
+    return _table(rows.emu_device_table, L, esize)
+
+
+def test_every_launchable_instantiation_has_an_emulated_counterpart(libs, emu):
+    """What fft_kernels.hip can launch (the shared list with the device's sizes) against what the emulators can run (the same
+    list with theirs): a launchable instantiation with no emulated counterpart fails.  At the long lengths the launchable set
+    must be, name for name, tests/golden/launchable_long_kernels.txt -- what the launch ladders gave before the list replaced
+    them (parsed from their rl_launch( sites at that commit; the allow_lds( sites gave the same set)."""
     rows, outer = libs
     can_run = _table(rows.emu_long_table)
     can_run_outer = {re.sub(r' LDS=\d+', '', s) for s in _table(outer.emu_outer_table)}
+    golden = set(open(os.path.join(ROOT, 'tests', 'golden', 'launchable_long_kernels.txt')).read().split('\n')) - {''}
+    got = set()
     for L in LENGTHS:
+        want_outer = set()
         for esize in (4, 8):
             assert rows.emu_long_q(L, esize, 0) == 1 and rows.emu_long_q(L, esize, 1) == 1
-            want = launchable_row_kernels(L, esize)
+            have = launchable(rows, L, esize)
+            assert not [w for w in have if w.startswith('k_colconv ')], 'the long lengths launch the outer column kernels in both types'
+            want = {w for w in have if w.startswith('k_row')}
             assert len([w for w in want if w.startswith('k_rowpass')]) == 8 and len(want) >= 11, sorted(want)
             missing = want - can_run
             assert not missing, 'launchable, not emulated: %s' % sorted(missing)
-        want = launchable_outer_kernels(outer, L)
-        assert len(want) == 18, sorted(want)
-        assert not (want - can_run_outer), sorted(want - can_run_outer)
+            want_outer |= have - want
+            got |= have
+        assert len(want_outer) == 18, sorted(want_outer)
+        assert not (want_outer - can_run_outer), sorted(want_outer - can_run_outer)
+    assert got == golden, (sorted(got - golden), sorted(golden - got))
     assert 'k_rowpair L=2304 T=f32 MODE=2 NXC=2048 SUBC=1' in can_run
+    # The short lengths (tests/emu/emu.cpp).  A variant with a compile-time image size (NYC / NXC: on the device 512, at L = 576
+    # in float) runs in the emulator at a size of its own, and with it at the length and in the types that host that size there
+    # (192 at L = 256, float and double): for such a row the size and, with it, L and T may differ.  No other field may, and a
+    # row without a compile-time size must match in every field.
+    can_run_short = _table(emu.emu_table)
+    sized = lambda s: re.sub(r'(NYC|NXC)=[1-9]\d*', r'\1=N', re.sub(r' L=\d+ T=f\d+', '', s))
+    can_run_sized = {sized(s) for s in can_run_short if re.search(r'(NYC|NXC)=[1-9]', s)}
+    for L in SHORT_LENGTHS:
+        for esize in (4, 8):
+            want = launchable(rows, L, esize)
+            assert len([w for w in want if w.startswith('k_rowpass')]) >= 8 and not [w for w in want if 'outer' in w], sorted(want)
+            missing = {w for w in want if not (sized(w) in can_run_sized if re.search(r'(NYC|NXC)=[1-9]', w) else w in can_run_short)}
+            assert not missing, 'launchable, not emulated: %s' % sorted(missing)
+    assert len(launchable(rows, 576, 4)) == 13 + 10 + 5 and len(launchable(rows, 576, 8)) == 6 + 8 + 3
 
 
 def test_every_launchable_row_kernel_may_use_its_lds():
     """A row kernel of a long length needs more than the default 64 KB of dynamic LDS in float64 at 4608 (4626 slots x 16 bytes):
-    every instantiation fft_kernels.hip can launch must be among those prepare() raises the limit of.  (Caught the PRESUM update,
-    launched for multi-view `ratio - 1` plans, missing from prepare_rows: a float64 4096^2 multi-view plan with RLSTED_SUB_ONE=1
-    could not launch it.)"""
-    for L in LENGTHS:
-        for esize in (4, 8):
-            missing = launchable_row_kernels(L, esize) - launchable_row_kernels(L, esize, 'allow_lds')
-            assert not missing, 'launched without allow_lds: %s' % sorted(missing)
+    every instantiation fft_kernels.hip can launch must be among those prepare() raises the limit of.  (The PRESUM update,
+    launched for multi-view `ratio - 1` plans, was once missing from a hand-written prepare list: a float64 4096^2 multi-view
+    plan with RLSTED_SUB_ONE=1 could not launch it.)  It holds by construction for every kernel of every length: a launch and
+    prepare() walk the same list of csrc/kernel_variants.hpp, and no rl_launch( or allow_lds( of fft_kernels.hip names one of
+    the four kernel templates outside such a walk, where the template arguments are the row's."""
+    text = re.sub(r'//[^\n]*', '', open(os.path.join(CSRC, 'fft_kernels.hip')).read())
+    sites = {'rl_launch': [], 'allow_lds': []}
+    for m in re.finditer(r'\b(rl_launch|allow_lds)\((k_\w+)<([^;]*?)>,', text):
+        assert m.group(2) in WALK_OF, m.group(0)
+        before = text[:m.start()]
+        walk = before.rfind(WALK_OF[m.group(2)])
+        assert walk >= 0 and '});' not in before[walk:] and re.match(r'for_each_\w+<[^(]*>\(\[&\]\(auto v\) \{', before[walk:]), \
+            'outside a walk over the variant list: %s' % m.group(0)
+        args = [a.strip() for a in m.group(3).split(',')]
+        assert all(a in ('RL_CFG_L', 'C', 'Q', 'QP', 'T') or a.startswith('V::') for a in args), 'hand-written template arguments: %s' % m.group(0)
+        sites[m.group(1)].append((m.group(2), tuple('Q' if a == 'QP' else a for a in args)))
+    assert sorted(sites['rl_launch']) == sorted(sites['allow_lds']) and sorted(k for k, _ in sites['rl_launch']) == sorted(WALK_OF)
+    assert len(re.findall(r'\b(?:rl_launch|allow_lds)\(', text)) == 8 + 2       # those, and the two definitions
 
 
 def test_outer_lds_is_the_launchers(libs):

@@ -47,6 +47,6 @@ cd "$ROOT"
 if [ -n "${RLSTED_ASAN_TESTS:-}" ]; then        # e.g. RLSTED_ASAN_TESTS=tests/test_long_rows_cpu.py tools/asan_emu.sh -k 4608
     python -m pytest $RLSTED_ASAN_TESTS -x -q -p no:cacheprovider "$@"
 else
-    python -m pytest tests/test_emulated_kernels.py tests/test_long_rows_cpu.py tests/test_sep_cpu.py tests/test_poisson_spec.py tests/test_asan_gauss_fit.py -x -q -p no:cacheprovider "$@"
+    python -m pytest tests/test_emulated_kernels.py tests/test_kernel_variants.py tests/test_long_rows_cpu.py tests/test_sep_cpu.py tests/test_poisson_spec.py tests/test_asan_gauss_fit.py -x -q -p no:cacheprovider "$@"
 fi
 echo "sanitizer run clean"
