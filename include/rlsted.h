@@ -125,6 +125,35 @@ int rl_deconv_set_acceleration(rl_deconv* h, int mode);
 /* out [batch]: the a that formed each frame's last extrapolated point (0 before one). */
 int rl_deconv_get_alpha(rl_deconv* h, double* out);
 
+/* Total-variation regularised Richardson-Lucy (RL-TV; Dey et al., Microsc. Res. Tech. 69, 260, 2006), per plan, off by default.
+ * Opt in: it departs from the reference's iteration by design.  At low dose plain Richardson-Lucy fits
+ * the noise once it runs long enough; the multiplicative TV step keeps the estimate piecewise smooth.  Per frame, with psi the
+ * plan's own iteration applied to the point at hand x (the estimate, or the extrapolated y_k when the Biggs-Andrews mode is on: its
+ * psi is then this regularised step), n = ny * nx, all arithmetic in the plan's element type T unless stated, contraction off, IEEE
+ * sqrt and /:
+ *     s      = (sum x) / n                     float64 sum in the fixed order of csrc/accel_kernels.hpp (thread, tree, workgroups);
+ *                                              1 exactly for the start from ones
+ *     eps2   = T((eps_rel s) (eps_rel s))      formed in float64, rounded once to T
+ *     dx[i,j]= x[i,j+1] - x[i,j]  (0 in the last column)       dy[i,j] = x[i+1,j] - x[i,j]  (0 in the last row)
+ *     m      = sqrt((dx dx + dy dy) + eps2)    px = dx / m     py = dy / m
+ *     div    = ((px[i,j] - px[i,j-1]) + (py[i,j] - py[i-1,j]))   (the subtracted term is 0 in column 0 / row 0)
+ *     w      = 1 / (1 - lambda div)
+ *     x_new  = psi(x) w
+ * Every pixel has |div| <= 2 + sqrt(2): px^2 + py^2 <= 1 and each of the two backward neighbours' components has magnitude <= 1.
+ * Accepted: 0 <= lambda <= 0.25 and eps_rel > 0 finite -- the denominator is then >= 0.146 with no clamp; anything else is
+ * RL_ERR_INVALID.  lambda == 0 switches the mode off: the plan then runs the plain path bit for bit.  The mode applies from the
+ * next iterate / batch run / iterate_until on, on every plan type and both element types; switching it on allocates one more image
+ * per frame and the sums' partials (counted in device_bytes).  iterate(a) then iterate(b) is iterate(a + b) bit for bit; a frame's
+ * result in a float64 plan does not depend on its batch; rl_forward / rl_adjoint / rl_deconv_divergence in between change nothing.
+ * CONDITIONING: the step is an explicit TV flow.  It amplifies differences in x -- rounding differences between two builds or
+ * element types included -- unless lambda max(x) / (eps_rel mean(x)) is well below 1/4: lambda = 0.01, eps_rel = 0.1 on natural
+ * images is stable (a 1e-7 relative perturbation per iteration moves the K = 200 result by 5e-7, less than it moves plain
+ * Richardson-Lucy); lambda >= 0.03, eps_rel <= 0.03, or sparse emitters on black are not (1e-2 .. 1e-1), and the result is then
+ * reproducible only on one build and element type.  rl_deconv_get_tv: the values in force (lambda 0: off);
+ * either pointer may be NULL. */
+int rl_deconv_set_tv(rl_deconv* h, double lambda, double eps_rel);
+int rl_deconv_get_tv(const rl_deconv* h, double* lambda, double* eps_rel);
+
 /* How well the current estimate explains the data: the Poisson I-divergence D(m || p) = sum m log(m / p) - m + p of every frame,
  * out [batch], with m the stored measurement and p = H(estimate) -- the quantity Richardson-Lucy minimises.  Computed on the
  * device: p is what rl_forward returns for the current estimate (the same launches, reading the estimate where it is), nothing
@@ -188,7 +217,8 @@ int rl_deconv_bench_cycles(rl_deconv* h, int k, int reps, int rng_kind, uint64_t
 
 /* Device address of a plan buffer for zero-copy hand-off (e.g. the RCCL gather
  * of final estimates): which = 0 estimate [batch][ny][nx], 1 measurement, 2
- * noiseless [batch][n_psf][ny][nx], 3 object.  The buffer stays owned by the
+ * noiseless [batch][n_psf][ny][nx], 3 object, 4 the RL-TV weights w [batch][ny][nx] of the
+ * last regularised step (RL_ERR_STATE before rl_deconv_set_tv switched the mode on).  The buffer stays owned by the
  * plan; *dtype = RL_F32 / RL_F64 element type.  Synchronise the context first.
  * The allocation extends 16 KiB past n_elements (zeroed slack that the row kernels' unconditional 64-lane
  * loads may read and discard): never write there, never assume the next buffer starts right behind. */

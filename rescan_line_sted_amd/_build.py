@@ -58,6 +58,7 @@ def jobs():
     out.append((os.path.join(OBJ, 'sep_kernels.o'), os.path.join(CSRC, 'sep_kernels.hip'), DEVICE))
     out.append((os.path.join(OBJ, 'accel_kernels.o'), os.path.join(CSRC, 'accel_kernels.hip'), DEVICE))
     out.append((os.path.join(OBJ, 'stop_kernels.o'), os.path.join(CSRC, 'stop_kernels.hip'), DEVICE))
+    out.append((os.path.join(OBJ, 'tv_kernels.o'), os.path.join(CSRC, 'tv_kernels.hip'), DEVICE))
     out.append((os.path.join(OBJ, 'fig3_kernels.o'), os.path.join(CSRC, 'fig3_kernels.hip'), DEVICE))
     out.append((os.path.join(OBJ, 'quality_api.o'), os.path.join(CSRC, 'quality_api.cpp'), ['-x', 'hip'] + DEVICE))
     out.append((os.path.join(OBJ, 'gauss_fit.o'), os.path.join(CSRC, 'gauss_fit.cpp'), ['-ffp-contract=off']))

@@ -27,6 +27,21 @@ def accel_mode(acceleration):
     except (KeyError, TypeError):
         raise ValueError("acceleration must be None or 'biggs-andrews'; got %r" % (acceleration,)) from None
 
+
+def tv_params(tv_lambda, tv_epsilon=0.1):
+    """(lambda, eps_rel) of rl_deconv_set_tv from the keywords: tv_lambda None or 0 -> off; otherwise 0 < tv_lambda <= 0.25 and
+    tv_epsilon > 0, finite."""
+    try:
+        lam = 0.0 if tv_lambda is None else float(tv_lambda)
+        eps = float(tv_epsilon)
+    except (TypeError, ValueError):
+        raise ValueError('tv_lambda and tv_epsilon must be numbers; got %r, %r' % (tv_lambda, tv_epsilon)) from None
+    if not 0.0 <= lam <= 0.25:                               # (nan fails both comparisons)
+        raise ValueError('tv_lambda must be None or in [0, 0.25]; got %r' % (tv_lambda,))
+    if not (eps > 0.0 and eps < float('inf')):
+        raise ValueError('tv_epsilon must be positive and finite; got %r' % (tv_epsilon,))
+    return lam, eps
+
 # name -> (restype, argtypes); exactly the symbols include/rlsted.h declares
 _c = ctypes
 _vp, _i, _dp = _c.c_void_p, _c.c_int, _c.POINTER(_c.c_double)
@@ -50,6 +65,8 @@ PROTOTYPES = {
     'rl_deconv_set_estimate': (_i, [_vp, _dp]),
     'rl_deconv_set_acceleration': (_i, [_vp, _i]),
     'rl_deconv_get_alpha': (_i, [_vp, _dp]),
+    'rl_deconv_set_tv': (_i, [_vp, _c.c_double, _c.c_double]),
+    'rl_deconv_get_tv': (_i, [_vp, _dp, _dp]),
     'rl_deconv_divergence': (_i, [_vp, _dp]),
     'rl_deconv_iterate_until': (_i, [_vp, _i, _i, _i, _c.c_double, _c.POINTER(_i), _dp, _c.POINTER(_i)]),
     'rl_deconv_get_object': (_i, [_vp, _dp]),
@@ -208,9 +225,11 @@ def common_psf_shape(psfs):
 class DeconvPlan:
     """rl_deconv: `batch` frames sharing one PSF set and one image shape."""
 
-    def __init__(self, psfs, batch, ny, nx, dtype='f32', device=0, stream=0, acceleration=None):
-        """acceleration: None (plain Richardson-Lucy, the reference's iteration) or 'biggs-andrews' (set_acceleration)."""
+    def __init__(self, psfs, batch, ny, nx, dtype='f32', device=0, stream=0, acceleration=None, tv_lambda=None, tv_epsilon=0.1):
+        """acceleration: None (plain Richardson-Lucy, the reference's iteration) or 'biggs-andrews' (set_acceleration).
+        tv_lambda: None (no regulariser) or the weight of the total-variation step, tv_epsilon its relative smoothing (set_tv)."""
         mode = accel_mode(acceleration)
+        tv = tv_params(tv_lambda, tv_epsilon)
         psfs = [as_f64(p) for p in psfs]
         for p in psfs:
             if p.ndim != 3 or p.shape[0] != 1:
@@ -227,6 +246,8 @@ class DeconvPlan:
         self.acceleration = None
         if mode:
             self.set_acceleration(acceleration)
+        if tv[0]:
+            self.set_tv(*tv)
 
     def __del__(self):
         h = getattr(self, 'handle', None)
@@ -286,6 +307,20 @@ class DeconvPlan:
         mode = accel_mode(acceleration)
         check(lib.rl_deconv_set_acceleration(self.handle, mode))
         self.acceleration = 'biggs-andrews' if mode else None
+
+    def set_tv(self, tv_lambda, tv_epsilon=0.1):
+        """Total-variation regularised Richardson-Lucy (include/rlsted.h rl_deconv_set_tv) from the next
+        iterate / batch run on: every step is multiplied by 1 / (1 - tv_lambda div(grad x / |grad x|)), the gradient's length smoothed
+        by tv_epsilon times the frame's mean.  tv_lambda None or 0: off (the plain path, bit for bit); at most 0.25.  The defaults of
+        the sweep, 0.01 and 0.1, are well conditioned on natural images; see the header for what is not."""
+        lam, eps = tv_params(tv_lambda, tv_epsilon)
+        check(lib.rl_deconv_set_tv(self.handle, lam, eps))
+
+    def tv(self):
+        """(tv_lambda, tv_epsilon) in force; tv_lambda 0.0: off."""
+        a, b = _c.c_double(), _c.c_double()
+        check(lib.rl_deconv_get_tv(self.handle, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
 
     def alpha(self):
         """(B,) float64: the extrapolation weight that formed each frame's last extrapolated point (0 before one)."""
@@ -409,7 +444,7 @@ class DeconvPlan:
         check(lib.rl_deconv_bench_cycles(self.handle, int(k), int(reps), rng, _c.c_uint64(seed), ctypes.byref(ms)))
         return ms.value
 
-    BUFFERS = {'estimate': 0, 'measurement': 1, 'noiseless': 2, 'object': 3}
+    BUFFERS = {'estimate': 0, 'measurement': 1, 'noiseless': 2, 'object': 3, 'tv_weight': 4}
 
     def device_array(self, which='estimate'):
         """Zero-copy view of a plan buffer as an object with __cuda_array_interface__
@@ -418,7 +453,7 @@ class DeconvPlan:
         idx = self.BUFFERS[which]
         p, n, dt = _vp(), _c.c_size_t(), _i()
         check(lib.rl_deconv_device_ptr(self.handle, idx, ctypes.byref(p), ctypes.byref(n), ctypes.byref(dt)))
-        shape = (self.B, self.ny, self.nx) if idx in (0, 3) else (self.B, self.V, self.ny, self.nx)
+        shape = (self.B, self.ny, self.nx) if idx in (0, 3, 4) else (self.B, self.V, self.ny, self.nx)
         self.ctx.synchronize()
         return DeviceArray(p.value, shape, '<f4' if dt.value == RL_F32 else '<f8', self)
 

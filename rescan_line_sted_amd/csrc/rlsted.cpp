@@ -23,6 +23,7 @@
 #include "sep_kernels.hpp"
 #include "sep_taps.hpp"
 #include "stop_kernels.hpp"
+#include "tv_kernels.hpp"
 
 using namespace rl;
 
@@ -305,7 +306,8 @@ struct rl_deconv {
             if (pair) RL_TRY(row_pair(ROW_FWD, nf, nullptr, pair_spec(f0), off(est, o), nullptr, nullptr));
             else if (!sep) RL_TRY(row(ROW_FWD, (unsigned)nf, nullptr, off(spec_a, (size_t)f0 * n_spec() * 2), off(est, o), nullptr, nullptr));
         }
-        RL_TRY(iterate_chunk({f0, nf, first, from_ones, /* drop_spectrum */ pair}));
+        const Iter it{f0, nf, first, from_ones, /* drop_spectrum */ pair};
+        RL_TRY(tv_on() ? tv_iterate(it, /* have_sum */ false, /* rebuild_spectrum */ false) : iterate_chunk(it));   // (est = y_s: the sum is not of it)
         HIP_TRY(accel_reduce(dtype, off(est, o), off(acc_y, o), off(acc_g, o), part, n_img(), nf,
                              (from_ones ? ACC_Y_ONES : 0) | (s > 0 ? ACC_HAVE_PREV : 0), cur()));
         return RL_OK;
@@ -357,6 +359,35 @@ struct rl_deconv {
     float ratio_scale(const Iter* it) const { return it && it->from_ones ? q_est : q_ratio; }
     // H_t inside a `ratio - 1` iteration: the spectra of residuals (rl_adjoint's input is an image)
     bool residual(ColKind kind, const Iter* it) const { return it && kind != COL_H && sub(); }
+    // ---- total-variation regularisation (tv_kernels.hpp, rl_deconv_set_tv): per frame the weights w of the point at hand in one image
+    // buffer and the float64 per-workgroup partials of sum est -- allocated when the mode is first switched on.  tv_sum_valid: the
+    // partials are of the estimate as it stands (APPLY left them); everything else that writes est clears it.
+    double tv_lambda = 0.0, tv_eps_rel = 0.1;
+    void* tv_w = nullptr;
+    double* tv_part = nullptr;
+    bool tv_sum_valid = false;
+    bool tv_on() const { return tv_lambda > 0.0; }
+    int ensure_tv() {
+        if (!tv_w) RL_TRY(alloc(&tv_w, (size_t)B * n_img() * esize(dtype)));
+        if (!tv_part) RL_TRY(alloc(&tv_part, (size_t)B * acc_blocks() * sizeof(double)));
+        return RL_OK;
+    }
+    // The regularised step on the frames of `it`: [SUM unless the partials are of the point at hand] -> WEIGHT -> the plan's iteration
+    // -> APPLY.  The step from ones has w = 1 exactly (s = 1, every difference 0): no WEIGHT, APPLY only leaves the sum.
+    // rebuild_spectrum: the loop reads rowFFT(est), and the spectrum ROW_UPDATE stored is of psi(x), not of psi(x) w.
+    int tv_iterate(const Iter& it, bool have_sum, bool rebuild_spectrum) {
+        const size_t o = (size_t)it.f0 * n_img();
+        double* part = tv_part + (size_t)it.f0 * acc_blocks();
+        if (!it.from_ones) {
+            if (!have_sum) HIP_TRY(tv_apply(dtype, off(est, o), nullptr, part, ny, nx, it.nf, TV_SUM_ONLY, cur()));
+            HIP_TRY(tv_weight(dtype, off(est, o), off(tv_w, o), part, tv_lambda, tv_eps_rel, ny, nx, it.nf, cur()));
+            if (rebuild_spectrum && pair) RL_TRY(row_pair(ROW_FWD, it.nf, nullptr, pair_spec(it.f0), off(est, o), nullptr, nullptr));
+            else if (rebuild_spectrum && !sep) RL_TRY(row(ROW_FWD, (unsigned)it.nf, nullptr, est_spec(it.f0), off(est, o), nullptr, nullptr));
+        }
+        RL_TRY(iterate_chunk(it));
+        HIP_TRY(tv_apply(dtype, off(est, o), it.from_ones ? nullptr : off(tv_w, o), part, ny, nx, it.nf, it.from_ones ? TV_SUM_ONLY : 0, cur()));
+        return RL_OK;
+    }
     // ---- frame pairs (conv_kernels.hpp rowpair_body; RLSTED_PAIR): two frames ride through one complex image, the
     // Richardson-Lucy loop of a single-view plan then runs on spectra [pairs][ny][lx] -- no Hermitian packing /
     // splitting around the row transforms.  The simulation and the H / H_t calls keep the per-frame layout.
@@ -789,7 +820,7 @@ struct rl_deconv {
         // per slice; `lanes` slices are in flight at once, together about the 256 MiB Infinity Cache
         const double budget_mb = opt.chunk_mb_set ? opt.chunk_mb : (opt.lanes > 1 ? 108.0 : 288.0);
         const double specs = one_buffer() ? 1.0 : 1.0 + V;   // spectra alive in an iteration
-        const double per_frame = (specs * 2.0 * n_spec() + (1.0 + V + (accel ? 3.0 : 0.0)) * n_img()) * esize(dtype);   // (+ x, y, g)
+        const double per_frame = (specs * 2.0 * n_spec() + (1.0 + V + (accel ? 3.0 : 0.0) + (tv_on() ? 1.0 : 0.0)) * n_img()) * esize(dtype);   // (+ x, y, g; + w)
         // Frames of 32 MB and more (2048^2 up) do not live in the Infinity Cache whatever the slice: there the slice
         // only has to fill the chip -- ~1 GB per slice measured best at 2048^2 (point 658 -> 713, 4 views 180 -> 192
         // frames/s over 2-frame / 1-frame slices).
@@ -973,6 +1004,7 @@ struct rl_deconv {
             const bool drop = pair && k >= 4;
             for (int i = 0; i < k && rc == RL_OK; ++i) {
                 if (accel) rc = accel_step(f0, nf, acc_steps + i, shortcut && i == 0, restart && i == 0);
+                else if (tv_on()) rc = tv_iterate({f0, nf, shortcut && i == 0, restart && i == 0, /* drop_spectrum */ pair}, i > 0 || tv_sum_valid, true);
                 else rc = iterate_chunk({f0, nf, shortcut && i == 0, restart && i == 0, drop && i == k - 1});
             }
         }
@@ -997,6 +1029,8 @@ struct rl_deconv {
             spec_valid = false;   // (a plain iterate after a change of mode rebuilds it; an accelerated one transforms y)
             acc_steps += k;
         }
+        if (tv_on()) spec_valid = false;   // (APPLY changed est after ROW_UPDATE stored its spectrum; a TV step transforms its own point)
+        if (k > 0 || restart) tv_sum_valid = tv_on() && !accel && k > 0;   // (accelerated: est is x_k, the next point y_k is formed from it)
         iterations += k;
         return RL_OK;
     }
@@ -1431,6 +1465,7 @@ int rl_deconv_set_estimate(rl_deconv* h, const double* estimate) {
     RL_TRY(h->upload(estimate, h->est, (size_t)h->B * h->n_img()));
     h->est_ready = true;
     h->spec_valid = false;   // the next iterate rebuilds rowFFT(estimate)
+    h->tv_sum_valid = false;
     RL_TRY(h->accel_reset());   // a set estimate is a point with no history
     return RL_OK;
 }
@@ -1458,6 +1493,25 @@ int rl_deconv_get_alpha(rl_deconv* h, double* out) {
     return RL_OK;
 }
 
+int rl_deconv_set_tv(rl_deconv* h, double lambda, double eps_rel) {
+    if (!h) return fail(RL_ERR_INVALID, "handle is NULL");
+    if (!(lambda >= 0.0 && lambda <= 0.25)) return fail(RL_ERR_INVALID, "lambda must be in [0, 0.25]");
+    if (!(eps_rel > 0.0) || !std::isfinite(eps_rel)) return fail(RL_ERR_INVALID, "eps_rel must be positive and finite");
+    HIP_TRY(hipSetDevice(h->ctx->device));
+    if (lambda > 0.0) RL_TRY(h->ensure_tv());
+    if ((lambda > 0.0) != h->tv_on()) h->spec_valid = false;
+    h->tv_lambda = lambda;
+    h->tv_eps_rel = eps_rel;
+    return RL_OK;
+}
+
+int rl_deconv_get_tv(const rl_deconv* h, double* lambda, double* eps_rel) {
+    if (!h) return fail(RL_ERR_INVALID, "handle is NULL");
+    if (lambda) *lambda = h->tv_lambda;
+    if (eps_rel) *eps_rel = h->tv_eps_rel;
+    return RL_OK;
+}
+
 int rl_deconv_reset_estimate(rl_deconv* h) {
     if (!h) return fail(RL_ERR_INVALID, "handle is NULL");
     h->est_ready = false;
@@ -1467,12 +1521,12 @@ int rl_deconv_reset_estimate(rl_deconv* h) {
 // rl_deconv_iterate between its events: k iterations on the whole batch, from ones if the plan holds no estimate
 static int iterate_batch(rl_deconv* h, int k) {
     bool restart = !h->est_ready;
-    // (an accelerated plan transforms the extrapolated point inside the loop instead)
-    if (!restart && !h->spec_valid && h->pair && !h->accel) {
+    // (an accelerated or a regularised plan transforms its point inside the loop instead)
+    if (!restart && !h->spec_valid && h->pair && !h->accel && !h->tv_on()) {
         RL_TRY(h->row_pair(ROW_FWD, h->B, nullptr, h->spec_a, h->est, nullptr, nullptr));
         h->spec_valid = true;
     }
-    if (!restart && !h->spec_valid && !h->sep && !h->accel) {   // H / H_t were called in between: rebuild rowFFT(est)
+    if (!restart && !h->spec_valid && !h->sep && !h->accel && !h->tv_on()) {   // H / H_t were called in between: rebuild rowFFT(est)
         RL_TRY(h->row(ROW_FWD, (unsigned)h->B, nullptr, h->spec_a, h->est, nullptr, nullptr));
         h->spec_valid = true;
     }
@@ -1545,6 +1599,7 @@ int rl_deconv_iterate_until(rl_deconv* h, int k_max, int check_every, int rule, 
     HIP_TRY(hipMemcpyAsync(h->est, h->stop_result, (size_t)h->B * h->n_img() * esize(h->dtype), hipMemcpyDeviceToDevice, s));
     h->est_ready = true;
     h->spec_valid = false;
+    h->tv_sum_valid = false;
     RL_TRY(h->accel_reset());
     for (int f = 0; f < h->B; ++f) {
         if (iterations_out) iterations_out[f] = state[f].iterations;
@@ -1835,7 +1890,11 @@ int rl_deconv_device_ptr(rl_deconv* h, int which, void** ptr, size_t* n_elements
     void* p = nullptr;
     size_t n = 0;
     switch (which) {
-        case 0: p = h->est; n = (size_t)h->B * h->n_img(); break;
+        case 0:   // (the caller may write the estimate: the sums RL-TV keeps of it are void)
+            p = h->est;
+            n = (size_t)h->B * h->n_img();
+            h->tv_sum_valid = false;
+            break;
         case 1:
             p = h->meas;
             n = (size_t)h->B * h->V * h->n_img();
@@ -1846,7 +1905,12 @@ int rl_deconv_device_ptr(rl_deconv* h, int which, void** ptr, size_t* n_elements
             break;
         case 2: p = h->noiseless; n = (size_t)h->B * h->V * h->n_img(); break;
         case 3: p = h->obj; n = (size_t)h->B * h->n_img(); break;
-        default: return fail(RL_ERR_INVALID, "which must be 0..3");
+        case 4:
+            if (!h->tv_w) return fail(RL_ERR_STATE, "no RL-TV weights: rl_deconv_set_tv has not switched the mode on");
+            p = h->tv_w;
+            n = (size_t)h->B * h->n_img();
+            break;
+        default: return fail(RL_ERR_INVALID, "which must be 0..4");
     }
     *ptr = p;
     if (n_elements) *n_elements = n;
@@ -1930,6 +1994,7 @@ int rl_deconv_time_kernels(rl_deconv* h, int reps, double* avg_ms) {
     // the repeated launches trashed the RL state on purpose; force a clean restart
     h->est_ready = false;
     h->spec_valid = false;
+    h->tv_sum_valid = false;
     return RL_OK;
 }
 

@@ -24,6 +24,11 @@ extrapolated Richardson-Lucy -- fewer iterations for the same fit to the data,
 by design not the reference's sequence of estimates.
 The default, None, is the reference's iteration.
 
+Regularisation: `Deconvolver(tv_lambda=0.01)` and `deconvolve(..., tv_lambda=0.01)`
+multiply every step by the total-variation weight of Dey et al. (2006) -- at low
+dose the estimate then stops fitting the noise.  The
+default, None, is the reference's iteration.
+
 Stopping: `deconvolve_until` stops every frame of a batch by its own Poisson
 I-divergence, formed on the device.
 """
@@ -49,12 +54,14 @@ class Deconvolver:
     (nz, ny, nx) float64 arrays, estimate updated in place by iterate()."""
 
     def __init__(self, psfs, output_prefix=None, verbose=True, dtype=None,
-                 device=None, rng='numpy', acceleration=None):
+                 device=None, rng='numpy', acceleration=None, tv_lambda=None, tv_epsilon=0.1):
         """'psfs' is a list of numpy arrays, one for each PSF (ref:479-494).
         dtype/device/rng/acceleration are extensions: device arithmetic type, GPU
         index, the Poisson generator ('numpy' = the reference's np.random.poisson
         on the host, 'philox' = counter-based generator on the device) and the
-        iteration (None = the reference's, 'biggs-andrews' = extrapolated)."""
+        iteration (None = the reference's, 'biggs-andrews' = extrapolated);
+        tv_lambda / tv_epsilon: the total-variation regulariser (None = off;
+        DeconvPlan.set_tv)."""
         self.psfs = list(psfs)
         if output_prefix is None:
             output_prefix = os.getcwd()
@@ -70,6 +77,7 @@ class Deconvolver:
         self.rng = rng
         _lib.accel_mode(acceleration)                   # (a bad name fails here, not at the first iteration)
         self.acceleration = acceleration
+        self.tv_lambda, self.tv_epsilon = _lib.tv_params(tv_lambda, tv_epsilon)
         for p in self.psfs:
             if np.ndim(p) != 3:
                 raise NotImplementedError('PSFs must be 3-D arrays (pz, py, px); got %s' % (np.shape(p),))
@@ -109,7 +117,7 @@ class Deconvolver:
             if p is not None and self._estimate_stale:      # keep what the old plan computed
                 self._estimate, self._estimate_stale = p.estimate(), False
             self._plan = DeconvPlan(self._plan_psfs(nz), nz, ny, nx, dtype=self.dtype, device=self.device,
-                                    acceleration=self.acceleration)
+                                    acceleration=self.acceleration, tv_lambda=self.tv_lambda, tv_epsilon=self.tv_epsilon)
             self._measurement_on_device = False             # the host copy is pushed again when needed
             self._estimate_push = self._estimate is not None and np.shape(self._estimate) == (nz, ny, nx)
             if hasattr(self, 'H_t_normalization'):
@@ -349,16 +357,20 @@ def simulate(objects, psfs, total_brightness=None, seed=0, dtype='f32', device=N
     return plan, plan.noiseless(), plan.measurement()
 
 
-def deconvolve(measurement, psfs, iterations, dtype='f32', device=None, plan=None, acceleration=None):
+def deconvolve(measurement, psfs, iterations, dtype='f32', device=None, plan=None, acceleration=None, tv_lambda=None,
+               tv_epsilon=0.1):
     """K Richardson-Lucy iterations on a batch: measurement (B, V, ny, nx).
     acceleration: None (plain) or 'biggs-andrews' (a given plan is switched to it).
+    tv_lambda, tv_epsilon: the total-variation regulariser (None: off; a given plan is switched to it).
     Returns the estimates (B, ny, nx)."""
+    _lib.tv_params(tv_lambda, tv_epsilon)
     measurement = np.asarray(measurement, dtype=np.float64)
     B, V, ny, nx = measurement.shape
     if plan is None:
         plan = DeconvPlan(psfs, B, ny, nx, dtype=dtype,
                           device=_DEFAULT_DEVICE if device is None else device)
     plan.set_acceleration(acceleration)
+    plan.set_tv(tv_lambda, tv_epsilon)
     plan.set_measurement(measurement)
     plan.reset_estimate()
     plan.iterate(iterations)
@@ -366,18 +378,20 @@ def deconvolve(measurement, psfs, iterations, dtype='f32', device=None, plan=Non
 
 
 def deconvolve_until(measurement, psfs, max_iterations, rule='discrepancy', threshold=1.0, check_every=1, dtype='f32',
-                     device=None, plan=None, acceleration=None):
+                     device=None, plan=None, acceleration=None, tv_lambda=None, tv_epsilon=0.1):
     """Richardson-Lucy from ones with a stopping rule per frame (DeconvPlan.iterate_until): measurement (B, V, ny, nx).
     rule 'discrepancy': a frame stops at the first check with 2 D / N <= threshold, D its Poisson I-divergence and N its
     V * ny * nx pixels; 'relative': at the first check with D_prev - D <= threshold * D_prev.  Checks every `check_every`
     iterations, `max_iterations` at most.  Returns (estimates (B, ny, nx), info) with info['iterations'], info['divergence'],
-    info['stopped']: (B,) arrays for the kept estimates."""
+    info['stopped']: (B,) arrays for the kept estimates.  tv_lambda, tv_epsilon: as for deconvolve."""
+    _lib.tv_params(tv_lambda, tv_epsilon)
     measurement = np.asarray(measurement, dtype=np.float64)
     B, V, ny, nx = measurement.shape
     if plan is None:
         plan = DeconvPlan(psfs, B, ny, nx, dtype=dtype,
                           device=_DEFAULT_DEVICE if device is None else device)
     plan.set_acceleration(acceleration)
+    plan.set_tv(tv_lambda, tv_epsilon)
     plan.set_measurement(measurement)
     plan.reset_estimate()
     info = plan.iterate_until(max_iterations, rule=rule, threshold=threshold, check_every=check_every)

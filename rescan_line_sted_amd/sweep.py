@@ -25,7 +25,7 @@ import hashlib
 import numpy as np
 
 from . import sharding
-from ._lib import DTYPES, RL_F32, RNG_PHILOX, Context, DeconvPlan, accel_mode, check, lib, ptr
+from ._lib import DTYPES, RL_F32, RNG_PHILOX, Context, DeconvPlan, accel_mode, check, lib, ptr, tv_params
 
 
 def make_tasks(objects, psf_sets, seeds):
@@ -77,15 +77,18 @@ def _psf_set_key(psfs):
     return val
 
 
-def plan_for(psfs, batch, shape, dtype='f32', device=0, stream=0, acceleration=None):
+def plan_for(psfs, batch, shape, dtype='f32', device=0, stream=0, acceleration=None, tv_lambda=None, tv_epsilon=0.1):
     """The plan of a (PSF set, image shape, batch): built on first use, kept for the next sweep (the reference builds its
     Deconvolvers once per figure too, line_sted_figure_2.py:39-45).  `stream`: which of the device's contexts it lives on;
-    `acceleration`: None or 'biggs-andrews' (DeconvPlan) -- part of the key, a plain and an accelerated sweep keep plans of their own."""
+    `acceleration`: None or 'biggs-andrews' (DeconvPlan) -- part of the key, a plain and an accelerated sweep keep plans of their own;
+    `tv_lambda`, `tv_epsilon`: the total-variation regulariser (DeconvPlan.set_tv; None: off) -- part of the key as well."""
     digest, views = _psf_set_key(psfs)
-    key = (digest, len(views), int(batch), tuple(shape), dtype, device, stream, accel_mode(acceleration))
+    tv = tv_params(tv_lambda, tv_epsilon)
+    key = (digest, len(views), int(batch), tuple(shape), dtype, device, stream, accel_mode(acceleration), tv if tv[0] else None)
     plan = _plans.pop(key, None)
     if plan is None:
-        plan = DeconvPlan(views, batch, shape[0], shape[1], dtype=dtype, device=device, stream=stream, acceleration=acceleration)
+        plan = DeconvPlan(views, batch, shape[0], shape[1], dtype=dtype, device=device, stream=stream, acceleration=acceleration,
+                          tv_lambda=tv_lambda, tv_epsilon=tv_epsilon)
         while len(_plans) >= PLAN_CACHE_MAX:
             _plans.pop(next(iter(_plans)))          # the least recently used one
     _plans[key] = plan
@@ -148,10 +151,11 @@ SWEEP_STREAMS = 4      # contexts of one GPU the groups of a sweep are dealt to 
 
 
 def run_tasks_device(tasks, objects, psf_sets, iterations, total_brightness=5e10, dtype='f32', device=0,
-                     max_frames_per_plan=256, streams=SWEEP_STREAMS, timing=None, acceleration=None):
+                     max_frames_per_plan=256, streams=SWEEP_STREAMS, timing=None, acceleration=None, tv_lambda=None, tv_epsilon=0.1):
     """Enqueue the tasks on one GPU (group by group, `rl_batch_submit`), synchronise once; returns their DeviceResults.
     timing (dict, optional): receives 'enqueue_s', the host's share (staging + launches) before the one synchronisation.
-    acceleration: None or 'biggs-andrews' (DeconvPlan): every task's iterations from ones, with a history of its own."""
+    acceleration: None or 'biggs-andrews' (DeconvPlan): every task's iterations from ones, with a history of its own.
+    tv_lambda, tv_epsilon: the total-variation regulariser of every task's iterations (DeconvPlan.set_tv; None: off)."""
     import time
     t_start = time.perf_counter()
     ids = object_ids(objects)
@@ -168,7 +172,7 @@ def run_tasks_device(tasks, objects, psf_sets, iterations, total_brightness=5e10
             # the caller's tasks are grouped; in general every task is submitted to its own address)
             stream = n_sub % max(1, streams)
             n_sub += 1
-            plan = plan_for(psf_sets[p], len(part), shape, dtype, device, stream, acceleration)
+            plan = plan_for(psf_sets[p], len(part), shape, dtype, device, stream, acceleration, tv_lambda, tv_epsilon)
             used.add(stream)
             frames = [np.ascontiguousarray(np.asarray(objects[tasks[i][0]], dtype=np.float64).reshape(shape)) for i in part]
             runs = _consecutive_runs(part, res)
@@ -199,11 +203,11 @@ def sort_by_group(tasks, objects):
 
 
 def run_tasks(tasks, objects, psf_sets, iterations, total_brightness=5e10, dtype='f32', device=0,
-              max_frames_per_plan=256, acceleration=None):
+              max_frames_per_plan=256, acceleration=None, tv_lambda=None, tv_epsilon=0.1):
     """Run tasks on one GPU.  Returns a list of (ny, nx) estimates in task order."""
     order = sort_by_group(tasks, objects)
     res = run_tasks_device([tasks[i] for i in order], objects, psf_sets, iterations, total_brightness, dtype, device,
-                           max_frames_per_plan, acceleration=acceleration)
+                           max_frames_per_plan, acceleration=acceleration, tv_lambda=tv_lambda, tv_epsilon=tv_epsilon)
     est = res.download()
     res.free()
     out = [None] * len(tasks)
@@ -235,14 +239,14 @@ def shard_sweep(tasks, objects, psf_sets, iterations, world):
 
 
 def figure_2_sweep(objects, psf_sets, seeds, iterations, total_brightness=5e10, dtype='f32',
-                   device=0, comm=None, info=None, acceleration=None):
+                   device=0, comm=None, info=None, acceleration=None, tv_lambda=None, tv_epsilon=0.1):
     """The sweep, sharded over the ranks of `comm` (sharding.RcclComm, or anything with its
     interface) when given.  Returns (tasks, estimates) on rank 0 and (tasks, None) elsewhere;
     estimates is an array (n_tasks, ny, nx) when all objects share a shape, otherwise a list of
     (ny, nx) arrays in task order.  The one gather carries the ranks' estimates unpadded: from device buffer to device
     buffer in the plans' arithmetic type (`comm.gather_device`), or -- a stand-in communicator without it -- as flat host
     arrays.  info (dict, optional) receives the partition's statistics.  acceleration: None (the reference's iteration) or
-    'biggs-andrews' (DeconvPlan.set_acceleration)."""
+    'biggs-andrews' (DeconvPlan.set_acceleration); tv_lambda, tv_epsilon: the total-variation regulariser (DeconvPlan.set_tv; None: off)."""
     tasks = make_tasks(objects, psf_sets, seeds)
     world = comm.world if comm is not None else 1
     rank = comm.rank if comm is not None else 0
@@ -253,14 +257,15 @@ def figure_2_sweep(objects, psf_sets, seeds, iterations, total_brightness=5e10, 
     if info is not None:
         info.update(sharding.partition_stats(shards, costs, task_groups(tasks, objects)))
     if comm is not None and hasattr(comm, 'gather_device'):
-        res = run_tasks_device(mine, objects, psf_sets, iterations, total_brightness, dtype, device, acceleration=acceleration)
+        res = run_tasks_device(mine, objects, psf_sets, iterations, total_brightness, dtype, device, acceleration=acceleration,
+                               tv_lambda=tv_lambda, tv_epsilon=tv_epsilon)
         if info is not None:
             info['unresolved_predictions_this_rank'] = unresolved_total(reset=True)
         flat = comm.gather_device(res, pix, 0)       # root: host float64, rank-major; others: None
         res.free()
     else:
         local = run_tasks(mine, objects, psf_sets, iterations, total_brightness, dtype, device,
-                          acceleration=acceleration) if mine else []
+                          acceleration=acceleration, tv_lambda=tv_lambda, tv_epsilon=tv_epsilon) if mine else []
         flat = np.concatenate([np.asarray(e, dtype=np.float64).ravel() for e in local]) if local else np.zeros(0)
         if comm is not None:
             flat = comm.gather(flat, pix, 0)
