@@ -399,6 +399,36 @@ int rl_fft2_magnitude(rl_ctx* ctx, const double* x, int n_img, int ny, int nx, d
 int rl_spline_sample(rl_ctx* ctx, const double* image, int ny, int nx, const double* ys, const double* xs, int n,
                      double* out);
 
+/* ---- ring statistics: per-ring sums over the 2-D spectra of device-resident image pairs ----
+ * What the figure-2 sweep is scored with (the ring RMS of fourier_error, line_sted_figure_2.py:353-355) and the Fourier ring
+ * correlation of two noise realisations, without downloading an image.
+ *
+ * For a pair of real images a, b [ny][nx] and a real scale s: A = fft2(a), B = fft2(s * b), unnormalised DFTs on the exact image
+ * grid (numpy.fft.fft2), every value widened to float64 before any arithmetic.
+ * Signed frequency of bin (ky, kx): sy = ky <= ny / 2 ? ky : ky - ny, sx likewise.  RING of the bin, in exact integer arithmetic,
+ * with q = (sy * nx)^2 + (sx * ny)^2, M = ny * nx, R = n_rings:
+ *     ring = isqrt(4 * R^2 * q) / M          (integer division) = floor(2 R * radius / (0.5 cycles per pixel))
+ * Bins whose ring is >= R (the corners) belong to no ring.  The default R = rl_ring_count(ny, nx) = min(ny, nx) / 2; for an even
+ * square image that ring is floor(sqrt(sy^2 + sx^2)).  (A float formula does not reproduce this: at 160 x 160 float64 moves the eight
+ * bins (+-33, +-56), (+-56, +-33), whose radius is exactly 65, one ring down.)  The table is built on the host, once per (ny, nx, n_rings) and context.
+ * out[pair][ring][RL_RING_FIELDS], summed over ALL ny * nx bins of the ring:
+ *     0  number of bins      1  sum |A|^2      2  sum |B|^2      3  sum Re(A conj(B))      4  sum |A - B|^2
+ * in a fixed order (ring_kernels.hpp), no floating-point atomics: bit-identical from run to run, and a pair's result does not
+ * depend on the other pairs of the call.
+ *
+ * a_dev / b_dev: device buffers of this GPU (an rl_device_alloc buffer such as a sweep's results, a plan buffer from
+ * rl_deconv_device_ptr) of dtype a_dtype / b_dtype (RL_F32 / RL_F64, they may differ); image i of the pair starts at ELEMENT
+ * offset a_offsets[i] / b_offsets[i] (host arrays [n_pairs]; any offset >= 0, no alignment assumed).  a_dev and b_dev may be the
+ * same buffer, and many pairs may name the same image.  b_scale: host [n_pairs], or NULL for 1.
+ * Pairs are processed in chunks whose working memory stays under a fixed cap; the ring table and the workspace are kept in the
+ * context and freed with it.  Synchronises the context's stream.
+ * RL_ERR_INVALID: a NULL pointer, n_pairs < 1, ny or nx < 2, n_rings < 1, a dtype that is neither, a negative offset;
+ * RL_ERR_UNSUPPORTED: ny or nx > 4096 (the transform is the O(n^3) matrix form), n_rings > 16384.                        */
+#define RL_RING_FIELDS 5
+int rl_ring_count(int ny, int nx);
+int rl_ring_stats(rl_ctx* ctx, const void* a_dev, int a_dtype, const int64_t* a_offsets, const void* b_dev, int b_dtype,
+                  const int64_t* b_offsets, const double* b_scale, int n_pairs, int ny, int nx, int n_rings, double* out);
+
 /* ---- line_sted_figure_3.py: the scan-position-by-scan-position imaging simulator (:76-273) ----
  * rl_rotate_image: `rotate` (:382-391) for one [ny][nx] plane -- scipy.ndimage.rotate(order 3,
  * mode 'nearest', reshape=False) about the centre; clip != 0 clips to [0, 1.1 * max(in)].  Host in / out. */

@@ -115,6 +115,8 @@ PROTOTYPES = {
     'rl_psf_report_batch': (_i, [_vp, _i, _dp, _dp, _c.POINTER(_dp)]),
     'rl_fft2_magnitude': (_i, [_vp, _dp, _i, _i, _i, _c.c_double, _i, _dp]),
     'rl_spline_sample': (_i, [_vp, _dp, _i, _i, _dp, _dp, _i, _dp]),
+    'rl_ring_count': (_i, [_i, _i]),
+    'rl_ring_stats': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _vp, _i, _c.POINTER(_c.c_int64), _dp, _i, _i, _i, _i, _dp]),
 }
 
 

@@ -61,6 +61,25 @@ struct rl_ctx {
         return RL_OK;
     }
 
+    // rl_ring_stats (ring_api.cpp): the device ring tables, one per (ny, nx, n_rings), and a grow-only workspace; freed with the
+    // context (rl_ctx_destroy deletes it with its device current)
+    struct RingTable {
+        int* row_ptr = nullptr;   // [n_rings + 1]
+        int* bins = nullptr;      // [row_ptr[n_rings]]
+    };
+    struct RingCache {
+        std::map<std::pair<std::pair<int, int>, int>, RingTable> tables;
+        void* work = nullptr;
+        size_t work_bytes = 0;
+        ~RingCache() {
+            for (auto& kv : tables) {
+                if (kv.second.row_ptr) (void)hipFree(kv.second.row_ptr);
+                if (kv.second.bins) (void)hipFree(kv.second.bins);
+            }
+            if (work) (void)hipFree(work);
+        }
+    } ring;
+
     int device = 0;
     hipStream_t stream = nullptr;
     std::map<std::pair<int, int>, void*> tw;   // (L, dtype) -> device table

@@ -1,0 +1,115 @@
+// ring_api.cpp -- C ABI of the per-ring spectrum statistics of device-resident image pairs (include/rlsted.h, rl_ring_stats): the
+// host side -- the ring table (built once per (ny, nx, n_rings) and context), the chunking under the workspace cap, the launches
+// of ring_kernels.hip.  Only offsets and scales go up and n_pairs * n_rings * RL_RING_FIELDS doubles come down.
+#include <algorithm>
+#include <vector>
+
+#include "ctx.hpp"
+#include "ring_kernels.hpp"
+
+using namespace rl;
+
+namespace {
+// T and F of the pairs in flight (2 * 16 * ny * nx bytes per pair) stay below this; a single pair larger than it runs alone
+constexpr size_t kRingWorkBytes = (size_t)256 << 20;
+constexpr int kRingMaxPairsPerLaunch = 65535;   // grid.z
+constexpr int kRingMaxRings = 4 * kRingMaxN;
+
+size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+int ring_table(rl_ctx* ctx, int ny, int nx, int n_rings, rl_ctx::RingTable* out) {
+    const auto key = std::make_pair(std::make_pair(ny, nx), n_rings);
+    auto it = ctx->ring.tables.find(key);
+    if (it != ctx->ring.tables.end()) {
+        *out = it->second;
+        return RL_OK;
+    }
+    std::vector<int> row_ptr, bins;
+    ring_build_table(ny, nx, n_rings, row_ptr, bins);
+    rl_ctx::RingTable t;
+    HIP_TRY(hipMalloc((void**)&t.row_ptr, row_ptr.size() * sizeof(int)));
+    hipError_t e = hipMalloc((void**)&t.bins, std::max<size_t>(bins.size(), 1) * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(t.row_ptr, row_ptr.data(), row_ptr.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !bins.empty()) e = hipMemcpy(t.bins, bins.data(), bins.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(t.row_ptr);
+        if (t.bins) (void)hipFree(t.bins);
+        return fail(RL_ERR_HIP, std::string("ring table: ") + hipGetErrorString(e));
+    }
+    ctx->ring.tables[key] = t;
+    *out = t;
+    return RL_OK;
+}
+
+int ring_workspace(rl_ctx* ctx, size_t bytes, char** out) {
+    if (bytes > ctx->ring.work_bytes) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (ctx->ring.work) (void)hipFree(ctx->ring.work);
+        ctx->ring.work = nullptr;
+        ctx->ring.work_bytes = 0;
+        HIP_TRY(hipMalloc(&ctx->ring.work, bytes));
+        ctx->ring.work_bytes = bytes;
+    }
+    *out = (char*)ctx->ring.work;
+    return RL_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rl_ring_count(int ny, int nx) { return std::min(ny, nx) / 2; }
+
+int rl_ring_stats(rl_ctx* ctx, const void* a_dev, int a_dtype, const int64_t* a_offsets, const void* b_dev, int b_dtype,
+                  const int64_t* b_offsets, const double* b_scale, int n_pairs, int ny, int nx, int n_rings, double* out) {
+    if (!ctx || !a_dev || !a_offsets || !b_dev || !b_offsets || !out) return fail(RL_ERR_INVALID, "NULL argument");
+    if (n_pairs < 1) return fail(RL_ERR_INVALID, "n_pairs < 1");
+    if (ny < 2 || nx < 2) return fail(RL_ERR_INVALID, "ny and nx must be at least 2");
+    if (n_rings < 1) return fail(RL_ERR_INVALID, "n_rings < 1");
+    if ((a_dtype != RL_F32 && a_dtype != RL_F64) || (b_dtype != RL_F32 && b_dtype != RL_F64))
+        return fail(RL_ERR_INVALID, "dtype must be RL_F32 or RL_F64");
+    if (ny > kRingMaxN || nx > kRingMaxN) return fail(RL_ERR_UNSUPPORTED, "ring statistics cover images up to 4096 x 4096");
+    if (n_rings > kRingMaxRings) return fail(RL_ERR_UNSUPPORTED, "more than 16384 rings");
+    for (int i = 0; i < n_pairs; ++i)
+        if (a_offsets[i] < 0 || b_offsets[i] < 0) return fail(RL_ERR_INVALID, "negative image offset");
+    HIP_TRY(hipSetDevice(ctx->device));
+
+    void *wx = nullptr, *wy = nullptr;
+    RL_TRY(ctx->plain_twiddles(nx, &wx));
+    RL_TRY(ctx->plain_twiddles(ny, &wy));
+    rl_ctx::RingTable table;
+    RL_TRY(ring_table(ctx, ny, nx, n_rings, &table));
+
+    const size_t img = (size_t)ny * nx * sizeof(RingC);
+    const int chunk = (int)std::min<size_t>({(size_t)n_pairs, (size_t)kRingMaxPairsPerLaunch, std::max<size_t>(1, kRingWorkBytes / (2 * img))});
+    const size_t meta = round_up((size_t)n_pairs * 8, 256), per_out = (size_t)n_rings * kRingFields * sizeof(double);
+    const size_t res = round_up((size_t)chunk * per_out, 256);
+    char* base = nullptr;
+    RL_TRY(ring_workspace(ctx, 3 * meta + res + 2 * (size_t)chunk * img, &base));
+    int64_t* d_aoff = (int64_t*)base;
+    int64_t* d_boff = (int64_t*)(base + meta);
+    double* d_scale = (double*)(base + 2 * meta);
+    double* d_out = (double*)(base + 3 * meta);
+    char* d_t = base + 3 * meta + res;
+    char* d_f = d_t + (size_t)chunk * img;
+
+    std::vector<double> ones;
+    if (!b_scale) {
+        ones.assign((size_t)n_pairs, 1.0);
+        b_scale = ones.data();
+    }
+    // (pageable sources: these copies have left the host arrays when they return)
+    HIP_TRY(hipMemcpyAsync(d_aoff, a_offsets, (size_t)n_pairs * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_boff, b_offsets, (size_t)n_pairs * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_scale, b_scale, (size_t)n_pairs * 8, hipMemcpyHostToDevice, ctx->stream));
+    for (int p0 = 0; p0 < n_pairs; p0 += chunk) {
+        const int np = std::min(chunk, n_pairs - p0);
+        HIP_TRY(ring_rows(a_dtype, b_dtype, a_dev, b_dev, d_aoff + p0, d_boff + p0, d_scale + p0, wx, d_t, ny, nx, np, ctx->stream));
+        HIP_TRY(ring_cols(d_t, wy, d_f, ny, nx, np, ctx->stream));
+        HIP_TRY(ring_reduce(d_f, table.row_ptr, table.bins, d_out, ny, nx, n_rings, np, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(out + (size_t)p0 * n_rings * kRingFields, d_out, (size_t)np * per_out, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return RL_OK;
+}
+
+}  // extern "C"

@@ -6,11 +6,20 @@ Deconvolver.record_iteration, on the device (csrc/quality_kernels.hip, float64):
   map_coordinates(image, coordinates)         scipy defaults, as used at :381-384
   error_vs_spatial_frequency(...)             line_sted_figure_2.py:362-390
 
+and the ring statistics of image pairs (csrc/ring_kernels.hip; the definition: include/rlsted.h, rl_ring_stats) with what is
+read off them -- no counterpart in the reference:
+
+  ring_stats(a, b, n_rings, scale)            [..., R, 5]: bins, sum |A|^2, sum |B|^2, sum Re(A conj B), sum |A - B|^2 per ring
+  frc(a, b), frc_resolution(freq, curve)      Fourier ring correlation of two noise realisations, and where it crosses 1/7
+  radial_fourier_error(estimate, true_object) the ring RMS of fourier_error
+
 ("ref2:NNN" = line numbers in figure_generation/line_sted_figure_2.py.)
 """
+import ctypes
+
 import numpy as np
 
-from ._lib import lib, check, ptr, as_f64
+from ._lib import DTYPES, lib, check, ptr, as_f64
 from .psf import _ctx, gaussian_filter
 
 
@@ -77,3 +86,116 @@ def error_vs_spatial_frequency(estimate, true_object, angle_degrees=0.0, radius=
     if not smooth:
         return z
     return gaussian_filter(z.reshape(1, 1, -1), (0, 0, samples / 80))[0, 0]     # ref2:387
+
+
+# ------------------------------------------------------------------ ring statistics
+RING_FIELDS = 5
+
+
+def ring_count(ny, nx):
+    """The default number of rings of an (ny, nx) image: min(ny, nx) // 2."""
+    return int(lib.rl_ring_count(int(ny), int(nx)))
+
+
+def ring_stats_device(ctx, a_dev, a_dtype, a_offsets, b_dev, b_dtype, b_offsets, shape, scale=None, n_rings=None):
+    """rl_ring_stats on device buffers: image pair i = (a_dev + a_offsets[i], b_dev + b_offsets[i]), offsets in elements, all
+    images of `shape`; dtypes 'f32' / 'f64'; scale None or one value per pair.  Returns [n_pairs][R][5] float64."""
+    ny, nx = int(shape[0]), int(shape[1])
+    R = ring_count(ny, nx) if n_rings is None else int(n_rings)
+    a_off = np.ascontiguousarray(a_offsets, dtype=np.int64).ravel()
+    b_off = np.ascontiguousarray(b_offsets, dtype=np.int64).ravel()
+    if a_off.size != b_off.size:
+        raise ValueError('one offset per pair in both buffers; got %d and %d' % (a_off.size, b_off.size))
+    sc = None
+    if scale is not None:
+        sc = as_f64(np.broadcast_to(np.asarray(scale, dtype=np.float64), a_off.shape))
+    out = np.empty((a_off.size, max(R, 0), RING_FIELDS))
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    check(lib.rl_ring_stats(ctx.handle, a_dev, DTYPES[a_dtype], a_off.ctypes.data_as(i64p), b_dev, DTYPES[b_dtype],
+                            b_off.ctypes.data_as(i64p), ptr(sc) if sc is not None else None, int(a_off.size), ny, nx, R, ptr(out)))
+    return out
+
+
+def _stack(x, name):
+    x = as_f64(x)
+    if x.ndim == 2:
+        return x[None], True
+    if x.ndim != 3:
+        raise ValueError('%s: expected a 2-D image or a 3-D stack of images' % name)
+    return x, False
+
+
+def ring_stats(a, b, n_rings=None, scale=None):
+    """The ring statistics of host images: a, b (ny, nx) or stacks (n, ny, nx); a single image on either side pairs with every image
+    of the other.  scale: None (1), a number, or one per pair -- b is multiplied by it.  Returns (R, 5) for two single images, else
+    (n, R, 5).  The images are uploaded and go through the same entry point as device-resident ones."""
+    a, one_a = _stack(a, 'a')
+    b, one_b = _stack(b, 'b')
+    if a.shape[1:] != b.shape[1:]:
+        raise ValueError('a and b differ in image shape: %s, %s' % (a.shape[1:], b.shape[1:]))
+    n = max(a.shape[0], b.shape[0])
+    if a.shape[0] not in (1, n) or b.shape[0] not in (1, n):
+        raise ValueError('stacks of %d and %d images do not pair up' % (a.shape[0], b.shape[0]))
+    from .sweep import DeviceResults                     # (sweep imports this module)
+    da, db = DeviceResults.from_host(list(a), 'f64', _ctx().device), DeviceResults.from_host(list(b), 'f64', _ctx().device)
+    try:
+        out = da.ring_stats(np.arange(n) if a.shape[0] == n else np.zeros(n, dtype=np.int64), truth=db,
+                            truth_index=np.arange(n) if b.shape[0] == n else np.zeros(n, dtype=np.int64), scale=scale, n_rings=n_rings)
+    finally:
+        da.free()
+        db.free()
+    return out[0] if one_a and one_b else out
+
+
+def ring_frequencies(n_rings):
+    """Cycles per pixel at the ring centres: ring r covers [r, r + 1) * 0.5 / R."""
+    return (np.arange(int(n_rings)) + 0.5) * 0.5 / int(n_rings)
+
+
+def frc_from_stats(stats):
+    """f3 / sqrt(f1 f2) along the last-but-one axis of [..., R, 5]; nan where a ring is empty or a denominator is 0."""
+    stats = np.asarray(stats, dtype=np.float64)
+    den = np.sqrt(stats[..., 1] * stats[..., 2])
+    ok = (stats[..., 0] > 0) & (den > 0)
+    return np.where(ok, stats[..., 3] / np.where(ok, den, 1.0), np.nan)
+
+
+def radial_error_from_stats(stats, shape):
+    """sqrt(f4 / f0) / (ny nx): the RMS over each ring of |fft2(estimate) - fft2(scaled truth)| / (ny nx); nan for an empty ring."""
+    stats = np.asarray(stats, dtype=np.float64)
+    ok = stats[..., 0] > 0
+    return np.where(ok, np.sqrt(stats[..., 4] / np.where(ok, stats[..., 0], 1.0)) / (int(shape[0]) * int(shape[1])), np.nan)
+
+
+def frc(a, b, n_rings=None):
+    """Fourier ring correlation of two images (two noise realisations of one object).  Returns (frequencies in cycles/pixel at the
+    ring centres, curve)."""
+    st = ring_stats(a, b, n_rings)
+    return ring_frequencies(st.shape[-2]), frc_from_stats(st)
+
+
+def frc_resolution(freq, curve, threshold=1.0 / 7.0):
+    """The period in pixels, 1 / frequency, at which the curve first falls below `threshold`: linearly interpolated between the last
+    ring at or above it and the first ring below (nan rings are passed over); the first ring's own frequency if the curve starts
+    below; inf if it never crosses."""
+    freq = np.asarray(freq, dtype=np.float64)
+    curve = np.asarray(curve, dtype=np.float64)
+    prev = None
+    for f, c in zip(freq, curve):
+        if np.isnan(c):
+            continue
+        if c < threshold:
+            if prev is None:
+                return 1.0 / f
+            f0, c0 = prev
+            return 1.0 / (f0 + (c0 - threshold) / (c0 - c) * (f - f0))
+        prev = (f, c)
+    return float('inf')
+
+
+def radial_fourier_error(estimate, true_object, n_rings=None):
+    """The ring RMS of fourier_error(estimate, true_object) (ref2:353-355): sqrt(mean over the ring of fourier_error^2).  Returns
+    (frequencies in cycles/pixel at the ring centres, profile)."""
+    est = as_f64(estimate)
+    st = ring_stats(est, true_object, n_rings)
+    return ring_frequencies(st.shape[-2]), radial_error_from_stats(st, est.shape[-2:])

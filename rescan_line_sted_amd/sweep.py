@@ -24,7 +24,7 @@ import hashlib
 
 import numpy as np
 
-from . import sharding
+from . import quality, sharding
 from ._lib import DTYPES, RL_F32, RNG_PHILOX, Context, DeconvPlan, accel_mode, check, lib, ptr, tv_params
 
 
@@ -130,12 +130,98 @@ class DeviceResults:
         check(lib.rl_device_download(self.ctx.handle, self.dev, DTYPES[self.dtype], self.n, ptr(flat)))
         return split_flat(flat, self.shapes)
 
+    @classmethod
+    def from_host(cls, images, dtype='f64', device=0):
+        """A buffer holding host images (true objects, say), uploaded once."""
+        images = [np.asarray(im, dtype=np.float64) for im in images]
+        out = cls([im.shape[-2:] for im in images], dtype, device)
+        flat = np.concatenate([im.ravel() for im in images]) if images else np.zeros(0)
+        check(lib.rl_device_upload(out.ctx.handle, out.dev, DTYPES[dtype], out.n, ptr(np.ascontiguousarray(flat))))
+        return out
+
+    def ring_stats(self, a_idx, b_idx=None, truth=None, truth_index=None, scale=None, n_rings=None):
+        """Ring statistics (quality.ring_stats, include/rlsted.h rl_ring_stats) of image pairs without a download: images `a_idx`
+        of this buffer against images `b_idx` of the same buffer (two seeds of a sweep), or against images `truth_index` (one
+        index, or one per pair) of `truth`, another DeviceResults of this GPU (DeviceResults.from_host of the true objects).
+        scale: None, a number or one per pair, multiplied into the b side.  All images of a call share one shape (ValueError
+        otherwise).  Returns [len(a_idx)][R][5] float64; synchronises this buffer's context, so whatever wrote the images must have
+        been synchronised (run_tasks_device has)."""
+        a_idx = [int(i) for i in np.atleast_1d(a_idx)]
+        if (b_idx is None) == (truth is None):
+            raise ValueError('give either b_idx or truth')
+        other = self if truth is None else truth
+        if truth is not None:
+            if truth.ctx.device != self.ctx.device:
+                raise ValueError('truth lives on another device')
+            b_idx = np.zeros(len(a_idx), dtype=np.int64) if truth_index is None else truth_index
+        b_idx = [int(i) for i in np.broadcast_to(np.atleast_1d(b_idx), (len(a_idx),))]
+        if not a_idx:
+            raise ValueError('no pairs')
+        shape = self.shapes[a_idx[0]]
+        if any(self.shapes[i] != shape for i in a_idx) or any(other.shapes[i] != shape for i in b_idx):
+            raise ValueError('the images of one ring_stats call must share one shape')
+        return quality.ring_stats_device(self.ctx, self.dev, self.dtype, self.offsets[a_idx], other.dev, other.dtype,
+                                         other.offsets[b_idx], shape, scale, n_rings)
+
     def free(self):
         if getattr(self, 'dev', None) is not None and self.dev.value and lib is not None:    # (lib: gone at interpreter shutdown)
             lib.rl_device_free(self.ctx.handle, self.dev)
             self.dev = ctypes.c_void_p()
 
     __del__ = free
+
+
+def _by_shape(shapes):
+    groups = {}
+    for i, s in enumerate(shapes):
+        groups.setdefault(tuple(s), []).append(i)
+    return groups
+
+
+def _pack_stats(per_task):
+    """An array [n][R][5] when every task has the same number of rings, otherwise the list."""
+    return np.stack(per_task) if per_task and len({s.shape for s in per_task}) == 1 else per_task
+
+
+def score_tasks(res, tasks, objects, total_brightness=5e10, n_rings=None):
+    """The ring statistics of every task's estimate in `res` (the DeviceResults of `tasks`) against its true object scaled to the
+    simulated brightness, scale = total_brightness / object.sum() (create_data_from_object, line_sted_tools.py:505-506), on the
+    device: each distinct object is uploaded once as float64, one rl_ring_stats call per image shape.  Returns [n_tasks][R][5]
+    (fields: quality.ring_stats; quality.radial_error_from_stats turns field 4 into the ring RMS of the reference's fourier_error)
+    -- a list of per-task arrays when shapes with different numbers of rings are mixed."""
+    names = sorted({o for o, _, _ in tasks})
+    where = {n: i for i, n in enumerate(names)}
+    imgs = [np.asarray(objects[n], dtype=np.float64).reshape(np.shape(objects[n])[-2:]) for n in names]
+    scales = {n: float(total_brightness) / float(im.sum()) for n, im in zip(names, imgs)}
+    truths = DeviceResults.from_host(imgs, 'f64', res.ctx.device)
+    out = [None] * len(tasks)
+    try:
+        for shape, idxs in _by_shape([res.shapes[i] for i in range(len(tasks))]).items():
+            st = res.ring_stats(idxs, truth=truths, truth_index=[where[tasks[i][0]] for i in idxs],
+                                scale=[scales[tasks[i][0]] for i in idxs], n_rings=n_rings)
+            for k, i in enumerate(idxs):
+                out[i] = st[k]
+    finally:
+        truths.free()
+    return _pack_stats(out)
+
+
+def frc_between_seeds(res, tasks, seed_a, seed_b, n_rings=None):
+    """Fourier ring statistics between the two noise realisations `seed_a`, `seed_b` of every (object, PSF set) of `tasks` that
+    has both, straight from `res`: returns (keys, stats) -- keys the (object, PSF set) pairs in task order of seed_a, stats
+    [len(keys)][R][5] (a list when ring counts differ); quality.frc_from_stats(stats) is the FRC curve."""
+    at = {t: i for i, t in enumerate(tasks)}
+    keys = [(o, p) for o, p, s in tasks if s == int(seed_a) and (o, p, int(seed_b)) in at]
+    if not keys:
+        raise ValueError('no (object, PSF set) has both seeds %r and %r' % (seed_a, seed_b))
+    ia = [at[(o, p, int(seed_a))] for o, p in keys]
+    ib = [at[(o, p, int(seed_b))] for o, p in keys]
+    out = [None] * len(keys)
+    for shape, ks in _by_shape([res.shapes[i] for i in ia]).items():
+        st = res.ring_stats([ia[k] for k in ks], b_idx=[ib[k] for k in ks], n_rings=n_rings)
+        for j, k in enumerate(ks):
+            out[k] = st[j]
+    return keys, _pack_stats(out)
 
 
 def split_flat(flat, shapes):
@@ -216,6 +302,23 @@ def run_tasks(tasks, objects, psf_sets, iterations, total_brightness=5e10, dtype
     return out
 
 
+def run_and_score_tasks(tasks, objects, psf_sets, iterations, total_brightness=5e10, dtype='f32', device=0, n_rings=None,
+                        acceleration=None, tv_lambda=None, tv_epsilon=0.1):
+    """run_tasks, with every estimate scored on the device before the one download (score_tasks).  Returns (estimates, scores):
+    two lists in task order, scores[i] of shape (R_i, 5)."""
+    order = sort_by_group(tasks, objects)
+    sorted_tasks = [tasks[i] for i in order]
+    res = run_tasks_device(sorted_tasks, objects, psf_sets, iterations, total_brightness, dtype, device,
+                           acceleration=acceleration, tv_lambda=tv_lambda, tv_epsilon=tv_epsilon)
+    sc = score_tasks(res, sorted_tasks, objects, total_brightness, n_rings)
+    est = res.download()
+    res.free()
+    out, scores = [None] * len(tasks), [None] * len(tasks)
+    for k, i in enumerate(order):
+        out[i], scores[i] = est[k], np.asarray(sc[k])
+    return out, scores
+
+
 def pad_stack(images, shape):
     """Stack 2-D images of different sizes into one (n, shape[0], shape[1]) array, top-left aligned
     and zero filled."""
@@ -239,14 +342,17 @@ def shard_sweep(tasks, objects, psf_sets, iterations, world):
 
 
 def figure_2_sweep(objects, psf_sets, seeds, iterations, total_brightness=5e10, dtype='f32',
-                   device=0, comm=None, info=None, acceleration=None, tv_lambda=None, tv_epsilon=0.1):
+                   device=0, comm=None, info=None, acceleration=None, tv_lambda=None, tv_epsilon=0.1, scores=False, n_rings=None):
     """The sweep, sharded over the ranks of `comm` (sharding.RcclComm, or anything with its
     interface) when given.  Returns (tasks, estimates) on rank 0 and (tasks, None) elsewhere;
     estimates is an array (n_tasks, ny, nx) when all objects share a shape, otherwise a list of
     (ny, nx) arrays in task order.  The one gather carries the ranks' estimates unpadded: from device buffer to device
     buffer in the plans' arithmetic type (`comm.gather_device`), or -- a stand-in communicator without it -- as flat host
     arrays.  info (dict, optional) receives the partition's statistics.  acceleration: None (the reference's iteration) or
-    'biggs-andrews' (DeconvPlan.set_acceleration); tv_lambda, tv_epsilon: the total-variation regulariser (DeconvPlan.set_tv; None: off)."""
+    'biggs-andrews' (DeconvPlan.set_acceleration); tv_lambda, tv_epsilon: the total-variation regulariser (DeconvPlan.set_tv; None: off).
+    scores=True: every rank also scores its own shard on the device (score_tasks, `n_rings` rings) before the gather, the small
+    score arrays travel through `comm.gather`, and the function returns (tasks, estimates, scores) -- scores [n_tasks][R][5] in task
+    order (a list when ring counts differ) on rank 0, None elsewhere.  The estimates are those of scores=False."""
     tasks = make_tasks(objects, psf_sets, seeds)
     world = comm.world if comm is not None else 1
     rank = comm.rank if comm is not None else 0
@@ -256,26 +362,47 @@ def figure_2_sweep(objects, psf_sets, seeds, iterations, total_brightness=5e10, 
     pix = [sum(shapes[i][0] * shapes[i][1] for i in sh) for sh in shards]
     if info is not None:
         info.update(sharding.partition_stats(shards, costs, task_groups(tasks, objects)))
+    mine_scores = None
     if comm is not None and hasattr(comm, 'gather_device'):
         res = run_tasks_device(mine, objects, psf_sets, iterations, total_brightness, dtype, device, acceleration=acceleration,
                                tv_lambda=tv_lambda, tv_epsilon=tv_epsilon)
         if info is not None:
             info['unresolved_predictions_this_rank'] = unresolved_total(reset=True)
+        if scores and mine:
+            mine_scores = score_tasks(res, mine, objects, total_brightness, n_rings)
         flat = comm.gather_device(res, pix, 0)       # root: host float64, rank-major; others: None
         res.free()
     else:
-        local = run_tasks(mine, objects, psf_sets, iterations, total_brightness, dtype, device,
-                          acceleration=acceleration, tv_lambda=tv_lambda, tv_epsilon=tv_epsilon) if mine else []
+        if scores:
+            local, mine_scores = run_and_score_tasks(mine, objects, psf_sets, iterations, total_brightness, dtype, device, n_rings,
+                                                     acceleration=acceleration, tv_lambda=tv_lambda, tv_epsilon=tv_epsilon) if mine else ([], [])
+        else:
+            local = run_tasks(mine, objects, psf_sets, iterations, total_brightness, dtype, device,
+                              acceleration=acceleration, tv_lambda=tv_lambda, tv_epsilon=tv_epsilon) if mine else []
         flat = np.concatenate([np.asarray(e, dtype=np.float64).ravel() for e in local]) if local else np.zeros(0)
         if comm is not None:
             flat = comm.gather(flat, pix, 0)
-    if flat is None:
-        return tasks, None
     order = [i for sh in shards for i in sh]
+    all_scores = None
+    if scores:
+        rings = [quality.ring_count(*s) if n_rings is None else int(n_rings) for s in shapes]
+        have = mine_scores is not None and len(mine_scores)
+        sflat = np.concatenate([np.asarray(x, dtype=np.float64).ravel() for x in mine_scores]) if have else np.zeros(0)
+        if comm is not None:
+            sflat = comm.gather(sflat, [sum(rings[i] for i in sh) * quality.RING_FIELDS for sh in shards], 0)
+        if sflat is not None:
+            all_scores, o = [None] * len(tasks), 0
+            for i in order:
+                k = rings[i] * quality.RING_FIELDS
+                all_scores[i] = np.asarray(sflat[o:o + k]).reshape(rings[i], quality.RING_FIELDS)
+                o += k
+            all_scores = _pack_stats(all_scores)
+    if flat is None:
+        return (tasks, None, None) if scores else (tasks, None)
     parts = split_flat(np.asarray(flat), [shapes[i] for i in order])
     est = [None] * len(tasks)
     for k, i in enumerate(order):
         est[i] = parts[k]
     if len(set(shapes)) == 1:
-        return tasks, np.stack(est) if est else np.zeros((0,) + (shapes[0] if shapes else (0, 0)))
-    return tasks, est
+        est = np.stack(est) if est else np.zeros((0,) + (shapes[0] if shapes else (0, 0)))
+    return (tasks, est, all_scores) if scores else (tasks, est)

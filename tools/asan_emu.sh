@@ -3,7 +3,8 @@
 # bodies (tests/emu/emu.cpp: the FFT passes; tests/emu/long_emu.cpp, long_outer_emu.cpp: the row kernels of the long
 # lengths and the outer-decimation column kernels as the launcher instantiates them; tests/emu/sep_emu.cpp: the separable /
 # direct stencils, their tap tables and the box normaliser; tests/emu/tv_emu.cpp: the RL-TV weight and apply kernels, the LDS
-# tile allocated at exactly the kernel's element count -- the same templates the HIP kernels are made of, one OS thread
+# tile allocated at exactly the kernel's element count; tests/emu/ring_emu.cpp: the ring-statistics products and reduction, image
+# buffers of exactly the bytes the offsets reach -- the same templates the HIP kernels are made of, one OS thread
 # per GPU thread) and the
 # MINPACK restatement (csrc/gauss_fit.cpp) with AddressSanitizer + UndefinedBehaviorSanitizer and runs the tests that
 # drive them -- every index computation of the convolution kernels, of the stencils' three LDS regions (allocated at
@@ -32,6 +33,8 @@ echo "building $OUT/libsep_emu.so (sanitized)"
 g++ $FLAGS "$ROOT/tests/emu/sep_emu.cpp" -o "$OUT/libsep_emu.so"
 echo "building $OUT/libtv_emu.so (sanitized)"
 g++ $FLAGS "$ROOT/tests/emu/tv_emu.cpp" -o "$OUT/libtv_emu.so"
+echo "building $OUT/libring_emu.so (sanitized)"
+g++ $FLAGS "$ROOT/tests/emu/ring_emu.cpp" -o "$OUT/libring_emu.so"
 echo "building $OUT/libgaussfit.so (sanitized)"
 g++ $FLAGS -I"$ROOT/include" "$ROOT/rescan_line_sted_amd/csrc/gauss_fit.cpp" "$ROOT/tools/asan_gauss_fit_main.cpp" -o "$OUT/libgaussfit.so"
 fi
@@ -46,11 +49,12 @@ export RLSTED_LONG_EMU_LIB="$OUT/liblong_emu.so"
 export RLSTED_LONG_OUTER_EMU_LIB="$OUT/liblong_outer_emu.so"
 export RLSTED_SEP_EMU_LIB="$OUT/libsep_emu.so"
 export RLSTED_TV_EMU_LIB="$OUT/libtv_emu.so"
+export RLSTED_RING_EMU_LIB="$OUT/libring_emu.so"
 export RLSTED_GAUSSFIT_LIB="$OUT/libgaussfit.so"
 cd "$ROOT"
 if [ -n "${RLSTED_ASAN_TESTS:-}" ]; then        # e.g. RLSTED_ASAN_TESTS=tests/test_long_rows_cpu.py tools/asan_emu.sh -k 4608
     python -m pytest $RLSTED_ASAN_TESTS -x -q -p no:cacheprovider "$@"
 else
-    python -m pytest tests/test_emulated_kernels.py tests/test_kernel_variants.py tests/test_long_rows_cpu.py tests/test_sep_cpu.py tests/test_tv_cpu.py tests/test_poisson_spec.py tests/test_asan_gauss_fit.py -x -q -p no:cacheprovider "$@"
+    python -m pytest tests/test_emulated_kernels.py tests/test_kernel_variants.py tests/test_long_rows_cpu.py tests/test_sep_cpu.py tests/test_tv_cpu.py tests/test_ring_cpu.py tests/test_poisson_spec.py tests/test_asan_gauss_fit.py -x -q -p no:cacheprovider "$@"
 fi
 echo "sanitizer run clean"
