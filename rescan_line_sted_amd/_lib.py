@@ -84,6 +84,7 @@ PROTOTYPES = {
     'rl_host_alloc': (_i, [_c.c_size_t, _c.POINTER(_vp)]),
     'rl_host_free': (_i, [_vp]),
     'rl_deconv_strategy': (_i, [_vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)]),
+    'rl_deconv_object_classes': (_i, [_vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)]),
     'rl_deconv_unresolved': (_i, [_vp, _c.POINTER(_c.c_uint64), _i]),
     'rl_deconv_dims': (_i, [_vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)]),
     'rl_batch_run': (_i, [_vp, _vp, _i, _i, _i, _dp]),
@@ -268,6 +269,13 @@ class DeconvPlan:
         check(lib.rl_deconv_strategy(self.handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
         return {'separable': a.value == 1, 'direct_stencil': a.value == 2, 'real_psf_spectrum': bool(b.value),
                 'split_column_pass': bool(c.value), 'frame_pairs': bool(d.value)}
+
+    def object_classes(self):
+        """Frames that carry the same object are simulated once per slice (include/rlsted.h rl_deconv_object_classes):
+        the classes of the object as last set (0: unknown) and how many slices of the last cycle shared their simulation."""
+        a, b, c = _i(), _i(), _i()
+        check(lib.rl_deconv_object_classes(self.handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return {'classes': a.value, 'shared_slices': b.value, 'slices': c.value}
 
     def set_object(self, obj, total_brightness=None):
         obj = as_f64(obj).reshape(self.B, self.ny, self.nx)

@@ -62,9 +62,18 @@ struct PoissonKeys {
     unsigned image0, V;
     const unsigned long long* frame_seeds;   // [frames] or nullptr
     const unsigned* frame_ids;               // [frames] (with frame_seeds)
+    // [frames] or nullptr: frame f of the launch takes its rates from images rate_frame[f] * V + view of `noiseless` (frames that
+    // carry the same object share one simulated image, object_classes.hpp); the counters above stay the frame's own
+    const unsigned* rate_frame;
     __device__ __forceinline__ unsigned long long seed(unsigned img) const { return frame_seeds ? frame_seeds[img / V] : seed0; }
     __device__ __forceinline__ unsigned image(unsigned img) const {
         return frame_seeds ? frame_ids[img / V] * V + img % V : image0 + img;
+    }
+    template <typename T>
+    __device__ __forceinline__ T rate(const T* __restrict__ noiseless, unsigned i, unsigned n_pix) const {
+        if (!rate_frame) return noiseless[i];   // (uniform)
+        const unsigned img = i / n_pix, pix = i - img * n_pix;
+        return noiseless[((size_t)rate_frame[img / V] * V + img % V) * n_pix + pix];
     }
 };
 
@@ -92,7 +101,7 @@ __global__ void __launch_bounds__(256) k_poisson(const T* __restrict__ noiseless
         for (int e = 0; e < kPoissonE; ++e) {
             const unsigned i = tile0 + tid + 256u * (unsigned)e;
             if (i < total) {
-                const T lam_t = noiseless[i];
+                const T lam_t = keys.rate(noiseless, i, n_pix);
                 const double lam = (double)lam_t;
                 if (rng_kind != 1) {
                     noisy[i] = (T)(lam + 1e-9);
@@ -274,9 +283,9 @@ hipError_t aux_box_norm(int dtype, const double* integral_dev, void* out, int V,
 
 hipError_t aux_poisson(int dtype, const void* noiseless, void* noisy, unsigned n_pix, unsigned n_img, unsigned image0,
                        unsigned long long seed, int rng_kind, void* list_ws, hipStream_t s,
-                       const unsigned long long* frame_seeds, const unsigned* frame_ids, unsigned V) {
+                       const unsigned long long* frame_seeds, const unsigned* frame_ids, unsigned V, const unsigned* rate_frame) {
     (void)list_ws;   // (rounds 1-3: the global work list between the two launches)
-    const PoissonKeys keys{seed, image0, V ? V : 1u, frame_seeds, frame_ids};
+    const PoissonKeys keys{seed, image0, V ? V : 1u, frame_seeds, frame_ids, rate_frame};
     const size_t total = (size_t)n_pix * n_img;
     if (total >= 0xffffffffull - (size_t)kPoissonTile * 4096) return hipErrorInvalidValue;      // 32-bit pixel indices (and their tile stride)
     if (total == 0) return hipSuccess;
@@ -356,6 +365,24 @@ hipError_t aux_cast(int dtype_src, const void* src, int dtype_dst, void* dst, si
     const unsigned g = blocks_for(total, 256);
     if (dtype_src == DT_F32) k_cast<float, double><<<g, 256, 0, s>>>((const float*)src, (double*)dst, total);
     else k_cast<double, float><<<g, 256, 0, s>>>((const double*)src, (float*)dst, total);
+    return hipGetLastError();
+}
+
+// dst image j = src image list[j / V] * V + j % V   (images of n values; src and dst do not overlap)
+template <typename T>
+__global__ void k_gather_images(const T* __restrict__ src, T* __restrict__ dst, const unsigned* __restrict__ list, size_t n, size_t images,
+                                unsigned V) {
+    const size_t total = n * images;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t j = i / n;
+        dst[i] = src[((size_t)list[j / V] * V + j % V) * n + (i - j * n)];
+    }
+}
+hipError_t aux_gather_images(int dtype, const void* src, void* dst, const unsigned* list, size_t n, size_t images, unsigned V, hipStream_t s) {
+    if (images == 0 || n == 0) return hipSuccess;
+    const unsigned g = blocks_for(n * images, 256);
+    if (dtype == DT_F32) k_gather_images<float><<<g, 256, 0, s>>>((const float*)src, (float*)dst, list, n, images, V ? V : 1u);
+    else k_gather_images<double><<<g, 256, 0, s>>>((const double*)src, (double*)dst, list, n, images, V ? V : 1u);
     return hipGetLastError();
 }
 

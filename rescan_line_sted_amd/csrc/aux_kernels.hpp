@@ -49,9 +49,13 @@ hipError_t aux_psf_spectrum(int dtype, const double* psf_dev, const void* wx_dev
 size_t aux_poisson_workspace_bytes(size_t total_pixels);
 // frame_seeds / frame_ids (device arrays, one entry per frame of V views each) override seed / image0:
 // image (frame f, view v) then draws with seed frame_seeds[f] and image index frame_ids[f]*V + v.
+// rate_frame (device array, one entry per frame of the launch; nullptr: image i's rates are image i of `noiseless`): frame f's
+// rates are images rate_frame[f]*V + v of `noiseless` -- frames that carry the same object are simulated once.  The Philox
+// counters stay those of the frame itself, so every draw is the one it would be from a copy of the rates.
 hipError_t aux_poisson(int dtype, const void* noiseless, void* noisy, unsigned n_pix, unsigned n_img, unsigned image0,
                        unsigned long long seed, int rng_kind, void* list_ws, hipStream_t s,
-                       const unsigned long long* frame_seeds = nullptr, const unsigned* frame_ids = nullptr, unsigned V = 1);
+                       const unsigned long long* frame_seeds = nullptr, const unsigned* frame_ids = nullptr, unsigned V = 1,
+                       const unsigned* rate_frame = nullptr);
 // float64 stack [frames][n] (device) -> plan dtype, each frame scaled to sum target[f]
 // Every `sums` argument below is device memory of aux_sums_elems(frames) doubles: the frames' sums, then scratch for the partial
 // sums of large frames (aux_kernels.hip frame_sums).
@@ -71,6 +75,9 @@ hipError_t aux_scale_convert_indexed(int dtype, const double* src, const unsigne
 hipError_t aux_to_f64(int dtype, const void* src, double* dst, size_t total, hipStream_t s);
 // dst[i] = (dst type) src[i]: a plan buffer into a result buffer of another arithmetic type (same type: a device copy)
 hipError_t aux_cast(int dtype_src, const void* src, int dtype_dst, void* dst, size_t total, hipStream_t s);
+// dst image j = src image list[j / V] * V + j % V for `images` images of n values in the plan's dtype (list: device array; src
+// and dst must not overlap): the representatives' objects into their compact buffer, the shared rates back out to every frame
+hipError_t aux_gather_images(int dtype, const void* src, void* dst, const unsigned* list, size_t n, size_t images, unsigned V, hipStream_t s);
 // re[i] = z[i].re for n complex values of `dtype`; stats (device, 2 doubles) <- max |im|, max(|re|, |im|)
 hipError_t aux_split_real(int dtype, const void* z, size_t n, void* re, double* stats, hipStream_t s);
 // out [ny][nx] (plan dtype) = sum_v max(conv_same(ones, psf_v), 0) from the PSFs' float64 integral images

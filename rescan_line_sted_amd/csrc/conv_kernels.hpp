@@ -884,6 +884,9 @@ struct RowParams {
     // spectra are computed once per plan and every frame's ROW_RATIO reads them.
     int in_mod = 0;
     int sub_one = 0;        // ROW_RATIO stores rowFFT(ratio - 1), ROW_UPDATE multiplies by max(1 + acc / norm, 0): see rl_ratio
+    // ROW_UPDATE of the iteration that starts from estimate = 1 (ref:522): the estimate is taken as 1 instead of read -- nobody
+    // has to fill it first -- and 1 * x is x, so the values stored are those of an update that read a frame of ones.  Uniform.
+    int est_one = 0;
     float qscale = 1.0f;    // storage-precision study builds only (rl_spec_round)
     unsigned long long* unresolved = nullptr;   // ROW_RATIO: + the lanes that met a prediction <= 0 inside the image (rl_ratio); nullptr: not counted
 };
@@ -922,6 +925,11 @@ RL_HD void rowpass_body(const RowParams<T>& p, int tid, int bx, int by, cx<T>* l
     cx<T> pre[PREFETCH ? NB * R : 1];
     rl_stamp(sync, 0);
     auto request_operands = [&] {
+        if (MODE == ROW_UPDATE && p.est_one) {
+#pragma unroll
+            for (int s = 0; s < (PREFETCH ? NB * R : 1); ++s) pre[s] = mk<T>((T)1, (T)1);
+            return;
+        }
         const T* __restrict__ src = (MODE == ROW_RATIO ? p.src : p.dst) + (size_t)by * rimg;
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
@@ -1184,7 +1192,10 @@ RL_HD void row_item(const RowParams<T>& p, unsigned t, int by, int r0, RowSpectr
     cx<T> pre[NB * R];
     T* __restrict__ const est0 = p.dst + (size_t)by * rimg + (size_t)r0 * nx;
     T* __restrict__ const est1 = est0 + (ok1 ? nx : 0);
-    {
+    if (MODE == ROW_UPDATE && p.est_one) {
+#pragma unroll
+        for (int s = 0; s < NB * R; ++s) pre[s] = mk<T>((T)1, (T)1);
+    } else {
         const T* __restrict__ s0 = MODE == ROW_RATIO ? p.src + (size_t)by * rimg + (size_t)r0 * nx : est0;
         const T* __restrict__ s1 = s0 + (ok1 ? nx : 0);
 #pragma unroll
@@ -1347,7 +1358,10 @@ RL_HD void rowpair_body(const RowParams<T>& p, int tid, int bx, int by, cx<T>* l
     // (an L2 hit: one image shared by all frames) ahead of it too or right behind it (1: registers against waits)
     cx<T> pre[NB * R];
     T nrm[MODE == ROW_UPDATE ? NB * R : 1];
-    {
+    if (MODE == ROW_UPDATE && p.est_one) {
+#pragma unroll
+        for (int s = 0; s < NB * R; ++s) pre[s] = mk<T>((T)1, (T)1);
+    } else {
         const T* __restrict__ s0 = (MODE == ROW_UPDATE ? p.dst : p.src) + ra;
         const T* __restrict__ s1 = (MODE == ROW_UPDATE ? p.dst : p.src) + rb;
 #pragma unroll

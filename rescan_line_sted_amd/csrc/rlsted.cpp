@@ -19,6 +19,7 @@
 #include "aux_kernels.hpp"
 #include "conv_kernels.hpp"
 #include "kernel_table.hpp"
+#include "object_classes.hpp"
 #include "ctx.hpp"
 #include "sep_kernels.hpp"
 #include "sep_taps.hpp"
@@ -90,6 +91,7 @@ struct PlanOptions {
     bool col_split = true;       // RLSTED_COL_SPLIT=0: no split column pass (rl_deconv::col_split)
     bool real_psf = true;        // RLSTED_REAL_PSF=0: keep the complex multiplier for real PSF spectra
     bool ones_shortcut = true;   // RLSTED_ONES_SHORTCUT=0: the first iteration transforms its frame of ones instead of reading spec_ones
+    bool share_objects = true;   // RLSTED_SHARE_OBJECTS=0: every frame's H(object) is computed, also of frames that carry the same object
     // ---- strategy (deconv_build)
     int sep = 1;                 // RLSTED_SEP: separable stencils 0 never, 1 rank-1 PSFs with py + px <= 16, 2 whenever rank 1
     int sep_one = 1;             // RLSTED_SEP_ONE: 0 two passes, 1 one kernel up to 24 taps a side, 2 one kernel whenever the tile fits LDS
@@ -124,6 +126,7 @@ PlanOptions plan_options(int dtype, int n_psf) {
     o.col_split = flag("RLSTED_COL_SPLIT", o.col_split);
     o.real_psf = flag("RLSTED_REAL_PSF", o.real_psf);
     o.ones_shortcut = flag("RLSTED_ONES_SHORTCUT", o.ones_shortcut);
+    o.share_objects = flag("RLSTED_SHARE_OBJECTS", o.share_objects);
     o.sep = number("RLSTED_SEP", o.sep);
     o.sep_one = number("RLSTED_SEP_ONE", o.sep_one);
     o.direct = number("RLSTED_DIRECT", o.direct);
@@ -236,7 +239,7 @@ struct rl_deconv {
     // ---- rl_batch_submit: the tasks of a chunk -- objects, brightness targets, Philox keys -- are staged in one page-locked
     // block, uploaded on a copy stream of the plan's own and consumed on the context's stream; two blocks, so that chunk i + 1
     // is staged and uploaded while chunk i iterates.  Block layout (host and device): header -- [B] float64 targets, [B] uint64
-    // seeds, [B] uint32 image ids, [B] uint32 object index -- then the chunk's DISTINCT objects, [<= B][n_img] float64 (tasks that
+    // seeds, [B] uint32 image ids, [B] uint32 object index, [2][B] uint32 lists of the shared simulation (ShareLists) -- then the chunk's DISTINCT objects, [<= B][n_img] float64 (tasks that
     // share an object pointer -- a sweep's seeds -- are staged and uploaded once; only the used prefix of the block crosses PCIe);
     // the device block is followed by the objects' float64 sums and their scratch (aux_sums_elems(B)).
     struct BatchSlot {
@@ -251,7 +254,7 @@ struct rl_deconv {
     hipStream_t copy_stream = nullptr;
     unsigned long batch_chunks = 0;
     size_t slot_objects_bytes() const { return (size_t)B * n_img() * sizeof(double); }
-    size_t slot_header_bytes() const { return ((size_t)B * (8 + 8 + 4 + 4) + 15) / 16 * 16; }
+    size_t slot_header_bytes() const { return ((size_t)B * (8 + 8 + 4 + 4 + 4 + 4) + 15) / 16 * 16; }
     size_t slot_host_bytes() const { return slot_header_bytes() + slot_objects_bytes(); }
     bool batch_slots_ready = false;
     int ensure_batch_slots() {
@@ -354,7 +357,8 @@ struct rl_deconv {
     // from_ones: (study builds) the ratio of the iteration that starts from estimate = 1 is measurement / H(1), data scale: its
     //   ratio-type spectra carry q_est;
     // drop_spectrum: ROW_UPDATE does not transform the new estimate forward again (pair loop: the last iteration of a long run).
-    struct Iter { int f0, nf; bool first, from_ones, drop_spectrum; };
+    // est_one: the estimate is 1 and was NOT filled -- ROW_UPDATE takes it as 1 instead of reading it (RowParams::est_one).
+    struct Iter { int f0, nf; bool first, from_ones, drop_spectrum; bool est_one = false; };
     // scale of a ratio-type spectrum (ROW_RATIO's output, the H_t columns' input); it == nullptr: a launch outside the loop (rl_adjoint)
     float ratio_scale(const Iter* it) const { return it && it->from_ones ? q_est : q_ratio; }
     // H_t inside a `ratio - 1` iteration: the spectra of residuals (rl_adjoint's input is an image)
@@ -516,6 +520,7 @@ struct rl_deconv {
         RowParams<T> p;
         p.in_mod = in_mod;
         p.sub_one = sub() ? 1 : 0;
+        p.est_one = mode == ROW_UPDATE && it && it->est_one ? 1 : 0;
         p.unresolved = unresolved;
         p.qscale = mode == ROW_RATIO ? ratio_scale(it) : q_est;
         p.spec_in = (const cx<T>*)spec_in;
@@ -904,9 +909,9 @@ struct rl_deconv {
     }
     int pass_update(const Iter& it) {   // est *= H_t / norm, and rowFFT(est) for the next iteration
         void *e = off(est, (size_t)it.f0 * n_img()), *s = est_spec(it.f0);
-        if (pair) return row_pair(ROW_UPDATE, it.nf, s, it.drop_spectrum ? nullptr : s, nullptr, e, norm);
-        if (ht_fused()) return row(ROW_UPDATE, (unsigned)it.nf, s, s, nullptr, e, norm, nullptr, 1);
-        return row(ROW_UPDATE, (unsigned)it.nf, ratio_spec(it.f0), s, nullptr, e, norm);
+        if (pair) return row_pair(ROW_UPDATE, it.nf, s, it.drop_spectrum ? nullptr : s, nullptr, e, norm, 0, 1, &it);
+        if (ht_fused()) return row(ROW_UPDATE, (unsigned)it.nf, s, s, nullptr, e, norm, nullptr, 1, 0, &it);
+        return row(ROW_UPDATE, (unsigned)it.nf, ratio_spec(it.f0), s, nullptr, e, norm, nullptr, -1, 0, &it);
     }
     int iterate_chunk(const Iter& it) {
         if (sep) return sep_iterate(it.f0, it.nf);
@@ -924,17 +929,85 @@ struct rl_deconv {
         return row(ROW_INV, (unsigned)(B * V), spec_b, nullptr, nullptr, noiseless, nullptr);
     }
     // noiseless = H(obj) on a slice
-    int forward_slice(int f0, int nf) {
-        const size_t o = (size_t)f0 * V * n_img();
-        if (sep) return sep_forward(off(obj, (size_t)f0 * n_img()), off(noiseless, o), off(sep_tmp(), o), nf);
+    int forward_slice(int f0, int nf) { return forward_frames(f0, nf, off(obj, (size_t)f0 * n_img()), off(noiseless, (size_t)f0 * V * n_img())); }
+    // out [nf * V] = H(x [nf]) in the spectrum space of the slice that starts at frame f0 (nf: at most that slice's frames)
+    int forward_frames(int f0, int nf, const void* x, void* out) {
+        if (sep) return sep_forward(x, out, off(sep_tmp(), (size_t)f0 * V * n_img()), nf);
         void* sb = off(spec_b, (size_t)f0 * V * n_spec() * 2);
         // (frame pairs: the other lane's slice iterates in spec_a in the pair layout, whose slice boundaries are not
         // this layout's -- the simulation then stays in spec_b, in place)
         void* sa = !pair ? off(spec_a, (size_t)f0 * n_spec() * 2) : sb;
-        RL_TRY(row(ROW_FWD, (unsigned)nf, nullptr, sa, off(obj, (size_t)f0 * n_img()), nullptr, nullptr));
+        RL_TRY(row(ROW_FWD, (unsigned)nf, nullptr, sa, x, nullptr, nullptr));
         if (col_split()) RL_TRY(col_split_pass(sa, sb, parked(f0), nf, COL_H));   // (the same values as the whole pass)
         else RL_TRY(col(sa, sb, nf, COL_H));
-        RL_TRY(row(ROW_INV, (unsigned)(nf * V), sb, nullptr, nullptr, off(noiseless, o), nullptr));
+        RL_TRY(row(ROW_INV, (unsigned)(nf * V), sb, nullptr, nullptr, out, nullptr));
+        return RL_OK;
+    }
+    // ---- shared simulation (object_classes.hpp): frames that carry the same object are one class, and a slice of the batch
+    // computes H(object) of the first frame of each class it holds instead of every frame's -- the benchmark's batch and a sweep's
+    // seeds are one object many times over.  The representatives' objects and rates live in two compact buffers, a slice's
+    // side by side; the Poisson sampler reads every frame's rates through rate_of.  `noiseless` itself is then not written: it is
+    // filled from the compact rates when somebody asks for it (expand_noiseless).  RLSTED_SHARE_OBJECTS=0: off.
+    std::vector<int> obj_class;            // class of every frame of the object as it was set; empty: not known, nothing is shared
+    int n_classes = 0;
+    std::vector<SliceShare> share_slices;  // the layout for slices of share_cf frames (0: none built for the object at hand)
+    int share_cf = 0;
+    std::vector<uint32_t> share_reps, share_rate;   // host copies of the lists below
+    struct ShareLists { const unsigned *rep_frames, *rate_of; };   // device, [B] each: the plan's own or those of a batch slot
+    ShareLists share_lists{nullptr, nullptr};
+    unsigned* share_dev = nullptr;         // [2][B] the plan's own lists
+    void *obj_c = nullptr, *noiseless_c = nullptr;   // [share_cap] objects, [share_cap * V] rates
+    size_t share_cap = 0;
+    bool noiseless_sparse = false;         // the last simulation left (some) slices' rates in noiseless_c only
+    int last_shared_slices = 0, last_slices = 0;
+    bool share_possible() const { return opt.share_objects && !sep && (int)obj_class.size() == B && n_classes < B; }
+    // The layout for slices of cf frames from obj_class, its lists on the device -- `staged`: already there (rl_batch_submit puts
+    // them into the chunk's block), otherwise uploaded here -- and the representatives' objects gathered from obj.  On the
+    // context's stream; not while lanes are open.
+    int build_share(int cf, const ShareLists* staged) {
+        share_cf = 0;
+        noiseless_sparse = false;   // (whatever an earlier layout left is replaced by the simulation that follows)
+        const size_t total = (size_t)share_layout(obj_class, cf, share_slices, share_reps, share_rate);
+        if (total > share_cap) {   // (grow only; in groups of 8 images)
+            HIP_TRY(hipDeviceSynchronize());
+            share_cap = 0;
+            RL_TRY(release(&obj_c));
+            RL_TRY(release(&noiseless_c));
+            const size_t cap = (total + 7) / 8 * 8;
+            RL_TRY(alloc(&obj_c, cap * n_img() * esize(dtype), SLACK));
+            RL_TRY(alloc(&noiseless_c, cap * V * n_img() * esize(dtype), SLACK));
+            share_cap = cap;
+        }
+        if (staged) {
+            share_lists = *staged;
+        } else {
+            if (!share_dev) RL_TRY(alloc(&share_dev, 2 * (size_t)B * sizeof(unsigned), UNCOUNTED));
+            if (total) HIP_TRY(hipMemcpyAsync(share_dev, share_reps.data(), total * sizeof(unsigned), hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(share_dev + B, share_rate.data(), (size_t)B * sizeof(unsigned), hipMemcpyHostToDevice, ctx->stream));
+            share_lists = {share_dev, share_dev + B};
+        }
+        HIP_TRY(aux_gather_images(dtype, obj, obj_c, share_lists.rep_frames, n_img(), total, 1, ctx->stream));
+        if (!staged) HIP_TRY(hipStreamSynchronize(ctx->stream));   // the host lists are the plan's to change again
+        share_cf = cf;
+        return RL_OK;
+    }
+    // the object was (or may have been) replaced: nothing is known about its frames until somebody classifies them
+    void forget_classes() {
+        obj_class.clear();
+        n_classes = 0;
+        share_cf = 0;
+    }
+    // every frame's rates into `noiseless`, where a shared simulation left them in the compact buffer (on the context's stream)
+    int expand_noiseless() {
+        if (!noiseless_sparse) return RL_OK;
+        const int cf = share_cf;
+        for (int sl = 0, f0 = 0; f0 < B && cf > 0; f0 += cf, ++sl) {
+            const int nf = f0 + cf <= B ? cf : B - f0;
+            if (share_slices[(size_t)sl].nrep == 0) continue;
+            HIP_TRY(aux_gather_images(dtype, noiseless_c, off(noiseless, (size_t)f0 * V * n_img()), share_lists.rate_of + f0, n_img(),
+                                      (size_t)nf * V, (unsigned)V, ctx->stream));
+        }
+        noiseless_sparse = false;
         return RL_OK;
     }
     int join_open_lanes() {   // after a failed cycle between deferred joins
@@ -959,6 +1032,9 @@ struct rl_deconv {
         // goes to the same lane, so stream order alone keeps each slice's buffers consistent and the lanes need not meet.
         const bool keep_open = cycle_follows && nl > 1;
         if (accel && restart) RL_TRY(accel_reset());   // each run from ones (a task of rl_batch_run included) starts a fresh history
+        // the slices' representatives (a layout for another slice size is rebuilt; not between cycles whose lanes are still running)
+        if (draw && share_possible() && share_cf != cf && !lanes_open) RL_TRY(build_share(cf, nullptr));
+        const bool share = draw && share_possible() && share_cf == cf;
         if (nl > 1 && !lanes_open) {
             RL_TRY(ensure_lanes());
             HIP_TRY(hipEventRecord(fork, ctx->stream));
@@ -980,13 +1056,24 @@ struct rl_deconv {
             hipStream_t& a;
             ~ActiveGuard() { a = nullptr; }
         } active_guard{active};
+        int shared_slices = 0;
         auto simulate_slice = [&](int sl, int f0, int nf) -> int {
-            RL_TRY(forward_slice(f0, nf));
+            // a sharing slice: H of its representatives' objects alone, into the compact rates that every frame of the slice draws from
+            const SliceShare ss = share ? share_slices[(size_t)sl] : SliceShare{};
+            const void* rates = off(noiseless, (size_t)f0 * V * n_img());
+            if (ss.nrep > 0) {
+                RL_TRY(forward_frames(f0, ss.nrep, off(obj_c, (size_t)ss.c0 * n_img()), off(noiseless_c, (size_t)ss.c0 * V * n_img())));
+                rates = noiseless_c;
+                ++shared_slices;
+            } else {
+                RL_TRY(forward_slice(f0, nf));
+            }
             void* ws = (char*)slice_ws + (size_t)sl * slice_ws_stride;   // this slice's Poisson work list
             TimedScope t(this, TK_POISSON, false);
-            hipError_t e = aux_poisson(dtype, off(noiseless, (size_t)f0 * V * n_img()), off(meas, (size_t)f0 * V * n_img()),
+            hipError_t e = aux_poisson(dtype, rates, off(meas, (size_t)f0 * V * n_img()),
                                        (unsigned)n_img(), (unsigned)(nf * V), (unsigned)(f0 * V), draw->seed, draw->rng_kind, ws, cur(),
-                                       draw->key_seeds ? draw->key_seeds + f0 : nullptr, draw->key_ids ? draw->key_ids + f0 : nullptr, (unsigned)V);
+                                       draw->key_seeds ? draw->key_seeds + f0 : nullptr, draw->key_ids ? draw->key_ids + f0 : nullptr, (unsigned)V,
+                                       ss.nrep > 0 ? share_lists.rate_of + f0 : nullptr);
             if (e != hipSuccess) return fail(RL_ERR_HIP, std::string("Poisson kernels: ") + hipGetErrorString(e));
             return RL_OK;
         };
@@ -998,14 +1085,17 @@ struct rl_deconv {
             active = nl > 1 ? lane_stream[sl % nl] : nullptr;
             if (draw) rc = simulate_slice(sl, f0, nf);
             const bool shortcut = restart && opt.ones_shortcut && spec_ones && k > 0 && !sep;
-            if (restart && rc == RL_OK) rc = start_estimate_chunk(f0, nf, !shortcut);
+            // The plain loop's first iteration reads neither the estimate's spectrum (shortcut) nor -- est_one -- the estimate, and its
+            // ROW_UPDATE writes every pixel of it: nothing is filled.  The accelerated and the regularised steps read est themselves.
+            const bool ones_first = shortcut && !accel && !tv_on();
+            if (restart && rc == RL_OK && !ones_first) rc = start_estimate_chunk(f0, nf, !shortcut);
             // Frame pairs: the last iteration of a run of >= 4 does not transform its estimate forward again (1 of 2 row
             // transforms of that launch, the spectrum store); an rl_deconv_iterate that continues rebuilds it with one ROW_FWD.
             const bool drop = pair && k >= 4;
             for (int i = 0; i < k && rc == RL_OK; ++i) {
                 if (accel) rc = accel_step(f0, nf, acc_steps + i, shortcut && i == 0, restart && i == 0);
                 else if (tv_on()) rc = tv_iterate({f0, nf, shortcut && i == 0, restart && i == 0, /* drop_spectrum */ pair}, i > 0 || tv_sum_valid, true);
-                else rc = iterate_chunk({f0, nf, shortcut && i == 0, restart && i == 0, drop && i == k - 1});
+                else rc = iterate_chunk({f0, nf, shortcut && i == 0, restart && i == 0, drop && i == k - 1, ones_first && i == 0});
             }
         }
         active = nullptr;
@@ -1019,6 +1109,11 @@ struct rl_deconv {
             lanes_open = true;
         }
         RL_TRY(rc);
+        if (draw) {
+            noiseless_sparse = shared_slices > 0;
+            last_shared_slices = shared_slices;
+            last_slices = slices;
+        }
         if (restart) {
             est_ready = true;
             spec_valid = true;
@@ -1390,8 +1485,15 @@ int rl_deconv_set_object(rl_deconv* h, const double* obj, const double* total_br
     // :505-506  obj *= total_brightness / obj.sum(), per frame, on the device
     RL_TRY(h->upload_images(obj, h->obj, (size_t)h->B, total_brightness, &h->obj_level));
     if (total_brightness) h->obj_level.assign(total_brightness, total_brightness + h->B);   // the frames' sums after scaling
+    // Frames with the same pixels and the same target are the same object on the device too: a frame's scale is target / sum, and
+    // its sum is taken in an order that depends on the frame alone (k_frame_sums; which of its two forms runs is decided by the
+    // frame size, the same for every piece of an upload: pieces of 128 MiB hold at most 16 frames of the size that takes the chunked one).
+    h->forget_classes();
+    if (h->opt.share_objects && !h->sep) h->n_classes = classify_by_pixels(obj, h->n_img(), h->B, total_brightness, h->obj_class);
     HIP_TRY(hipEventRecord(h->ev0, h->ctx->stream));
     RL_TRY(h->forward_object());
+    h->noiseless_sparse = false;
+    if (h->share_possible()) RL_TRY(h->build_share(h->chunk_frames(), nullptr));
     HIP_TRY(hipEventRecord(h->ev1, h->ctx->stream));
     HIP_TRY(hipEventSynchronize(h->ev1));
     float ms = 0;
@@ -1407,6 +1509,7 @@ int rl_deconv_simulate(rl_deconv* h, int rng_kind, uint64_t seed) {
     if (!h->have_obj) return fail(RL_ERR_STATE, "rl_deconv_set_object has not been called");
     if (rng_kind != RL_RNG_NONE && rng_kind != RL_RNG_PHILOX) return fail(RL_ERR_INVALID, "unknown rng_kind");
     HIP_TRY(hipSetDevice(h->ctx->device));
+    RL_TRY(h->expand_noiseless());
     HIP_TRY(aux_poisson(h->dtype, h->noiseless, h->meas, (unsigned)h->n_img(), (unsigned)(h->B * h->V), 0, seed, rng_kind,
                         h->scratch, h->ctx->stream));
     HIP_TRY(hipStreamSynchronize(h->ctx->stream));
@@ -1429,6 +1532,7 @@ int rl_deconv_simulate_keyed(rl_deconv* h, int rng_kind, const uint64_t* seeds, 
     if (!h->key_ids) RL_TRY(h->alloc(&h->key_ids, (size_t)h->B * sizeof(uint32_t), rl_deconv::UNCOUNTED));
     HIP_TRY(hipMemcpyAsync(h->key_seeds, seeds, (size_t)h->B * sizeof(uint64_t), hipMemcpyHostToDevice, h->ctx->stream));
     HIP_TRY(hipMemcpyAsync(h->key_ids, image_ids, (size_t)h->B * sizeof(uint32_t), hipMemcpyHostToDevice, h->ctx->stream));
+    RL_TRY(h->expand_noiseless());
     HIP_TRY(aux_poisson(h->dtype, h->noiseless, h->meas, (unsigned)h->n_img(), (unsigned)(h->B * h->V), 0, 0, rng_kind,
                         h->scratch, h->ctx->stream, (const unsigned long long*)h->key_seeds, (const unsigned*)h->key_ids,
                         (unsigned)h->V));
@@ -1617,7 +1721,13 @@ int rl_deconv_iterate_until(rl_deconv* h, int k_max, int check_every, int rule, 
         return h->download(h->buf, out, (count));                                 \
     }
 RL_GETTER(rl_deconv_get_object, obj, (size_t)h->B* h->n_img(), h->have_obj, "object")
-RL_GETTER(rl_deconv_get_noiseless, noiseless, (size_t)h->B* h->V* h->n_img(), h->have_obj, "noiseless measurement")
+int rl_deconv_get_noiseless(rl_deconv* h, double* out) {
+    if (!h || !out) return fail(RL_ERR_INVALID, "NULL argument");
+    if (!h->have_obj) return fail(RL_ERR_STATE, "noiseless measurement is not available yet");
+    HIP_TRY(hipSetDevice(h->ctx->device));
+    RL_TRY(h->expand_noiseless());   // (a shared simulation keeps one image per class and slice)
+    return h->download(h->noiseless, out, (size_t)h->B * h->V * h->n_img());
+}
 RL_GETTER(rl_deconv_get_measurement, meas, (size_t)h->B* h->V* h->n_img(), h->have_meas, "measurement")
 RL_GETTER(rl_deconv_get_estimate, est, (size_t)h->B* h->n_img(), h->est_ready, "estimate")
 RL_GETTER(rl_deconv_get_normalization, norm, h->n_img(), true, "normalization")
@@ -1710,6 +1820,14 @@ int rl_deconv_strategy(const rl_deconv* h, int* separable, int* real_psf_spectru
     return RL_OK;
 }
 
+int rl_deconv_object_classes(const rl_deconv* h, int* classes, int* shared_slices, int* slices) {
+    if (!h) return fail(RL_ERR_INVALID, "handle is NULL");
+    if (classes) *classes = (int)h->obj_class.size() == h->B ? h->n_classes : 0;
+    if (shared_slices) *shared_slices = h->last_shared_slices;
+    if (slices) *slices = h->last_slices;
+    return RL_OK;
+}
+
 int rl_deconv_unresolved(rl_deconv* h, unsigned long long* count, int reset) {
     if (!h || !count) return fail(RL_ERR_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(h->ctx->device));
@@ -1751,6 +1869,7 @@ int rl_batch_submit(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_iters
         uint64_t* seeds = (uint64_t*)(tb + B);
         uint32_t* ids = (uint32_t*)(seeds + B);
         uint32_t* idx = ids + B;
+        uint32_t* lists = idx + B;   // [2][B]: ShareLists
         double* objs = (double*)(sl.host + h->slot_header_bytes());
         bool scaled = true;
         std::vector<double> level((size_t)B, 0.0);
@@ -1779,6 +1898,19 @@ int rl_batch_submit(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_iters
                 for (size_t i = 0; i < n; ++i) usum[u] += objs[u * n + i];
             for (int f = 0; f < B; ++f) level[f] = usum[idx[f]];
         }
+        h->obj_level = level;
+        h->meas_level = level;
+        h->choose_loop(h->meas_level);
+        // tasks that share an object and a target are one class (object_classes.hpp); the lists of the slices' representatives ride in the header
+        h->forget_classes();
+        if (h->opt.share_objects && !h->sep) h->n_classes = classify_by_index(idx, scaled ? tb : nullptr, B, h->obj_class);
+        const bool share = h->share_possible();
+        const int cf = h->chunk_frames();
+        if (share) {
+            share_layout(h->obj_class, cf, h->share_slices, h->share_reps, h->share_rate);
+            std::copy(h->share_reps.begin(), h->share_reps.end(), lists);
+            std::copy(h->share_rate.begin(), h->share_rate.end(), lists + B);
+        }
         const size_t used = h->slot_header_bytes() + uniq.size() * n * sizeof(double);
         HIP_TRY(hipMemcpyAsync(sl.dev, sl.host, used, hipMemcpyHostToDevice, h->copy_stream));
         HIP_TRY(hipEventRecord(sl.uploaded, h->copy_stream));
@@ -1791,9 +1923,10 @@ int rl_batch_submit(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_iters
         double* d_sums = (double*)(sl.dev + (h->slot_host_bytes() + 7) / 8 * 8);
         // :505-506  obj *= total_brightness / obj.sum(), per frame, on the device
         HIP_TRY(aux_scale_convert_indexed(h->dtype, d_objs, d_idx, uniq.size(), h->obj, n, (size_t)B, scaled ? d_tb : nullptr, d_sums, s));
-        h->obj_level = level;
-        h->meas_level = level;
-        h->choose_loop(h->meas_level);
+        if (share) {
+            const rl_deconv::ShareLists staged{d_idx + B, d_idx + 2 * B};
+            RL_TRY(h->build_share(cf, &staged));
+        }
         h->have_obj = true;
         const rl_deconv::Draw draw{rng_kind, 0, d_seeds, d_ids};
         const int rc = h->run_slices(k_iters, true, &draw);   // per slice: H(obj), keyed Poisson draws, estimate = 1, k iterations
@@ -1903,8 +2036,19 @@ int rl_deconv_device_ptr(rl_deconv* h, int which, void** ptr, size_t* n_elements
             h->meas_level.clear();
             h->meas_external = true;
             break;
-        case 2: p = h->noiseless; n = (size_t)h->B * h->V * h->n_img(); break;
-        case 3: p = h->obj; n = (size_t)h->B * h->n_img(); break;
+        case 2:   // (a shared simulation left one image per class and slice: every frame's is written now)
+            HIP_TRY(hipSetDevice(h->ctx->device));
+            RL_TRY(h->expand_noiseless());
+            p = h->noiseless;
+            n = (size_t)h->B * h->V * h->n_img();
+            break;
+        case 3:   // (the caller may write the objects: which frames carry the same one is no longer known)
+            HIP_TRY(hipSetDevice(h->ctx->device));
+            RL_TRY(h->expand_noiseless());
+            h->forget_classes();
+            p = h->obj;
+            n = (size_t)h->B * h->n_img();
+            break;
         case 4:
             if (!h->tv_w) return fail(RL_ERR_STATE, "no RL-TV weights: rl_deconv_set_tv has not switched the mode on");
             p = h->tv_w;

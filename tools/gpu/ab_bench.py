@@ -2,8 +2,9 @@
 
     python3 tools/gpu/ab_bench.py [--size 512] [--views 1] [--batch 1024] [--k 20] [--rounds 5] [--dtype f32] LIB_A LIB_B ...
 
-Each library is bound through its own copy of rescan_line_sted_amd._lib.  Prints per library the median / min step time,
-frames/s, and the estimate's largest deviation from the first library's (same seed, same objects).
+Each library is bound through its own copy of rescan_line_sted_amd._lib.  Prints per library the median / min step time and
+the spread of its rounds (max - min: a difference between libraries inside it is not a difference), frames/s, and the
+estimate's largest deviation from the first library's (same seed, same objects).
 """
 import argparse
 import importlib.util
@@ -73,8 +74,10 @@ def main():
     for i, path in enumerate(a.libs):
         t = np.array(times[i])
         d = float(np.max(np.abs(ests[i] - ests[0])) / np.max(np.abs(ests[0])))
-        print('%-44s median %8.3f ms  min %8.3f ms  %9.0f frames/s (median)  max dev vs first %.2e  %s' % (
-            os.path.basename(path), np.median(t) * 1e3, t.min() * 1e3, a.batch / np.median(t), d, plans[i].strategy()), flush=True)
+        print('%-44s median %8.3f ms  min %8.3f ms  spread %6.3f ms  %9.0f frames/s (median)  max dev vs first %.2e  %s' % (
+            os.path.basename(path), np.median(t) * 1e3, t.min() * 1e3, (t.max() - t.min()) * 1e3, a.batch / np.median(t), d,
+            plans[i].strategy()), flush=True)
+        print('%-44s rounds (ms): %s' % ('', ' '.join('%.3f' % (x * 1e3) for x in t)), flush=True)
 
 
 if __name__ == '__main__':

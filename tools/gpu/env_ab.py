@@ -26,7 +26,7 @@ for cfg in sys.argv[4:]:
     plan.bench_cycles(20, 1, seed=1)
     plans.append(plan)
 times = [[] for _ in plans]
-for r in range(4):
+for r in range(6):
     for i, plan in enumerate(plans):
         plan.ctx.synchronize()
         t0 = time.perf_counter()
@@ -34,4 +34,5 @@ for r in range(4):
         plan.ctx.synchronize()
         times[i].append((time.perf_counter() - t0) / 2)
 for cfg, t in zip(sys.argv[4:], times):
-    print('%-40s median %8.2f ms  %8.1f frames/s' % (cfg or '(default)', np.median(t) * 1e3, B / np.median(t)), flush=True)
+    print('%-40s median %8.3f ms  spread %6.3f ms  %8.1f frames/s' % (cfg or '(default)', np.median(t) * 1e3, (max(t) - min(t)) * 1e3,
+                                                                     B / np.median(t)), flush=True)
