@@ -441,6 +441,31 @@ int rl_ring_count(int ny, int nx);
 int rl_ring_stats(rl_ctx* ctx, const void* a_dev, int a_dtype, const int64_t* a_offsets, const void* b_dev, int b_dtype,
                   const int64_t* b_offsets, const double* b_scale, int n_pairs, int ny, int nx, int n_rings, double* out);
 
+/* ---- angle-resolved ring statistics: the rings of rl_ring_stats cut into n_sectors = S orientation sectors ----
+ * What separates a 2-line scan from a 3-line scan from a point PSF: the error and the ring correlation along one direction.
+ * Bin (ky, kx) has the signed frequencies sy, sx of rl_ring_stats; with the integers Y = sy * nx, X = sx * ny (the two that form
+ * q) its ring is unchanged.
+ * ORIENTATION: theta = atan2(Y, X) folded into [0, pi): (Y, X) is replaced by (-Y, -X) when Y < 0 or (Y = 0 and X < 0).  theta is
+ * measured from +kx towards +ky in physical cycles per pixel (the angle_degrees of error_vs_spatial_frequency); a bin and its
+ * Hermitian partner -k have the same theta.
+ * SECTOR of the bin:  sector = floor(S * theta / pi + 1/2) mod S.  Sector j is centred on j * 180 / S degrees and half-open,
+ * [centre - 90 / S, centre + 90 / S) degrees; S = 2 * num_angles puts the figure's best angle in the middle of sector 0 and its
+ * worst angle in the middle of sector 1.  The DC bin has no orientation and belongs to sector 0.
+ * EXACTNESS: a bin lies exactly on a boundary only when that boundary is a multiple of 45 degrees (the tangent of any other
+ * boundary angle is irrational): for odd S the boundary at 90 degrees (bins with X = 0), for S = 2 mod 4 those at 45 and 135
+ * degrees (bins with |Y| = |X|).  These ties are decided in integers (Y = 0, X = 0, |Y| = |X|) and by the half-open rule go to
+ * the upper sector.  Everywhere else the host builder uses long double, and if a bin that is no tie comes closer to a boundary
+ * than 2^-30 (in units of S * theta / pi) the call fails with RL_ERR_UNSUPPORTED rather than guessing.  The device never
+ * computes an angle.  The table is built on the host, once per (ny, nx, n_rings, n_sectors) and context.
+ * out[pair][ring][sector][RL_RING_FIELDS]: the five fields of rl_ring_stats summed over the bins of the cell (ring, sector), in
+ * a fixed order (ring_kernels.hpp), bit-identical from run to run and independent of the other pairs of the call.  An empty
+ * cell is five zeros, never nan.  Because -k shares k's cell, every cell's sums are those of a real image pair, like a ring's.
+ * Every other rule is that of rl_ring_stats: offsets, dtypes, b_scale, chunking under the workspace cap (the result chunk is S
+ * times as large), the 4096 limit, the error codes; and RL_ERR_INVALID: n_sectors < 1;  RL_ERR_UNSUPPORTED: n_sectors > 64.   */
+int rl_ring_sector_stats(rl_ctx* ctx, const void* a_dev, int a_dtype, const int64_t* a_offsets, const void* b_dev, int b_dtype,
+                         const int64_t* b_offsets, const double* b_scale, int n_pairs, int ny, int nx, int n_rings,
+                         int n_sectors, double* out);
+
 /* ---- line_sted_figure_3.py: the scan-position-by-scan-position imaging simulator (:76-273) ----
  * rl_rotate_image: `rotate` (:382-391) for one [ny][nx] plane -- scipy.ndimage.rotate(order 3,
  * mode 'nearest', reshape=False) about the centre; clip != 0 clips to [0, 1.1 * max(in)].  Host in / out. */

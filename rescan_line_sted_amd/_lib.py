@@ -118,6 +118,7 @@ PROTOTYPES = {
     'rl_spline_sample': (_i, [_vp, _dp, _i, _i, _dp, _dp, _i, _dp]),
     'rl_ring_count': (_i, [_i, _i]),
     'rl_ring_stats': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _vp, _i, _c.POINTER(_c.c_int64), _dp, _i, _i, _i, _i, _dp]),
+    'rl_ring_sector_stats': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _vp, _i, _c.POINTER(_c.c_int64), _dp, _i, _i, _i, _i, _i, _dp]),
 }
 
 

@@ -61,21 +61,25 @@ struct rl_ctx {
         return RL_OK;
     }
 
-    // rl_ring_stats (ring_api.cpp): the device ring tables, one per (ny, nx, n_rings), and a grow-only workspace; freed with the
-    // context (rl_ctx_destroy deletes it with its device current)
+    // rl_ring_stats, rl_ring_sector_stats (ring_api.cpp): the device ring tables, one per (ny, nx, n_rings), the sector tables,
+    // one per (ny, nx, n_rings, n_sectors), and a grow-only workspace; freed with the context (rl_ctx_destroy deletes it with its
+    // device current)
     struct RingTable {
-        int* row_ptr = nullptr;   // [n_rings + 1]
+        int* row_ptr = nullptr;   // [n_rings + 1]; a sector table's cell_ptr [n_rings * n_sectors + 1]
         int* bins = nullptr;      // [row_ptr[n_rings]]
     };
     struct RingCache {
         std::map<std::pair<std::pair<int, int>, int>, RingTable> tables;
+        std::map<std::pair<std::pair<int, int>, std::pair<int, int>>, RingTable> sector_tables;
         void* work = nullptr;
         size_t work_bytes = 0;
+        static void release(RingTable& t) {
+            if (t.row_ptr) (void)hipFree(t.row_ptr);
+            if (t.bins) (void)hipFree(t.bins);
+        }
         ~RingCache() {
-            for (auto& kv : tables) {
-                if (kv.second.row_ptr) (void)hipFree(kv.second.row_ptr);
-                if (kv.second.bins) (void)hipFree(kv.second.bins);
-            }
+            for (auto& kv : tables) release(kv.second);
+            for (auto& kv : sector_tables) release(kv.second);
             if (work) (void)hipFree(work);
         }
     } ring;

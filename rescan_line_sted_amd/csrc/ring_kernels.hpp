@@ -26,6 +26,17 @@
 //   workgroup tree over the kRingThreads slots: s[t] = s[t] + s[t + h] for t < h, h = kRingThreads / 2, ..., 1
 // No float atomics, no partials across workgroups; contraction off outside the explicit fma.  A pair's result depends on its own
 // two images, the shape and the table only: never on the pairs beside it in the call.
+//
+// REDUCE BY SECTOR (rl_ring_sector_stats): the rings cut into n_sectors = S orientation sectors, cell c = ring * S + sector
+// (sector_of_bin, ring_build_sector_table: CSR over the cells, a cell's bins in increasing ky * nx + kx; the orientation is decided
+// on the host, ties in integers -- the device never computes an angle).  One workgroup of kRingThreads threads, four wave64s, per
+// (pair, ring); a WAVE owns a cell: wave w takes sectors w, w + 4, ... of the ring.  Per cell, in float64:
+//   lane      s_l = (((0 + term_0) + term_1) + ...) over bins cell_ptr[c] + l, + kRingWave, ... of the cell, in table order; the
+//             terms are those of REDUCE (ring_sum_bins, the one body of both)
+//   wave tree over the kRingWave lanes: v[l] = v[l] + v[l + h] for l < h, h = kRingWave / 2, ..., 1 (lane l reads lane l + h in
+//             registers; the lanes at and above h compute values nobody reads)
+//   lane 0    stores field 0 = cell_ptr[c + 1] - cell_ptr[c] and the four sums; an empty cell is five zeros.
+// No workgroup barrier, no LDS, no float atomics, no partials across waves.
 #pragma once
 #include "fft_core.hpp"
 
@@ -42,6 +53,8 @@ constexpr int kRingKT = 16;         // k per LDS step
 constexpr int kRingMicro = 4;       // a thread's outputs: kRingMicro x kRingMicro, strided by 16
 constexpr int kRingPitchA = kRingTile + 1;   // ROWS fills A k-fastest: the odd pitch spreads a wave's 16 k over the banks
 constexpr int kRingFields = 5;
+constexpr int kRingWave = 64;       // lanes of a wave: the sector reduce gives a wave a cell
+constexpr int kRingMaxSectors = 64;
 constexpr int kRingMaxN = 4096;     // longest image side (products g * k stay below 2^31)
 
 struct alignas(16) RingC {
@@ -84,6 +97,14 @@ struct RingReduceParams {
     const int* bins;           // [row_ptr[n_rings]]  ky * nx + kx
     double* out;               // [pairs][n_rings][kRingFields]
     int ny, nx, n_rings;
+};
+
+struct RingSectorParams {
+    const RingC* f;            // F [pairs][ny][nx]
+    const int* cell_ptr;       // [n_rings * n_sectors + 1]
+    const int* bins;           // [cell_ptr[n_rings * n_sectors]]  ky * nx + kx
+    double* out;               // [pairs][n_rings][n_sectors][kRingFields]
+    int ny, nx, n_rings, n_sectors;
 };
 
 RL_HD RingTw ring_tw_init(int g, int n, int t) {
@@ -190,16 +211,14 @@ RL_HD void ring_store_thread(RingC* out, int ny, int nx, int pair, int m0, int n
         }
 }
 
-// REDUCE, thread t of the workgroup of (pair, ring): its sums of fields 1..4 -> s[0..3]
-RL_HD void ring_reduce_thread(const RingReduceParams& p, int pair, int ring, int t, double* s) {
+// the sums of fields 1..4 over the table entries begin, begin + stride, ... below end, in that order -> s[0..3]
+RL_HD void ring_sum_bins(const RingC* f, int ny, int nx, const int* bins, int begin, int end, int stride, double* s) {
 #pragma clang fp contract(off)
-    const RingC* f = p.f + (size_t)pair * p.ny * p.nx;
     double s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0;
-    const int end = p.row_ptr[ring + 1];
-    for (int i = p.row_ptr[ring] + t; i < end; i += kRingThreads) {
-        const int bin = p.bins[i], ky = bin / p.nx, kx = bin - ky * p.nx;
-        const int my = ky ? p.ny - ky : 0, mx = kx ? p.nx - kx : 0;
-        const RingC z = f[bin], zm = f[(size_t)my * p.nx + mx];
+    for (int i = begin; i < end; i += stride) {
+        const int bin = bins[i], ky = bin / nx, kx = bin - ky * nx;
+        const int my = ky ? ny - ky : 0, mx = kx ? nx - kx : 0;
+        const RingC z = f[bin], zm = f[(size_t)my * nx + mx];
         const double ar = 0.5 * (z.re + zm.re), ai = 0.5 * (z.im - zm.im);
         const double br = 0.5 * (z.im + zm.im), bi = 0.5 * (zm.re - z.re);
         const double dr = ar - br, di = ai - bi;
@@ -214,6 +233,11 @@ RL_HD void ring_reduce_thread(const RingReduceParams& p, int pair, int ring, int
     s[3] = s4;
 }
 
+// REDUCE, thread t of the workgroup of (pair, ring): its sums of fields 1..4 -> s[0..3]
+RL_HD void ring_reduce_thread(const RingReduceParams& p, int pair, int ring, int t, double* s) {
+    ring_sum_bins(p.f + (size_t)pair * p.ny * p.nx, p.ny, p.nx, p.bins, p.row_ptr[ring] + t, p.row_ptr[ring + 1], kRingThreads, s);
+}
+
 // one step of the workgroup tree on the four fields' slots s[field][kRingThreads]
 RL_HD void ring_tree_step(double (*s)[kRingThreads], int t, int h) {
 #pragma clang fp contract(off)
@@ -225,6 +249,26 @@ RL_HD void ring_reduce_write(const RingReduceParams& p, int pair, int ring, cons
     double* o = p.out + ((size_t)pair * p.n_rings + ring) * kRingFields;
     o[0] = (double)(p.row_ptr[ring + 1] - p.row_ptr[ring]);
     for (int c = 0; c < 4; ++c) o[1 + c] = s[c][0];
+}
+
+// REDUCE BY SECTOR, lane l of the wave that owns cell (ring, sector) of `pair`: its sums of fields 1..4 -> v[0..3]
+RL_HD void ring_sector_lane(const RingSectorParams& p, int pair, int ring, int sector, int lane, double* v) {
+    const int c = ring * p.n_sectors + sector;
+    ring_sum_bins(p.f + (size_t)pair * p.ny * p.nx, p.ny, p.nx, p.bins, p.cell_ptr[c] + lane, p.cell_ptr[c + 1], kRingWave, v);
+}
+
+// one step of the wave tree on a lane's four sums: `up` holds those of the lane h above it
+RL_HD void ring_wave_step(double* v, const double* up) {
+#pragma clang fp contract(off)
+    for (int c = 0; c < 4; ++c) v[c] = v[c] + up[c];
+}
+
+// lane 0 of the wave, after the tree
+RL_HD void ring_sector_write(const RingSectorParams& p, int pair, int ring, int sector, const double* v) {
+    const int c = ring * p.n_sectors + sector;
+    double* o = p.out + ((size_t)pair * p.n_rings * p.n_sectors + c) * kRingFields;
+    o[0] = (double)(p.cell_ptr[c + 1] - p.cell_ptr[c]);
+    for (int k = 0; k < 4; ++k) o[1 + k] = v[k];
 }
 
 // ---- the ring table (host).  ring(ky, kx) = isqrt(4 R^2 q) / M in exact integers, q = (sy nx)^2 + (sx ny)^2, M = ny nx, sy / sx
@@ -260,13 +304,61 @@ inline void ring_build_table(int ny, int nx, int n_rings, std::vector<int>& row_
         if (ring[i] < n_rings) bins[(size_t)at[ring[i]]++] = (int)i;
 }
 
-// ---- launchers (ring_kernels.hip): `pairs` pairs on stream s; dtypes RL_F32 / RL_F64 of the two image buffers
+// ---- the sector of a bin (host; the definition: include/rlsted.h, rl_ring_sector_stats).  With Y = sy nx, X = sx ny folded into the
+// upper half plane, theta = atan2(Y, X) in [0, pi) and sector = floor(S theta / pi + 1/2) mod S.  A bin lies exactly on a sector
+// boundary only where that boundary is a multiple of 45 degrees (any other boundary has an irrational tangent): those directions
+// -- Y = 0, X = 0, |Y| = |X| -- are decided in integers, floor((S + 2) / 4), floor((S + 1) / 2), floor((3 S + 2) / 4), which puts
+// a tie into the upper sector.  Everything else goes through long double; a bin closer to a boundary than 2^-30 sets *too_close
+// instead of being guessed (none is known: the closest seen is 7.8e-5, at 160 x 160 with S = 4).
+inline int sector_of_bin(int ky, int kx, int ny, int nx, int n_sectors, bool* too_close) {
+    const int64_t S = n_sectors;
+    int64_t Y = (int64_t)(ky <= ny / 2 ? ky : ky - ny) * nx, X = (int64_t)(kx <= nx / 2 ? kx : kx - nx) * ny;
+    if (Y < 0 || (Y == 0 && X < 0)) {
+        Y = -Y;
+        X = -X;
+    }
+    if (Y == 0) return 0;   // 0 degrees, and the DC bin
+    if (X == 0) return (int)(((S + 1) / 2) % S);
+    if (Y == X) return (int)(((S + 2) / 4) % S);
+    if (Y == -X) return (int)(((3 * S + 2) / 4) % S);
+    const long double u = (long double)S * atan2l((long double)Y, (long double)X) / 3.14159265358979323846264338327950288L + 0.5L;
+    const long double f = floorl(u);
+    if (u - f < 0x1p-30L || f + 1.0L - u < 0x1p-30L) *too_close = true;
+    return (int)((int64_t)f % S);
+}
+
+// CSR over the cells c = ring * n_sectors + sector: cell_ptr [n_rings * n_sectors + 1], bins = ky * nx + kx in increasing order
+// within a cell; bins whose ring is >= n_rings belong to none.  false: a bin too close to a sector boundary (sector_of_bin)
+inline bool ring_build_sector_table(int ny, int nx, int n_rings, int n_sectors, std::vector<int>& cell_ptr, std::vector<int>& bins) {
+    const size_t cells = (size_t)n_rings * n_sectors;
+    std::vector<int> cell((size_t)ny * nx, -1);
+    cell_ptr.assign(cells + 1, 0);
+    bool too_close = false;
+    for (int ky = 0; ky < ny; ++ky)
+        for (int kx = 0; kx < nx; ++kx) {
+            const int r = ring_of_bin(ky, kx, ny, nx, n_rings);
+            if (r >= n_rings) continue;
+            const int c = r * n_sectors + sector_of_bin(ky, kx, ny, nx, n_sectors, &too_close);
+            cell[(size_t)ky * nx + kx] = c;
+            ++cell_ptr[(size_t)c + 1];
+        }
+    for (size_t c = 0; c < cells; ++c) cell_ptr[c + 1] += cell_ptr[c];
+    bins.assign((size_t)cell_ptr[cells], 0);
+    std::vector<int> at(cell_ptr.begin(), cell_ptr.end() - 1);
+    for (size_t i = 0; i < cell.size(); ++i)
+        if (cell[i] >= 0) bins[(size_t)at[(size_t)cell[i]]++] = (int)i;
+    return !too_close;
+}
+
+// ---- launchers (ring_kernels.hip, ring_sector_kernels.hip): `pairs` pairs on stream s; dtypes RL_F32 / RL_F64 of the two image buffers
 #if defined(__HIPCC__) || defined(__HIP_PLATFORM_AMD__)
 hipError_t ring_rows(int a_dtype, int b_dtype, const void* a, const void* b, const int64_t* a_off, const int64_t* b_off,
                      const double* scale, const void* wx, void* t_out, int ny, int nx, int pairs, hipStream_t s);
 hipError_t ring_cols(const void* t_in, const void* wy, void* f_out, int ny, int nx, int pairs, hipStream_t s);
 hipError_t ring_reduce(const void* f, const int* row_ptr, const int* bins, double* out, int ny, int nx, int n_rings, int pairs,
                        hipStream_t s);
+hipError_t ring_reduce_sectors(const void* f, const int* cell_ptr, const int* bins, double* out, int ny, int nx, int n_rings,
+                               int n_sectors, int pairs, hipStream_t s);
 #endif
 
 }  // namespace rl

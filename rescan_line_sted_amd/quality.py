@@ -12,6 +12,9 @@ read off them -- no counterpart in the reference:
   ring_stats(a, b, n_rings, scale)            [..., R, 5]: bins, sum |A|^2, sum |B|^2, sum Re(A conj B), sum |A - B|^2 per ring
   frc(a, b), frc_resolution(freq, curve)      Fourier ring correlation of two noise realisations, and where it crosses 1/7
   radial_fourier_error(estimate, true_object) the ring RMS of fourier_error
+  sector_stats(a, b, n_sectors, ...)          [..., R, S, 5]: the same fields per (ring, orientation sector) cell (rl_ring_sector_stats)
+  directional_fourier_error(estimate, true_object, n_sectors)   the cell RMS of fourier_error: one error profile per orientation
+  frc_resolution_by_angle(stats)              frc_resolution of each sector's curve
 
 ("ref2:NNN" = line numbers in figure_generation/line_sted_figure_2.py.)
 """
@@ -97,9 +100,8 @@ def ring_count(ny, nx):
     return int(lib.rl_ring_count(int(ny), int(nx)))
 
 
-def ring_stats_device(ctx, a_dev, a_dtype, a_offsets, b_dev, b_dtype, b_offsets, shape, scale=None, n_rings=None):
-    """rl_ring_stats on device buffers: image pair i = (a_dev + a_offsets[i], b_dev + b_offsets[i]), offsets in elements, all
-    images of `shape`; dtypes 'f32' / 'f64'; scale None or one value per pair.  Returns [n_pairs][R][5] float64."""
+def _stats_device(ctx, a_dev, a_dtype, a_offsets, b_dev, b_dtype, b_offsets, shape, scale, n_rings, n_sectors):
+    """rl_ring_stats (n_sectors None) or rl_ring_sector_stats on device buffers."""
     ny, nx = int(shape[0]), int(shape[1])
     R = ring_count(ny, nx) if n_rings is None else int(n_rings)
     a_off = np.ascontiguousarray(a_offsets, dtype=np.int64).ravel()
@@ -109,11 +111,28 @@ def ring_stats_device(ctx, a_dev, a_dtype, a_offsets, b_dev, b_dtype, b_offsets,
     sc = None
     if scale is not None:
         sc = as_f64(np.broadcast_to(np.asarray(scale, dtype=np.float64), a_off.shape))
-    out = np.empty((a_off.size, max(R, 0), RING_FIELDS))
     i64p = ctypes.POINTER(ctypes.c_int64)
-    check(lib.rl_ring_stats(ctx.handle, a_dev, DTYPES[a_dtype], a_off.ctypes.data_as(i64p), b_dev, DTYPES[b_dtype],
-                            b_off.ctypes.data_as(i64p), ptr(sc) if sc is not None else None, int(a_off.size), ny, nx, R, ptr(out)))
+    head = (ctx.handle, a_dev, DTYPES[a_dtype], a_off.ctypes.data_as(i64p), b_dev, DTYPES[b_dtype], b_off.ctypes.data_as(i64p),
+            ptr(sc) if sc is not None else None, int(a_off.size), ny, nx, R)
+    if n_sectors is None:
+        out = np.empty((a_off.size, max(R, 0), RING_FIELDS))
+        check(lib.rl_ring_stats(*head, ptr(out)))
+    else:
+        out = np.empty((a_off.size, max(R, 0), max(int(n_sectors), 0), RING_FIELDS))
+        check(lib.rl_ring_sector_stats(*head, int(n_sectors), ptr(out)))
     return out
+
+
+def ring_stats_device(ctx, a_dev, a_dtype, a_offsets, b_dev, b_dtype, b_offsets, shape, scale=None, n_rings=None):
+    """rl_ring_stats on device buffers: image pair i = (a_dev + a_offsets[i], b_dev + b_offsets[i]), offsets in elements, all
+    images of `shape`; dtypes 'f32' / 'f64'; scale None or one value per pair.  Returns [n_pairs][R][5] float64."""
+    return _stats_device(ctx, a_dev, a_dtype, a_offsets, b_dev, b_dtype, b_offsets, shape, scale, n_rings, None)
+
+
+def sector_stats_device(ctx, a_dev, a_dtype, a_offsets, b_dev, b_dtype, b_offsets, shape, n_sectors, scale=None, n_rings=None):
+    """rl_ring_sector_stats on device buffers: ring_stats_device with every ring cut into `n_sectors` orientation sectors (sector
+    j centred on j * 180 / n_sectors degrees, sector_angles).  Returns [n_pairs][R][S][5] float64; an empty cell is five zeros."""
+    return _stats_device(ctx, a_dev, a_dtype, a_offsets, b_dev, b_dtype, b_offsets, shape, scale, n_rings, int(n_sectors))
 
 
 def _stack(x, name):
@@ -125,10 +144,11 @@ def _stack(x, name):
     return x, False
 
 
-def ring_stats(a, b, n_rings=None, scale=None):
+def ring_stats(a, b, n_rings=None, scale=None, n_sectors=None):
     """The ring statistics of host images: a, b (ny, nx) or stacks (n, ny, nx); a single image on either side pairs with every image
     of the other.  scale: None (1), a number, or one per pair -- b is multiplied by it.  Returns (R, 5) for two single images, else
-    (n, R, 5).  The images are uploaded and go through the same entry point as device-resident ones."""
+    (n, R, 5); with n_sectors = S (sector_stats) (R, S, 5) and (n, R, S, 5).  The images are uploaded and go through the same entry
+    point as device-resident ones."""
     a, one_a = _stack(a, 'a')
     b, one_b = _stack(b, 'b')
     if a.shape[1:] != b.shape[1:]:
@@ -140,7 +160,8 @@ def ring_stats(a, b, n_rings=None, scale=None):
     da, db = DeviceResults.from_host(list(a), 'f64', _ctx().device), DeviceResults.from_host(list(b), 'f64', _ctx().device)
     try:
         out = da.ring_stats(np.arange(n) if a.shape[0] == n else np.zeros(n, dtype=np.int64), truth=db,
-                            truth_index=np.arange(n) if b.shape[0] == n else np.zeros(n, dtype=np.int64), scale=scale, n_rings=n_rings)
+                            truth_index=np.arange(n) if b.shape[0] == n else np.zeros(n, dtype=np.int64), scale=scale, n_rings=n_rings,
+                            n_sectors=n_sectors)
     finally:
         da.free()
         db.free()
@@ -152,8 +173,23 @@ def ring_frequencies(n_rings):
     return (np.arange(int(n_rings)) + 0.5) * 0.5 / int(n_rings)
 
 
+def sector_stats(a, b, n_sectors, n_rings=None, scale=None):
+    """ring_stats per (ring, orientation sector) cell: (R, S, 5) for two single images, else (n, R, S, 5)."""
+    return ring_stats(a, b, n_rings, scale, n_sectors=int(n_sectors))
+
+
+def sector_angles(n_sectors):
+    """The sector centres in degrees, j * 180 / S: measured from +kx towards +ky (error_vs_spatial_frequency's angle_degrees)."""
+    return np.arange(int(n_sectors)) * 180.0 / int(n_sectors)
+
+
+def rings_from_sectors(stats):
+    """[..., R, S, 5] -> [..., R, 5]: every field summed over the sectors of its ring."""
+    return np.asarray(stats, dtype=np.float64).sum(axis=-2)
+
+
 def frc_from_stats(stats):
-    """f3 / sqrt(f1 f2) along the last-but-one axis of [..., R, 5]; nan where a ring is empty or a denominator is 0."""
+    """f3 / sqrt(f1 f2) per ring of [..., R, 5] (per cell of [..., R, S, 5]); nan where a ring is empty or a denominator is 0."""
     stats = np.asarray(stats, dtype=np.float64)
     den = np.sqrt(stats[..., 1] * stats[..., 2])
     ok = (stats[..., 0] > 0) & (den > 0)
@@ -161,7 +197,8 @@ def frc_from_stats(stats):
 
 
 def radial_error_from_stats(stats, shape):
-    """sqrt(f4 / f0) / (ny nx): the RMS over each ring of |fft2(estimate) - fft2(scaled truth)| / (ny nx); nan for an empty ring."""
+    """sqrt(f4 / f0) / (ny nx): the RMS over each ring (each cell of [..., R, S, 5]) of |fft2(estimate) - fft2(scaled truth)| / (ny nx);
+    nan for an empty ring."""
     stats = np.asarray(stats, dtype=np.float64)
     ok = stats[..., 0] > 0
     return np.where(ok, np.sqrt(stats[..., 4] / np.where(ok, stats[..., 0], 1.0)) / (int(shape[0]) * int(shape[1])), np.nan)
@@ -199,3 +236,21 @@ def radial_fourier_error(estimate, true_object, n_rings=None):
     est = as_f64(estimate)
     st = ring_stats(est, true_object, n_rings)
     return ring_frequencies(st.shape[-2]), radial_error_from_stats(st, est.shape[-2:])
+
+
+def directional_fourier_error(estimate, true_object, n_sectors, n_rings=None):
+    """The RMS of fourier_error(estimate, true_object) over each (ring, orientation sector) cell: what error_vs_spatial_frequency
+    cuts out of the spectrum along one angle, for n_sectors angles at once.  Returns (frequencies in cycles/pixel at the ring
+    centres, sector centres in degrees, profile [R][S]); nan where a cell is empty."""
+    est = as_f64(estimate)
+    st = sector_stats(est, true_object, n_sectors, n_rings)
+    return ring_frequencies(st.shape[-3]), sector_angles(n_sectors), radial_error_from_stats(st, est.shape[-2:])
+
+
+def frc_resolution_by_angle(stats, threshold=1.0 / 7.0):
+    """frc_resolution of each sector's correlation curve of stats [R][S][5] (two noise realisations): [S] periods in pixels."""
+    curves = frc_from_stats(stats)
+    if curves.ndim != 2:
+        raise ValueError('expected the statistics of one pair, [R][S][5]')
+    freq = ring_frequencies(curves.shape[0])
+    return np.array([frc_resolution(freq, curves[:, j], threshold) for j in range(curves.shape[1])])

@@ -139,12 +139,13 @@ class DeviceResults:
         check(lib.rl_device_upload(out.ctx.handle, out.dev, DTYPES[dtype], out.n, ptr(np.ascontiguousarray(flat))))
         return out
 
-    def ring_stats(self, a_idx, b_idx=None, truth=None, truth_index=None, scale=None, n_rings=None):
+    def ring_stats(self, a_idx, b_idx=None, truth=None, truth_index=None, scale=None, n_rings=None, n_sectors=None):
         """Ring statistics (quality.ring_stats, include/rlsted.h rl_ring_stats) of image pairs without a download: images `a_idx`
         of this buffer against images `b_idx` of the same buffer (two seeds of a sweep), or against images `truth_index` (one
         index, or one per pair) of `truth`, another DeviceResults of this GPU (DeviceResults.from_host of the true objects).
         scale: None, a number or one per pair, multiplied into the b side.  All images of a call share one shape (ValueError
-        otherwise).  Returns [len(a_idx)][R][5] float64; synchronises this buffer's context, so whatever wrote the images must have
+        otherwise).  n_sectors = S: per (ring, orientation sector) cell (quality.sector_stats, rl_ring_sector_stats).  Returns
+        [len(a_idx)][R][5] float64, with sectors [len(a_idx)][R][S][5]; synchronises this buffer's context, so whatever wrote the images must have
         been synchronised (run_tasks_device has)."""
         a_idx = [int(i) for i in np.atleast_1d(a_idx)]
         if (b_idx is None) == (truth is None):
@@ -160,6 +161,9 @@ class DeviceResults:
         shape = self.shapes[a_idx[0]]
         if any(self.shapes[i] != shape for i in a_idx) or any(other.shapes[i] != shape for i in b_idx):
             raise ValueError('the images of one ring_stats call must share one shape')
+        if n_sectors is not None:
+            return quality.sector_stats_device(self.ctx, self.dev, self.dtype, self.offsets[a_idx], other.dev, other.dtype,
+                                               other.offsets[b_idx], shape, n_sectors, scale, n_rings)
         return quality.ring_stats_device(self.ctx, self.dev, self.dtype, self.offsets[a_idx], other.dev, other.dtype,
                                          other.offsets[b_idx], shape, scale, n_rings)
 
@@ -179,16 +183,17 @@ def _by_shape(shapes):
 
 
 def _pack_stats(per_task):
-    """An array [n][R][5] when every task has the same number of rings, otherwise the list."""
+    """An array [n][R][5] ([n][R][S][5] with sectors) when every task has the same number of rings, otherwise the list."""
     return np.stack(per_task) if per_task and len({s.shape for s in per_task}) == 1 else per_task
 
 
-def score_tasks(res, tasks, objects, total_brightness=5e10, n_rings=None):
+def score_tasks(res, tasks, objects, total_brightness=5e10, n_rings=None, n_sectors=None):
     """The ring statistics of every task's estimate in `res` (the DeviceResults of `tasks`) against its true object scaled to the
     simulated brightness, scale = total_brightness / object.sum() (create_data_from_object, line_sted_tools.py:505-506), on the
     device: each distinct object is uploaded once as float64, one rl_ring_stats call per image shape.  Returns [n_tasks][R][5]
     (fields: quality.ring_stats; quality.radial_error_from_stats turns field 4 into the ring RMS of the reference's fourier_error)
-    -- a list of per-task arrays when shapes with different numbers of rings are mixed."""
+    -- a list of per-task arrays when shapes with different numbers of rings are mixed.  n_sectors = S: angle-resolved, a task's
+    score is [R][S][5] (rl_ring_sector_stats; quality.rings_from_sectors sums it back to [R][5])."""
     names = sorted({o for o, _, _ in tasks})
     where = {n: i for i, n in enumerate(names)}
     imgs = [np.asarray(objects[n], dtype=np.float64).reshape(np.shape(objects[n])[-2:]) for n in names]
@@ -198,7 +203,7 @@ def score_tasks(res, tasks, objects, total_brightness=5e10, n_rings=None):
     try:
         for shape, idxs in _by_shape([res.shapes[i] for i in range(len(tasks))]).items():
             st = res.ring_stats(idxs, truth=truths, truth_index=[where[tasks[i][0]] for i in idxs],
-                                scale=[scales[tasks[i][0]] for i in idxs], n_rings=n_rings)
+                                scale=[scales[tasks[i][0]] for i in idxs], n_rings=n_rings, n_sectors=n_sectors)
             for k, i in enumerate(idxs):
                 out[i] = st[k]
     finally:
@@ -206,10 +211,11 @@ def score_tasks(res, tasks, objects, total_brightness=5e10, n_rings=None):
     return _pack_stats(out)
 
 
-def frc_between_seeds(res, tasks, seed_a, seed_b, n_rings=None):
+def frc_between_seeds(res, tasks, seed_a, seed_b, n_rings=None, n_sectors=None):
     """Fourier ring statistics between the two noise realisations `seed_a`, `seed_b` of every (object, PSF set) of `tasks` that
     has both, straight from `res`: returns (keys, stats) -- keys the (object, PSF set) pairs in task order of seed_a, stats
-    [len(keys)][R][5] (a list when ring counts differ); quality.frc_from_stats(stats) is the FRC curve."""
+    [len(keys)][R][5] (a list when ring counts differ); quality.frc_from_stats(stats) is the FRC curve.  n_sectors = S: stats
+    [len(keys)][R][S][5], one curve per orientation (quality.frc_resolution_by_angle)."""
     at = {t: i for i, t in enumerate(tasks)}
     keys = [(o, p) for o, p, s in tasks if s == int(seed_a) and (o, p, int(seed_b)) in at]
     if not keys:
@@ -218,7 +224,7 @@ def frc_between_seeds(res, tasks, seed_a, seed_b, n_rings=None):
     ib = [at[(o, p, int(seed_b))] for o, p in keys]
     out = [None] * len(keys)
     for shape, ks in _by_shape([res.shapes[i] for i in ia]).items():
-        st = res.ring_stats([ia[k] for k in ks], b_idx=[ib[k] for k in ks], n_rings=n_rings)
+        st = res.ring_stats([ia[k] for k in ks], b_idx=[ib[k] for k in ks], n_rings=n_rings, n_sectors=n_sectors)
         for j, k in enumerate(ks):
             out[k] = st[j]
     return keys, _pack_stats(out)
@@ -303,14 +309,14 @@ def run_tasks(tasks, objects, psf_sets, iterations, total_brightness=5e10, dtype
 
 
 def run_and_score_tasks(tasks, objects, psf_sets, iterations, total_brightness=5e10, dtype='f32', device=0, n_rings=None,
-                        acceleration=None, tv_lambda=None, tv_epsilon=0.1):
+                        acceleration=None, tv_lambda=None, tv_epsilon=0.1, n_sectors=None):
     """run_tasks, with every estimate scored on the device before the one download (score_tasks).  Returns (estimates, scores):
-    two lists in task order, scores[i] of shape (R_i, 5)."""
+    two lists in task order, scores[i] of shape (R_i, 5), with n_sectors = S (R_i, S, 5)."""
     order = sort_by_group(tasks, objects)
     sorted_tasks = [tasks[i] for i in order]
     res = run_tasks_device(sorted_tasks, objects, psf_sets, iterations, total_brightness, dtype, device,
                            acceleration=acceleration, tv_lambda=tv_lambda, tv_epsilon=tv_epsilon)
-    sc = score_tasks(res, sorted_tasks, objects, total_brightness, n_rings)
+    sc = score_tasks(res, sorted_tasks, objects, total_brightness, n_rings, n_sectors)
     est = res.download()
     res.free()
     out, scores = [None] * len(tasks), [None] * len(tasks)
@@ -342,7 +348,8 @@ def shard_sweep(tasks, objects, psf_sets, iterations, world):
 
 
 def figure_2_sweep(objects, psf_sets, seeds, iterations, total_brightness=5e10, dtype='f32',
-                   device=0, comm=None, info=None, acceleration=None, tv_lambda=None, tv_epsilon=0.1, scores=False, n_rings=None):
+                   device=0, comm=None, info=None, acceleration=None, tv_lambda=None, tv_epsilon=0.1, scores=False, n_rings=None,
+                   n_sectors=None):
     """The sweep, sharded over the ranks of `comm` (sharding.RcclComm, or anything with its
     interface) when given.  Returns (tasks, estimates) on rank 0 and (tasks, None) elsewhere;
     estimates is an array (n_tasks, ny, nx) when all objects share a shape, otherwise a list of
@@ -352,7 +359,8 @@ def figure_2_sweep(objects, psf_sets, seeds, iterations, total_brightness=5e10, 
     'biggs-andrews' (DeconvPlan.set_acceleration); tv_lambda, tv_epsilon: the total-variation regulariser (DeconvPlan.set_tv; None: off).
     scores=True: every rank also scores its own shard on the device (score_tasks, `n_rings` rings) before the gather, the small
     score arrays travel through `comm.gather`, and the function returns (tasks, estimates, scores) -- scores [n_tasks][R][5] in task
-    order (a list when ring counts differ) on rank 0, None elsewhere.  The estimates are those of scores=False."""
+    order (a list when ring counts differ) on rank 0, None elsewhere.  The estimates are those of scores=False.  n_sectors = S:
+    the scores are angle-resolved, [n_tasks][R][S][5] (score_tasks)."""
     tasks = make_tasks(objects, psf_sets, seeds)
     world = comm.world if comm is not None else 1
     rank = comm.rank if comm is not None else 0
@@ -369,13 +377,14 @@ def figure_2_sweep(objects, psf_sets, seeds, iterations, total_brightness=5e10, 
         if info is not None:
             info['unresolved_predictions_this_rank'] = unresolved_total(reset=True)
         if scores and mine:
-            mine_scores = score_tasks(res, mine, objects, total_brightness, n_rings)
+            mine_scores = score_tasks(res, mine, objects, total_brightness, n_rings, n_sectors)
         flat = comm.gather_device(res, pix, 0)       # root: host float64, rank-major; others: None
         res.free()
     else:
         if scores:
             local, mine_scores = run_and_score_tasks(mine, objects, psf_sets, iterations, total_brightness, dtype, device, n_rings,
-                                                     acceleration=acceleration, tv_lambda=tv_lambda, tv_epsilon=tv_epsilon) if mine else ([], [])
+                                                     acceleration=acceleration, tv_lambda=tv_lambda, tv_epsilon=tv_epsilon,
+                                                     n_sectors=n_sectors) if mine else ([], [])
         else:
             local = run_tasks(mine, objects, psf_sets, iterations, total_brightness, dtype, device,
                               acceleration=acceleration, tv_lambda=tv_lambda, tv_epsilon=tv_epsilon) if mine else []
@@ -386,15 +395,17 @@ def figure_2_sweep(objects, psf_sets, seeds, iterations, total_brightness=5e10, 
     all_scores = None
     if scores:
         rings = [quality.ring_count(*s) if n_rings is None else int(n_rings) for s in shapes]
+        cell = (quality.RING_FIELDS,) if n_sectors is None else (int(n_sectors), quality.RING_FIELDS)    # what a ring holds
+        per_ring = int(np.prod(cell))
         have = mine_scores is not None and len(mine_scores)
         sflat = np.concatenate([np.asarray(x, dtype=np.float64).ravel() for x in mine_scores]) if have else np.zeros(0)
         if comm is not None:
-            sflat = comm.gather(sflat, [sum(rings[i] for i in sh) * quality.RING_FIELDS for sh in shards], 0)
+            sflat = comm.gather(sflat, [sum(rings[i] for i in sh) * per_ring for sh in shards], 0)
         if sflat is not None:
             all_scores, o = [None] * len(tasks), 0
             for i in order:
-                k = rings[i] * quality.RING_FIELDS
-                all_scores[i] = np.asarray(sflat[o:o + k]).reshape(rings[i], quality.RING_FIELDS)
+                k = rings[i] * per_ring
+                all_scores[i] = np.asarray(sflat[o:o + k]).reshape((rings[i],) + cell)
                 o += k
             all_scores = _pack_stats(all_scores)
     if flat is None:

@@ -11,13 +11,20 @@ and two routes to the per-ring sum of |fft2(estimate) - fft2(scaled truth)|^2 of
   host    DeviceResults.download() + quality.fourier_error per image + numpy ring binning (np.bincount on a prepared table)
   device  sweep.score_tasks
 
+and, with --sectors S (the angle-resolved statistics, rl_ring_sector_stats), two more:
+
+  sectors sweep.score_tasks(n_sectors=S): ROWS and COLS are the launches of `device`, so the difference is k_ring_reduce_sectors
+          against k_ring_reduce plus S times the result bytes
+  angles  what the sectors replace: DeviceResults.download() + quality.error_vs_spatial_frequency at the figure's two angles (0 and
+          90 / num_angles degrees with num_angles = S / 2) per estimate
+
 warmed, alternated in one process, --repeats times each, a host clock around calls that end in a synchronise.  Prints every time, the
 median and the spread, the largest relative difference of the two routes' field 4, and the float64 operations of the two matrix
 products from the shapes (8 ny nx (nx + ny) per pair: a complex multiply-add is four fused multiply-adds).
 
-    python tools/gpu/ring_stats_bench.py [--workload 512|config4|both] [--repeats 5] [--out FILE]
-    rocprofv3 --kernel-trace --stats -d DIR --output-format csv -- python tools/gpu/ring_stats_bench.py --device-only --repeats 3
-    python tools/gpu/ring_stats_bench.py --rates DIR/.../kernel_stats.csv --device-only --repeats 3
+    python tools/gpu/ring_stats_bench.py [--workload 512|config4|both] [--repeats 5] [--sectors 6] [--out FILE]
+    rocprofv3 --kernel-trace --stats -d DIR --output-format csv -- python tools/gpu/ring_stats_bench.py --device-only --repeats 3 [--sectors 6]
+    python tools/gpu/ring_stats_bench.py --rates DIR/.../kernel_stats.csv --device-only --repeats 3 [--sectors 6]
       (the achieved FLOP/s of k_ring_rows / k_ring_cols in such a trace: the run's operation count over the kernels' total time)
 """
 import argparse
@@ -83,12 +90,25 @@ def host_route(res, tasks, objects, tables):
     return out
 
 
-def device_route(res, tasks, objects):
+def device_route(res, tasks, objects, sectors=None):
     from rescan_line_sted_amd import sweep
-    return sweep.score_tasks(res, tasks, objects, BRIGHT)
+    return sweep.score_tasks(res, tasks, objects, BRIGHT, n_sectors=sectors)
 
 
-def run(name, repeats, device_only, say):
+def angles_route(res, tasks, objects, sectors):
+    from rescan_line_sted_amd import quality
+    est = res.download()
+    worst = 90.0 / max(sectors // 2, 1)
+    return [[quality.error_vs_spatial_frequency(e, (BRIGHT / objects[o].sum()) * objects[o], ang) for ang in (0.0, worst)]
+            for (o, _, _), e in zip(tasks, est)]
+
+
+def scorings(repeats, sectors):
+    """score_tasks calls of one workload's run: the warm-up and `repeats`, of each device route."""
+    return (repeats + 1) * (2 if sectors else 1)
+
+
+def run(name, repeats, device_only, say, sectors=None):
     from rescan_line_sted_amd import sweep
     objects, psf_sets, seeds, iterations = workload(name)
     tasks = sweep.make_tasks(objects, psf_sets, seeds)
@@ -101,7 +121,13 @@ def run(name, repeats, device_only, say):
         % (name, len(tasks), sorted(set(shapes)), flops / 1e9, res.n * res.itemsize / 1e6))
     tables = {s: ring_table(*s) for s in set(shapes)}
     dev = device_route(res, tasks, objects)                        # warm-up of both routes (--rates counts this call too)
-    times = {'host': [], 'device': []}
+    times = {'host': [], 'device': [], 'sectors': [], 'angles': []}
+    if sectors:
+        cells = device_route(res, tasks, objects, sectors)
+        worst = max(float(np.max(np.abs(np.asarray(c).sum(axis=1)[:, 4] - np.asarray(d)[:, 4]) / np.asarray(d)[:, 4])) for c, d in zip(cells, dev))
+        say('%s: largest relative difference of field 4 between the sectors summed and the rings %.3g' % (name, worst))
+        if not device_only:
+            angles_route(res, tasks[:8], objects, sectors)
     if not device_only:
         host = host_route(res, tasks, objects, tables)
         worst = max(float(np.max(np.abs(np.asarray(d)[:, 4] - h) / np.maximum(np.abs(h), 1e-300))) for d, h in zip(dev, host))
@@ -114,13 +140,25 @@ def run(name, repeats, device_only, say):
         t = time.perf_counter()
         device_route(res, tasks, objects)
         times['device'].append(time.perf_counter() - t)
-    for route in ('host', 'device'):
+        if sectors:
+            t = time.perf_counter()
+            device_route(res, tasks, objects, sectors)
+            times['sectors'].append(time.perf_counter() - t)
+            if not device_only:
+                t = time.perf_counter()
+                angles_route(res, tasks, objects, sectors)
+                times['angles'].append(time.perf_counter() - t)
+    for route in ('host', 'device', 'sectors', 'angles'):
         ts = times[route]
         if ts:
-            say('%s %-6s ms: %s  median %.2f  min %.2f  max %.2f' % (name, route, ' '.join('%.2f' % (1e3 * x) for x in ts),
+            say('%s %-7s ms: %s  median %.2f  min %.2f  max %.2f' % (name, route, ' '.join('%.2f' % (1e3 * x) for x in ts),
                                                                      1e3 * float(np.median(ts)), 1e3 * min(ts), 1e3 * max(ts)))
     if times['host']:
         say('%s: host / device (medians) %.1f' % (name, float(np.median(times['host'])) / float(np.median(times['device']))))
+    if times['sectors']:
+        say('%s: sectors / device (medians) %.2f' % (name, float(np.median(times['sectors'])) / float(np.median(times['device']))))
+    if times['angles']:
+        say('%s: angles / sectors (medians) %.1f' % (name, float(np.median(times['angles'])) / float(np.median(times['sectors']))))
     res.free()
 
 
@@ -139,6 +177,7 @@ def main():
     ap.add_argument('--workload', default='both', choices=('512', 'config4', 'both'))
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--device-only', action='store_true')
+    ap.add_argument('--sectors', type=int, default=0, help='also time score_tasks(n_sectors=S) and the two-angle host route')
     ap.add_argument('--rates', default=None, help='kernel_stats.csv of a rocprofv3 trace of the same command line')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
@@ -151,10 +190,10 @@ def main():
             log.flush()
     names = ('512', 'config4') if a.workload == 'both' else (a.workload,)
     if a.rates:                                                    # no device work: the operation count of that command line
-        rates(a.rates, sum(product_flops(TASK_SHAPES[n]) for n in names) * (a.repeats + 1), say)
+        rates(a.rates, sum(product_flops(TASK_SHAPES[n]) for n in names) * scorings(a.repeats, a.sectors), say)
         return
     for n in names:
-        run(n, a.repeats, a.device_only, say)
+        run(n, a.repeats, a.device_only, say, a.sectors or None)
 
 
 if __name__ == '__main__':
