@@ -240,17 +240,23 @@ int rl_deconv_device_ptr(rl_deconv* h, int which, void** ptr, size_t* n_elements
  * the rounding error of a bright partner.  Any of the pointers may be NULL.                                  */
 int rl_deconv_strategy(const rl_deconv* h, int* separable, int* real_psf_spectrum, int* split_column_pass, int* frame_pairs);
 
-/* Frames that carry the same object are simulated once per slice of the batch.  Two frames are of one class when their
+/* Frames that carry the same object are simulated once per cycle.  Two frames are of one class when their
  * float64 input images (rl_deconv_set_object: compared with up to 8 earlier frames; rl_batch_run / rl_batch_submit: the tasks'
  * object pointers) and their brightness targets are the same: their scaled objects are then the same bits on the device, and so
- * is H(object).  A simulate + deconvolve cycle (rl_deconv_bench_cycles, rl_batch_run, rl_batch_submit; FFT path) computes H of
- * the first frame of each class within a slice when those are at most half the slice's frames, and every frame's Poisson draw
+ * is H(object).  A slice of the batch SHARES when the distinct classes within it are at most half its frames.  A simulate +
+ * deconvolve cycle (rl_deconv_bench_cycles, rl_batch_run, rl_batch_submit; FFT path) computes H once for each class that its
+ * sharing slices hold, before the first slice, and every frame's Poisson draw in such a slice
  * reads its class's rates with the frame's own Philox counters: measurements and estimates are bit for bit those of the
  * per-frame simulation (RLSTED_SHARE_OBJECTS=0).  The noiseless buffer is written in full before it is handed out
  * (rl_deconv_get_noiseless, rl_deconv_device_ptr which = 2); handing out the object buffer (which = 3) ends the sharing until
  * the next object is set.  *classes: classes of the object as last set (0: not known); *shared_slices of *slices: slices of the
- * last cycle that simulated representatives only.  Any of the pointers may be NULL.                                        */
+ * last cycle that shared.  Any of the pointers may be NULL.                                        */
 int rl_deconv_object_classes(const rl_deconv* h, int* classes, int* shared_slices, int* slices);
+
+/* Images H(object) was computed for in the last simulate + deconvolve cycle (rl_deconv_bench_cycles, rl_deconv_time_cycle, the last
+ * chunk of rl_batch_run / rl_batch_submit): n_psf per object class that the cycle's sharing slices hold -- a class is simulated once
+ * per cycle, however many slices draw from it -- plus n_psf per frame of the slices that do not share.  0 before the first cycle. */
+int rl_deconv_simulated_images(const rl_deconv* h, int* images);
 
 /* Predictions the plan could not resolve.  iterate divides the measurement by H(estimate) clamped at 0 (line_sted_tools.py:575,
  * 524); in exact arithmetic that prediction is positive, but a transform resolves a value to eps * the frame's maximum only, so

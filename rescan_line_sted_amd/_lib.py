@@ -85,6 +85,7 @@ PROTOTYPES = {
     'rl_host_free': (_i, [_vp]),
     'rl_deconv_strategy': (_i, [_vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)]),
     'rl_deconv_object_classes': (_i, [_vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)]),
+    'rl_deconv_simulated_images': (_i, [_vp, _c.POINTER(_i)]),
     'rl_deconv_unresolved': (_i, [_vp, _c.POINTER(_c.c_uint64), _i]),
     'rl_deconv_dims': (_i, [_vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)]),
     'rl_batch_run': (_i, [_vp, _vp, _i, _i, _i, _dp]),
@@ -277,6 +278,13 @@ class DeconvPlan:
         a, b, c = _i(), _i(), _i()
         check(lib.rl_deconv_object_classes(self.handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return {'classes': a.value, 'shared_slices': b.value, 'slices': c.value}
+
+    def simulated_images(self):
+        """Images H(object) was computed for in the last cycle (include/rlsted.h rl_deconv_simulated_images): a class that the
+        cycle's sharing slices hold counts once, whatever the number of slices that draw from it."""
+        a = _i()
+        check(lib.rl_deconv_simulated_images(self.handle, ctypes.byref(a)))
+        return a.value
 
     def set_object(self, obj, total_brightness=None):
         obj = as_f64(obj).reshape(self.B, self.ny, self.nx)

@@ -4,9 +4,9 @@
 // A batch often holds one object many times over -- a sweep's seeds, the benchmark's frames -- and H(object) of two such
 // frames is the same image bit for bit.  Frames are in one CLASS when their scaled objects are bit-identical by construction:
 // the same float64 input pixels and the same brightness target (the device scales a frame by target / sum, the sum taken in an
-// order that depends on the frame's pixels alone: aux_kernels.hip k_frame_sums).  Each slice of the batch then simulates the
-// first frame of each class it holds -- its representatives -- and the Poisson sampler draws every frame from its
-// representative's rates (rlsted.cpp run_slices).
+// order that depends on the frame's pixels alone: aux_kernels.hip k_frame_sums).  A slice of the batch in which few classes
+// cover many frames SHARES (share_layout); a cycle simulates each class its sharing slices hold once (class_layout), and the
+// Poisson sampler draws every frame of such a slice from its class's rates (rlsted.cpp run_slices).
 #pragma once
 
 #include <cstddef>
@@ -101,6 +101,37 @@ inline int share_layout(const std::vector<int>& cls, int cf, std::vector<SliceSh
             for (int i = 0; i < nf; ++i) rate_of[(size_t)(f0 + i)] = (uint32_t)(s.c0 + local[(size_t)i]);
         }
         slices.push_back(s);
+    }
+    return (int)rep_frames.size();
+}
+
+// One simulation per class and CYCLE: H(object) of a class is the same image in every slice, so the sharing slices of a
+// share_layout draw from ONE compact image per class instead of one per (slice, class).  Rewrites the layout in place:
+//   rep_frames[c] = the first frame of a sharing slice that carries compact class c   (returned count entries)
+//   rate_of[f]    = the compact class of frame f                                      (frames of sharing slices; 0 elsewhere)
+// Which slices share, and each slice's nrep, stay as share_layout decided; c0 no longer means anything and is zeroed.
+// Returns the number of compact classes: those that a sharing slice holds, numbered in order of first appearance.
+inline int class_layout(const std::vector<int>& cls, int cf, std::vector<SliceShare>& slices, std::vector<uint32_t>& rep_frames,
+                        std::vector<uint32_t>& rate_of) {
+    const int B = (int)cls.size();
+    rep_frames.clear();
+    rate_of.assign((size_t)B, 0u);
+    if (cf < 1) cf = 1;
+    int n_cls = 0;
+    for (int c : cls) n_cls = c + 1 > n_cls ? c + 1 : n_cls;
+    std::vector<int> compact((size_t)n_cls, -1);
+    for (size_t sl = 0; sl < slices.size(); ++sl) {
+        slices[sl].c0 = 0;
+        if (slices[sl].nrep == 0) continue;
+        const int f0 = (int)sl * cf;
+        for (int f = f0; f < f0 + cf && f < B; ++f) {
+            int& c = compact[(size_t)cls[(size_t)f]];
+            if (c < 0) {
+                c = (int)rep_frames.size();
+                rep_frames.push_back((uint32_t)f);
+            }
+            rate_of[(size_t)f] = (uint32_t)c;
+        }
     }
     return (int)rep_frames.size();
 }

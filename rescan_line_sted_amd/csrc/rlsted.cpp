@@ -872,7 +872,9 @@ struct rl_deconv {
         for (int l = 0; l < opt.lanes; ++l) {
             HIP_TRY(hipStreamCreateWithFlags(&lane_stream[l], hipStreamNonBlocking));
             HIP_TRY(hipEventCreateWithFlags(&lane_done[l], hipEventDisableTiming));
+            HIP_TRY(hipEventCreateWithFlags(&lane_drawn[l], hipEventDisableTiming));
         }
+        HIP_TRY(hipEventCreateWithFlags(&rates_ready, hipEventDisableTiming));
         return RL_OK;
     }
     // ---- one iteration = four passes (stencil plans: sep_iterate).  Each pass picks its variant from the plan: the pair loop -- the
@@ -943,11 +945,13 @@ struct rl_deconv {
         RL_TRY(row(ROW_INV, (unsigned)(nf * V), sb, nullptr, nullptr, out, nullptr));
         return RL_OK;
     }
-    // ---- shared simulation (object_classes.hpp): frames that carry the same object are one class, and a slice of the batch
-    // computes H(object) of the first frame of each class it holds instead of every frame's -- the benchmark's batch and a sweep's
-    // seeds are one object many times over.  The representatives' objects and rates live in two compact buffers, a slice's
-    // side by side; the Poisson sampler reads every frame's rates through rate_of.  `noiseless` itself is then not written: it is
-    // filled from the compact rates when somebody asks for it (expand_noiseless).  RLSTED_SHARE_OBJECTS=0: off.
+    // ---- shared simulation (object_classes.hpp): frames that carry the same object are one class -- the benchmark's batch and a
+    // sweep's seeds are one object many times over -- and a simulate + deconvolve cycle computes H(object) ONCE per class that its
+    // sharing slices hold (forward_classes, at the start of the cycle) instead of every frame's.  The classes' objects and rates
+    // live in two compact buffers indexed by class; the Poisson sampler of a sharing slice reads every frame's rates through
+    // rate_of.  `noiseless` itself is then not written: it is filled from the compact rates when somebody asks for it
+    // (expand_noiseless).  Which slices share is share_layout's rule (representatives at most half the slice's frames); the others
+    // simulate every frame as they always did.  RLSTED_SHARE_OBJECTS=0: off.
     std::vector<int> obj_class;            // class of every frame of the object as it was set; empty: not known, nothing is shared
     int n_classes = 0;
     std::vector<SliceShare> share_slices;  // the layout for slices of share_cf frames (0: none built for the object at hand)
@@ -957,7 +961,16 @@ struct rl_deconv {
     ShareLists share_lists{nullptr, nullptr};
     unsigned* share_dev = nullptr;         // [2][B] the plan's own lists
     void *obj_c = nullptr, *noiseless_c = nullptr;   // [share_cap] objects, [share_cap * V] rates
+    // spectrum space of the class simulation, its own: the slices' parts of spec_a / spec_b / spec_x belong to the lanes' loops
+    void *cls_spec_a = nullptr, *cls_spec_b = nullptr, *cls_spec_x = nullptr;   // [share_cap], [share_cap * V], [share_cap * V] (split plans)
     size_t share_cap = 0;
+    int share_classes = 0;                 // compact images in use: the classes the sharing slices of the layout hold
+    // Order between the class simulation and the draws on other lanes (run_slices): the lanes wait for rates_ready before their first
+    // shared draw of a cycle; the simulation of the NEXT cycle waits for lane_drawn[l], recorded behind lane l's last shared draw.
+    hipEvent_t rates_ready = nullptr;
+    hipEvent_t lane_drawn[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr};
+    bool lane_drawn_set[kMaxLanes] = {false, false, false, false};
+    int last_sim_images = 0;               // images H was computed for in the last cycle (rl_deconv_simulated_images)
     bool noiseless_sparse = false;         // the last simulation left (some) slices' rates in noiseless_c only
     int last_shared_slices = 0, last_slices = 0;
     bool share_possible() const { return opt.share_objects && !sep && (int)obj_class.size() == B && n_classes < B; }
@@ -967,15 +980,27 @@ struct rl_deconv {
     int build_share(int cf, const ShareLists* staged) {
         share_cf = 0;
         noiseless_sparse = false;   // (whatever an earlier layout left is replaced by the simulation that follows)
-        const size_t total = (size_t)share_layout(obj_class, cf, share_slices, share_reps, share_rate);
+        share_classes = 0;
+        share_layout(obj_class, cf, share_slices, share_reps, share_rate);
+        const size_t total = (size_t)class_layout(obj_class, cf, share_slices, share_reps, share_rate);
         if (total > share_cap) {   // (grow only; in groups of 8 images)
             HIP_TRY(hipDeviceSynchronize());
             share_cap = 0;
             RL_TRY(release(&obj_c));
             RL_TRY(release(&noiseless_c));
-            const size_t cap = (total + 7) / 8 * 8;
+            RL_TRY(release(&cls_spec_a));
+            RL_TRY(release(&cls_spec_b));
+            RL_TRY(release(&cls_spec_x));
+            const size_t cap = (total + 7) / 8 * 8, sp = n_spec() * 2 * esize(dtype);
             RL_TRY(alloc(&obj_c, cap * n_img() * esize(dtype), SLACK));
             RL_TRY(alloc(&noiseless_c, cap * V * n_img() * esize(dtype), SLACK));
+            if (!pair_layout) RL_TRY(alloc(&cls_spec_a, cap * sp, SLACK));   // (a pair plan simulates in place unless its frames' levels forbid pairs: forward_classes)
+            RL_TRY(alloc(&cls_spec_b, cap * V * sp, SLACK));
+            if (col_split()) {
+                const size_t parked_bytes = cap * V * n_spec_x() * 2 * esize(dtype);
+                RL_TRY(alloc(&cls_spec_x, parked_bytes));
+                HIP_TRY(hipMemsetAsync(cls_spec_x, 0, parked_bytes, ctx->stream));
+            }
             share_cap = cap;
         }
         if (staged) {
@@ -989,13 +1014,29 @@ struct rl_deconv {
         HIP_TRY(aux_gather_images(dtype, obj, obj_c, share_lists.rep_frames, n_img(), total, 1, ctx->stream));
         if (!staged) HIP_TRY(hipStreamSynchronize(ctx->stream));   // the host lists are the plan's to change again
         share_cf = cf;
+        share_classes = (int)total;
         return RL_OK;
+    }
+    // noiseless_c [n * V] = H(obj_c [n]): the launches forward_frames runs over a slice's frames (the split pass on a split plan:
+    // see forward_object), in the class simulation's own spectrum space
+    int forward_classes(int n) {
+        void* sb = cls_spec_b;
+        if (!pair && !cls_spec_a) {   // a pair plan whose frames at hand run the per-frame loop (choose_loop): first use
+            RL_TRY(alloc(&cls_spec_a, share_cap * n_spec() * 2 * esize(dtype), SLACK));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));   // (the zeroed slack, before another stream's kernels read past the end)
+        }
+        void* sa = !pair ? cls_spec_a : sb;   // (as forward_frames does)
+        RL_TRY(row(ROW_FWD, (unsigned)n, nullptr, sa, obj_c, nullptr, nullptr));
+        if (col_split()) RL_TRY(col_split_pass(sa, sb, cls_spec_x, n, COL_H));
+        else RL_TRY(col(sa, sb, n, COL_H));
+        return row(ROW_INV, (unsigned)(n * V), sb, nullptr, nullptr, noiseless_c, nullptr);
     }
     // the object was (or may have been) replaced: nothing is known about its frames until somebody classifies them
     void forget_classes() {
         obj_class.clear();
         n_classes = 0;
         share_cf = 0;
+        share_classes = 0;
     }
     // every frame's rates into `noiseless`, where a shared simulation left them in the compact buffer (on the context's stream)
     int expand_noiseless() {
@@ -1056,17 +1097,46 @@ struct rl_deconv {
             hipStream_t& a;
             ~ActiveGuard() { a = nullptr; }
         } active_guard{active};
-        int shared_slices = 0;
+        int shared_slices = 0, sim_images = 0;
+        auto hip_rc = [&](hipError_t e, const char* what) -> int {
+            return e == hipSuccess ? RL_OK : fail(RL_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+        };
+        // The cycle's class simulation: H of every class the sharing slices hold, once, on the stream that starts the cycle's first
+        // slice.  It replaces the rates the cycle before drew from, so it first waits for that cycle's last shared draw on every
+        // lane (lanes that stay open between cycles do not meet otherwise); the other lanes wait for it before their first shared draw.
+        bool lane_waits[kMaxLanes] = {false, false, false, false};   // lane l has yet to wait for rates_ready
+        int lane_last_shared[kMaxLanes] = {-1, -1, -1, -1};          // the last sharing slice that goes to lane l
+        if (share && share_classes > 0) {
+            active = nl > 1 ? lane_stream[0] : nullptr;
+            for (int l = 0; l < kMaxLanes && rc == RL_OK; ++l) {
+                if (!lane_drawn_set[l]) continue;
+                lane_drawn_set[l] = false;
+                rc = hip_rc(hipStreamWaitEvent(cur(), lane_drawn[l], 0), "class simulation");
+            }
+            if (rc == RL_OK) rc = forward_classes(share_classes);
+            sim_images += share_classes * V;
+            if (nl > 1 && rc == RL_OK) {
+                rc = hip_rc(hipEventRecord(rates_ready, cur()), "class simulation");
+                for (int l = 1; l < nl; ++l) lane_waits[l] = true;
+                for (int sl = 0; sl < slices; ++sl)
+                    if (share_slices[(size_t)sl].nrep > 0) lane_last_shared[sl % nl] = sl;
+            }
+        }
         auto simulate_slice = [&](int sl, int f0, int nf) -> int {
-            // a sharing slice: H of its representatives' objects alone, into the compact rates that every frame of the slice draws from
+            // a sharing slice: every frame draws from its class's rates, which the class simulation above left in the compact buffer
             const SliceShare ss = share ? share_slices[(size_t)sl] : SliceShare{};
             const void* rates = off(noiseless, (size_t)f0 * V * n_img());
+            const int lane = nl > 1 ? sl % nl : 0;
             if (ss.nrep > 0) {
-                RL_TRY(forward_frames(f0, ss.nrep, off(obj_c, (size_t)ss.c0 * n_img()), off(noiseless_c, (size_t)ss.c0 * V * n_img())));
+                if (lane_waits[lane]) {
+                    HIP_TRY(hipStreamWaitEvent(cur(), rates_ready, 0));
+                    lane_waits[lane] = false;
+                }
                 rates = noiseless_c;
                 ++shared_slices;
             } else {
                 RL_TRY(forward_slice(f0, nf));
+                sim_images += nf * V;
             }
             void* ws = (char*)slice_ws + (size_t)sl * slice_ws_stride;   // this slice's Poisson work list
             TimedScope t(this, TK_POISSON, false);
@@ -1075,6 +1145,10 @@ struct rl_deconv {
                                        draw->key_seeds ? draw->key_seeds + f0 : nullptr, draw->key_ids ? draw->key_ids + f0 : nullptr, (unsigned)V,
                                        ss.nrep > 0 ? share_lists.rate_of + f0 : nullptr);
             if (e != hipSuccess) return fail(RL_ERR_HIP, std::string("Poisson kernels: ") + hipGetErrorString(e));
+            if (lane_last_shared[lane] == sl) {   // (several lanes only)
+                HIP_TRY(hipEventRecord(lane_drawn[lane], cur()));
+                lane_drawn_set[lane] = true;
+            }
             return RL_OK;
         };
         // (Round 1 also tried the simulation of all slices ahead of the RL lanes on a stream of its own: 16.5 k against 17.2 k
@@ -1113,6 +1187,7 @@ struct rl_deconv {
             noiseless_sparse = shared_slices > 0;
             last_shared_slices = shared_slices;
             last_slices = slices;
+            last_sim_images = sim_images;
         }
         if (restart) {
             est_ready = true;
@@ -1227,8 +1302,10 @@ int rl_deconv_destroy(rl_deconv* h) {
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->fork) (void)hipEventDestroy(h->fork);
+    if (h->rates_ready) (void)hipEventDestroy(h->rates_ready);
     for (int l = 0; l < kMaxLanes; ++l) {
         if (h->lane_done[l]) (void)hipEventDestroy(h->lane_done[l]);
+        if (h->lane_drawn[l]) (void)hipEventDestroy(h->lane_drawn[l]);
         if (h->lane_stream[l]) (void)hipStreamDestroy(h->lane_stream[l]);
     }
     delete h;
@@ -1828,6 +1905,12 @@ int rl_deconv_object_classes(const rl_deconv* h, int* classes, int* shared_slice
     return RL_OK;
 }
 
+int rl_deconv_simulated_images(const rl_deconv* h, int* images) {
+    if (!h || !images) return fail(RL_ERR_INVALID, "NULL argument");
+    *images = h->last_sim_images;
+    return RL_OK;
+}
+
 int rl_deconv_unresolved(rl_deconv* h, unsigned long long* count, int reset) {
     if (!h || !count) return fail(RL_ERR_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(h->ctx->device));
@@ -1908,6 +1991,7 @@ int rl_batch_submit(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_iters
         const int cf = h->chunk_frames();
         if (share) {
             share_layout(h->obj_class, cf, h->share_slices, h->share_reps, h->share_rate);
+            class_layout(h->obj_class, cf, h->share_slices, h->share_reps, h->share_rate);
             std::copy(h->share_reps.begin(), h->share_reps.end(), lists);
             std::copy(h->share_rate.begin(), h->share_rate.end(), lists + B);
         }
@@ -2036,7 +2120,7 @@ int rl_deconv_device_ptr(rl_deconv* h, int which, void** ptr, size_t* n_elements
             h->meas_level.clear();
             h->meas_external = true;
             break;
-        case 2:   // (a shared simulation left one image per class and slice: every frame's is written now)
+        case 2:   // (a shared simulation left one image per class: every frame's is written now)
             HIP_TRY(hipSetDevice(h->ctx->device));
             RL_TRY(h->expand_noiseless());
             p = h->noiseless;
