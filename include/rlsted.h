@@ -472,6 +472,35 @@ int rl_ring_sector_stats(rl_ctx* ctx, const void* a_dev, int a_dtype, const int6
                          const int64_t* b_offsets, const double* b_scale, int n_pairs, int ny, int nx, int n_rings,
                          int n_sectors, double* out);
 
+/* ---- ensemble statistics: per-pixel mean, variance, squared bias and mean squared error over groups of images ----
+ * What the noise realisations of one (object, PSF set) operating point of a sweep say together, without downloading an image:
+ * the error of the ensemble split into what the blur leaves (bias^2) and what the noise adds (variance).
+ * Group g is the n = group_ptr[g + 1] - group_ptr[g] images of n_pixels contiguous values of src_dtype (RL_F32 / RL_F64) at the
+ * ELEMENT offsets member_offsets[group_ptr[g] .. group_ptr[g + 1]) of src_dev (host arrays; any offset >= 0, no alignment
+ * assumed; groups may differ in size and an image may be listed in many groups; no cap on n).  truth_dev: NULL, or a device
+ * buffer of truth_dtype whose n_pixels values at element offset truth_offsets[g], times truth_scale[g] (NULL: 1), are the
+ * group's true image s t.  Per pixel, every value widened to float64 before any arithmetic, no contraction, the members
+ * x_0 ... x_{n-1} in list order:
+ *     mean = ((((0 + x_0) + x_1) + ...) + x_{n-1}) / n
+ *     ss   = sum_m (x_m - mean)^2                      a second pass over the members, same order
+ *     var  = n > 1 ? ss / (n - 1) : 0
+ *     bias = mean - s t,  b2 = bias * bias
+ *     mse  = (sum_m (x_m - s t)^2) / n                 (= b2 + (n - 1) / n var, up to rounding)
+ * Without a truth b2 = mse = 0.
+ * mean_dev, var_dev: device float64 [n_groups][n_pixels], either may be NULL; neither may overlap the member images.
+ * out: host [n_groups][RL_ENSEMBLE_FIELDS], sums over the group's pixels:
+ *     0  n      1  sum mean      2  sum var      3  sum b2      4  sum mse      5  sum (s t)^2
+ * in a fixed order (ensemble_kernels.hpp) that n_pixels and src_dtype alone decide, no floating-point atomics: bit-identical
+ * from run to run, and a group's numbers do not depend on the other groups of the call.
+ * The tables and the partial sums live in a workspace kept in the context and freed with it.  Synchronises the context's stream.
+ * RL_ERR_INVALID: a NULL ctx / src_dev / member_offsets / group_ptr / out, n_groups < 1, group_ptr[0] < 0, an empty or
+ * decreasing group_ptr range, n_pixels < 1, a dtype that is neither, a negative offset, truth_dev without truth_offsets, a map
+ * that overlaps the member images.                                                                                          */
+#define RL_ENSEMBLE_FIELDS 6
+int rl_ensemble_stats(rl_ctx* ctx, const void* src_dev, int src_dtype, const int64_t* member_offsets, const int32_t* group_ptr,
+                      int n_groups, const void* truth_dev, int truth_dtype, const int64_t* truth_offsets,
+                      const double* truth_scale, size_t n_pixels, double* mean_dev, double* var_dev, double* out);
+
 /* ---- line_sted_figure_3.py: the scan-position-by-scan-position imaging simulator (:76-273) ----
  * rl_rotate_image: `rotate` (:382-391) for one [ny][nx] plane -- scipy.ndimage.rotate(order 3,
  * mode 'nearest', reshape=False) about the centre; clip != 0 clips to [0, 1.1 * max(in)].  Host in / out. */

@@ -120,6 +120,8 @@ PROTOTYPES = {
     'rl_ring_count': (_i, [_i, _i]),
     'rl_ring_stats': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _vp, _i, _c.POINTER(_c.c_int64), _dp, _i, _i, _i, _i, _dp]),
     'rl_ring_sector_stats': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _vp, _i, _c.POINTER(_c.c_int64), _dp, _i, _i, _i, _i, _i, _dp]),
+    'rl_ensemble_stats': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int32), _i, _vp, _i, _c.POINTER(_c.c_int64), _dp,
+                               _c.c_size_t, _vp, _vp, _dp]),
 }
 
 

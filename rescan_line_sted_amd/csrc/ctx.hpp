@@ -84,6 +84,16 @@ struct rl_ctx {
         }
     } ring;
 
+    // rl_ensemble_stats (ensemble_api.cpp): a grow-only workspace for the offset tables, the partials and the totals; freed with
+    // the context
+    struct EnsembleWork {
+        void* work = nullptr;
+        size_t work_bytes = 0;
+        ~EnsembleWork() {
+            if (work) (void)hipFree(work);
+        }
+    } ensemble;
+
     int device = 0;
     hipStream_t stream = nullptr;
     std::map<std::pair<int, int>, void*> tw;   // (L, dtype) -> device table

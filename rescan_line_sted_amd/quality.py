@@ -254,3 +254,102 @@ def frc_resolution_by_angle(stats, threshold=1.0 / 7.0):
         raise ValueError('expected the statistics of one pair, [R][S][5]')
     freq = ring_frequencies(curves.shape[0])
     return np.array([frc_resolution(freq, curves[:, j], threshold) for j in range(curves.shape[1])])
+
+
+# ------------------------------------------------------------------ ensemble statistics
+ENSEMBLE_FIELDS = 6
+
+
+def ensemble_stats_device(ctx, dev, dtype, groups_offsets, n_pixels, truth=None, mean_dev=None, var_dev=None):
+    """rl_ensemble_stats (include/rlsted.h) on a device buffer: group g is the images of `n_pixels` values at the element offsets
+    groups_offsets[g] (a list of offset lists; groups may differ in size) of `dev`, dtype 'f32' / 'f64'.  truth: None, or
+    (truth_dev, truth_dtype, truth_offsets, scale) -- one element offset per group and scale None, a number or one per group.
+    mean_dev, var_dev: None, or device float64 [G][n_pixels] that receive the per-pixel mean and unbiased variance.
+    Returns [G][6] float64: n, and the pixel sums of mean, variance, bias^2, mean squared error and (scaled truth)^2."""
+    groups = [np.ascontiguousarray(g, dtype=np.int64).ravel() for g in groups_offsets]
+    G = len(groups)
+    gp = np.zeros(G + 1, dtype=np.int32)
+    gp[1:] = np.cumsum([g.size for g in groups]) if G else []
+    off = np.ascontiguousarray(np.concatenate(groups)) if G else np.zeros(0, dtype=np.int64)
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    t_dev, t_dtype, t_off, sc = None, 0, None, None
+    if truth is not None:
+        t_dev, t_name, t_offsets, scale = truth
+        t_dtype = DTYPES[t_name]
+        t_off = np.ascontiguousarray(t_offsets, dtype=np.int64).ravel()
+        if t_off.size != G:
+            raise ValueError('one truth offset per group; got %d for %d groups' % (t_off.size, G))
+        if scale is not None:
+            sc = as_f64(np.broadcast_to(np.asarray(scale, dtype=np.float64), (G,)))
+    out = np.empty((G, ENSEMBLE_FIELDS))
+    check(lib.rl_ensemble_stats(ctx.handle, dev, DTYPES[dtype], off.ctypes.data_as(i64p), gp.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                G, t_dev, t_dtype, t_off.ctypes.data_as(i64p) if t_off is not None else None,
+                                ptr(sc) if sc is not None else None, int(n_pixels), mean_dev, var_dev, ptr(out)))
+    return out
+
+
+def ensemble_stats(stack, truth=None, scale=None):
+    """The ensemble statistics of host images: `stack` (n, ...) -- n members of one group, any image shape -- or a list of such
+    stacks, one per group (the groups may differ in n, not in image shape).  truth: None, one image, or one per group; scale: None
+    (1), a number or one per group, multiplied into the truth.  Returns (mean, variance, scalars): the float64 maps of the image
+    shape and [6] (ensemble_stats_device) for a single stack, with a leading group axis for a list.  The images are uploaded and go
+    through the same entry point as device-resident ones."""
+    single = not isinstance(stack, (list, tuple))
+    stacks = [as_f64(s) for s in ([stack] if single else stack)]
+    if not stacks or any(s.ndim < 2 or s.shape[0] < 1 for s in stacks):
+        raise ValueError('expected a stack (n, ...) of n >= 1 images, or a list of them')
+    shape = stacks[0].shape[1:]
+    if any(s.shape[1:] != shape for s in stacks):
+        raise ValueError('the groups differ in image shape')
+    flat = (int(np.prod(shape)), 1)
+    from .sweep import DeviceResults                     # (sweep imports this module)
+    members = [im.reshape(flat) for s in stacks for im in s]
+    groups, at = [], 0
+    for s in stacks:
+        groups.append(list(range(at, at + s.shape[0])))
+        at += s.shape[0]
+    src = DeviceResults.from_host(members, 'f64', _ctx().device)
+    tr = None
+    try:
+        if truth is not None:
+            t = as_f64(truth)
+            t = t.reshape((-1,) + flat) if t.shape != shape else t.reshape((1,) + flat)
+            if t.shape[0] not in (1, len(stacks)):
+                raise ValueError('one truth image, or one per group')
+            tr = DeviceResults.from_host(list(t), 'f64', _ctx().device)
+            t_idx = np.arange(len(stacks)) if t.shape[0] == len(stacks) else np.zeros(len(stacks), dtype=np.int64)
+            means, variances, sc = src.ensemble(groups, truth=tr, truth_index=t_idx, scale=scale)
+        else:
+            means, variances, sc = src.ensemble(groups)
+        try:
+            m = np.stack(means.download()).reshape((len(stacks),) + shape)
+            v = np.stack(variances.download()).reshape((len(stacks),) + shape)
+        finally:
+            means.free()
+            variances.free()
+    finally:
+        src.free()
+        if tr is not None:
+            tr.free()
+    return (m[0], v[0], sc[0]) if single else (m, v, sc)
+
+
+def spectral_bias_variance_rms(spectrum, shape):
+    """[..., 3] (bin count, bias power, variance power per ring or per (ring, sector) cell: sweep.bias_variance_spectrum) ->
+    (bias RMS, noise RMS), each sqrt(power / count) / (ny nx): the units of radial_error_from_stats; nan for an empty ring."""
+    spectrum = np.asarray(spectrum, dtype=np.float64)
+    ok = spectrum[..., 0] > 0
+    cnt = np.where(ok, spectrum[..., 0], 1.0)
+    pix = int(shape[0]) * int(shape[1])
+    return (np.where(ok, np.sqrt(spectrum[..., 1] / cnt) / pix, np.nan), np.where(ok, np.sqrt(spectrum[..., 2] / cnt) / pix, np.nan))
+
+
+def ssnr_from(mean_stats, spectrum, n):
+    """The spectral signal-to-noise ratio of an n-member ensemble mean per ring (or cell): field 1 of the ring statistics of the
+    mean image (sum |fft2(mean)|^2: mean_stats [..., 5]) over the variance power of `spectrum` [..., 3] divided by n (the noise
+    power left in a mean of n).  nan for an empty ring or a variance power of 0."""
+    mean_stats = np.asarray(mean_stats, dtype=np.float64)
+    spectrum = np.asarray(spectrum, dtype=np.float64)
+    noise = spectrum[..., 2] / float(n)
+    ok = (spectrum[..., 0] > 0) & (noise > 0)
+    return np.where(ok, mean_stats[..., 1] / np.where(ok, noise, 1.0), np.nan)

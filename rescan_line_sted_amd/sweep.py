@@ -128,7 +128,19 @@ class DeviceResults:
         """ONE device-to-host transfer; the list of (ny, nx) float64 estimates."""
         flat = np.empty(self.n, dtype=np.float64)
         check(lib.rl_device_download(self.ctx.handle, self.dev, DTYPES[self.dtype], self.n, ptr(flat)))
-        return split_flat(flat, self.shapes)
+        return [flat[int(o):int(o) + sh[0] * sh[1]].reshape(sh) for o, sh in zip(self.offsets, self.shapes)]
+
+    @classmethod
+    def with_layout(cls, shapes, order, dtype='f64', device=0):
+        """A buffer whose images lie in memory in the order `order` (a permutation of the indices) while image i keeps index i:
+        what lets the images of one shape be neighbours (the [G][n_pixels] maps of one rl_ensemble_stats call) whatever their
+        indices.  offsets[i] is still image i's element offset; there is no offsets[len(shapes)]."""
+        shapes = [tuple(s) for s in shapes]
+        out = cls([shapes[i] for i in order], dtype, device)
+        offsets = np.zeros(len(shapes), dtype=np.int64)
+        offsets[list(order)] = out.offsets[:-1]
+        out.shapes, out.offsets = shapes, offsets
+        return out
 
     @classmethod
     def from_host(cls, images, dtype='f64', device=0):
@@ -166,6 +178,49 @@ class DeviceResults:
                                                other.offsets[b_idx], shape, n_sectors, scale, n_rings)
         return quality.ring_stats_device(self.ctx, self.dev, self.dtype, self.offsets[a_idx], other.dev, other.dtype,
                                          other.offsets[b_idx], shape, scale, n_rings)
+
+    def _ensemble_into(self, groups, truth, truth_index, scale, mean_ptr, var_ptr):
+        """One rl_ensemble_stats call on the images `groups` (index lists) of this buffer; the maps go to the device addresses
+        given (None: not written).  Returns [G][6]."""
+        groups = [[int(i) for i in np.atleast_1d(g)] for g in groups]
+        if not groups or any(not g for g in groups):
+            raise ValueError('no groups, or an empty group')
+        shape = self.shapes[groups[0][0]]
+        if any(self.shapes[i] != shape for g in groups for i in g):
+            raise ValueError('the images of one ensemble call must share one shape')
+        t = None
+        if truth is not None:
+            if truth.ctx.device != self.ctx.device:
+                raise ValueError('truth lives on another device')
+            t_idx = np.zeros(len(groups), dtype=np.int64) if truth_index is None else truth_index
+            t_idx = [int(i) for i in np.broadcast_to(np.atleast_1d(t_idx), (len(groups),))]
+            if any(truth.shapes[i] != shape for i in t_idx):
+                raise ValueError('the images of one ensemble call must share one shape')
+            t = (truth.dev, truth.dtype, truth.offsets[t_idx], scale)
+        return quality.ensemble_stats_device(self.ctx, self.dev, self.dtype, [self.offsets[g] for g in groups], shape[0] * shape[1],
+                                             truth=t, mean_dev=mean_ptr, var_dev=var_ptr)
+
+    def ensemble(self, groups, truth=None, truth_index=None, scale=None, maps=True):
+        """Ensemble statistics (quality.ensemble_stats, include/rlsted.h rl_ensemble_stats) without a download: group g is the
+        images `groups[g]` (a list of index lists; the groups may differ in size) of this buffer -- the seeds of one operating
+        point of a sweep.  truth: None, or another DeviceResults of this GPU whose image `truth_index` (one index, or one per
+        group), times `scale` (None, a number or one per group), is the group's true image.  All images of a call share one shape
+        (ValueError otherwise).  Returns (means, variances, scalars): two float64 DeviceResults on this GPU holding one map per
+        group (None, None with maps=False) and [G][6] -- n and the pixel sums of mean, variance, bias^2, mean squared error and
+        (scaled truth)^2.  Synchronises this buffer's context, so whatever wrote the images must have been synchronised."""
+        means = variances = None
+        try:
+            if maps:
+                shape = self.shapes[int(np.atleast_1d(groups[0])[0])] if len(groups) and len(np.atleast_1d(groups[0])) else (0, 0)
+                means = DeviceResults([shape] * len(groups), 'f64', self.ctx.device)
+                variances = DeviceResults([shape] * len(groups), 'f64', self.ctx.device)
+            sc = self._ensemble_into(groups, truth, truth_index, scale, means.dev if maps else None, variances.dev if maps else None)
+        except Exception:
+            for m in (means, variances):
+                if m is not None:
+                    m.free()
+            raise
+        return means, variances, sc
 
     def free(self):
         if getattr(self, 'dev', None) is not None and self.dev.value and lib is not None:    # (lib: gone at interpreter shutdown)
@@ -228,6 +283,123 @@ def frc_between_seeds(res, tasks, seed_a, seed_b, n_rings=None, n_sectors=None):
         for j, k in enumerate(ks):
             out[k] = st[j]
     return keys, _pack_stats(out)
+
+
+def ensemble_keys(tasks):
+    """(keys, members): the (object, PSF set) pairs of `tasks` in order of first appearance, and per key the indices of all its
+    seeds in task order."""
+    members = {}
+    for i, (o, p, _) in enumerate(tasks):
+        members.setdefault((o, p), []).append(i)
+    keys = list(members)
+    return keys, [members[k] for k in keys]
+
+
+def _upload_truths(tasks, objects, total_brightness, device):
+    """The distinct objects of `tasks` as one float64 device buffer: (buffer, index of a name, scale of a name)."""
+    names = sorted({o for o, _, _ in tasks})
+    where = {n: i for i, n in enumerate(names)}
+    imgs = [np.asarray(objects[n], dtype=np.float64).reshape(np.shape(objects[n])[-2:]) for n in names]
+    scales = {n: float(total_brightness) / float(im.sum()) for n, im in zip(names, imgs)}
+    return DeviceResults.from_host(imgs, 'f64', device), where, scales
+
+
+def ensemble_tasks(res, tasks, objects, total_brightness=5e10, maps=True):
+    """The ensemble statistics of every (object, PSF set) operating point of `tasks` over its seeds, from `res` (the DeviceResults
+    of `tasks`) on the device: the truth is the object scaled to the simulated brightness, scale = total_brightness / object.sum()
+    as in score_tasks, each distinct object uploaded once as float64; one rl_ensemble_stats call per image shape.  Returns (keys,
+    counts, means, variances, scalars): the keys in order of first appearance (ensemble_keys), the number of seeds of each, two
+    float64 DeviceResults on res's GPU holding the per-pixel mean and unbiased variance map of key k as image k (None, None with
+    maps=False) and scalars [n_keys][6] (DeviceResults.ensemble): sum bias^2 (field 3) is what the blur leaves, sum variance
+    (field 2) what the noise adds, and field 4 = field 3 + (n - 1) / n field 2 up to rounding."""
+    keys, members = ensemble_keys(tasks)
+    counts = np.array([len(m) for m in members], dtype=np.int64)
+    scalars = np.zeros((len(keys), quality.ENSEMBLE_FIELDS))
+    if not keys:
+        return keys, counts, None, None, scalars
+    key_shapes = [res.shapes[m[0]] for m in members]
+    by_shape = _by_shape(key_shapes)
+    means = variances = None
+    truths, where, scales = _upload_truths(tasks, objects, total_brightness, res.ctx.device)
+    try:
+        if maps:
+            order = [k for ks in by_shape.values() for k in ks]          # the keys of one shape are neighbours in memory
+            means = DeviceResults.with_layout(key_shapes, order, 'f64', res.ctx.device)
+            variances = DeviceResults.with_layout(key_shapes, order, 'f64', res.ctx.device)
+        for shape, ks in by_shape.items():
+            sc = res._ensemble_into([members[k] for k in ks], truths, [where[keys[k][0]] for k in ks], [scales[keys[k][0]] for k in ks],
+                                    means.address(ks[0]) if maps else None, variances.address(ks[0]) if maps else None)
+            scalars[ks] = sc
+    except Exception:
+        for m in (means, variances):
+            if m is not None:
+                m.free()
+        raise
+    finally:
+        truths.free()
+    return keys, counts, means, variances, scalars
+
+
+def bias_variance_spectrum(res, tasks, objects, total_brightness=5e10, n_rings=None, n_sectors=None):
+    """The spectral form of ensemble_tasks' split, per ring (per (ring, orientation sector) cell with n_sectors = S), from the ring
+    entry points alone -- the DFT is linear, so the spectrum of the mean image is the mean of the spectra:
+        bias power      field 4 of the pair (mean image, truth, scale): sum |fft2(mean) - fft2(s t)|^2
+        variance power  1 / (n - 1) sum_m field 4 of (member m, mean image, scale 1): the unbiased variance of the members' spectra
+                        (0 for a key with one seed)
+    Returns (keys, counts, spectrum, mean_stats): per key spectrum [R][3] ([R][S][3]) = bin count, bias power, variance power
+    (quality.spectral_bias_variance_rms reads it), and mean_stats [R][5] ([R][S][5]), the ring statistics of (mean image, truth)
+    whose field 1 quality.ssnr_from wants; lists when ring counts differ.  For every bin set,
+        mean over seeds of field 4 (member, truth) = bias power + (n - 1) / n variance power   up to rounding."""
+    keys, members = ensemble_keys(tasks)
+    k_, counts, means, variances, _ = ensemble_tasks(res, tasks, objects, total_brightness, maps=True)
+    spectrum, mean_stats = [None] * len(keys), [None] * len(keys)
+    truths = None
+    try:
+        truths, where, scales = _upload_truths(tasks, objects, total_brightness, res.ctx.device)
+        for shape, ks in _by_shape([res.shapes[m[0]] for m in members]).items():
+            ms = means.ring_stats(ks, truth=truths, truth_index=[where[keys[k][0]] for k in ks], scale=[scales[keys[k][0]] for k in ks],
+                                  n_rings=n_rings, n_sectors=n_sectors)
+            flat = [i for k in ks for i in members[k]]
+            vs = res.ring_stats(flat, truth=means, truth_index=[k for k in ks for _ in members[k]], n_rings=n_rings, n_sectors=n_sectors)
+            at = 0
+            for j, k in enumerate(ks):
+                n = len(members[k])
+                power = np.zeros(ms[j].shape[:-1])
+                for m in range(n):                                       # (member order: one fixed float64 sum)
+                    power = power + vs[at + m][..., 4]
+                at += n
+                sp = np.zeros(ms[j].shape[:-1] + (3,))
+                sp[..., 0] = ms[j][..., 0]
+                sp[..., 1] = ms[j][..., 4]
+                sp[..., 2] = power / (n - 1) if n > 1 else 0.0
+                spectrum[k], mean_stats[k] = sp, ms[j]
+    finally:
+        for b in (means, variances, truths):
+            if b is not None:
+                b.free()
+    return keys, counts, _pack_stats(spectrum), _pack_stats(mean_stats)
+
+
+def bias_variance_vs_iterations(objects, psf_sets, seeds, iterations_list, total_brightness=5e10, dtype='f32', device=0,
+                                acceleration=None, tv_lambda=None, tv_epsilon=0.1):
+    """The semi-convergence picture: the ensemble scalars of every (object, PSF set) over `seeds` after K iterations, for every K
+    of `iterations_list`.  Runs run_tasks_device once per K on the group-sorted tasks and reduces each run with
+    ensemble_tasks(maps=False).  A task's noise depends only on its Philox key (seed, object id), so every K deconvolves the SAME
+    measurements, each time from ones: nothing is carried from one K to the next, and the cost is sum(iterations_list)
+    iterations per task, not max(iterations_list).  Returns (keys, out): out [len(iterations_list)][n_keys][6], row j what
+    ensemble_tasks gives for a sweep of iterations_list[j] iterations -- sum bias^2 (field 3) against sum variance (field 2)."""
+    tasks = make_tasks(objects, psf_sets, seeds)
+    tasks = [tasks[i] for i in sort_by_group(tasks, objects)]
+    keys = ensemble_keys(tasks)[0]
+    out = np.zeros((len(iterations_list), len(keys), quality.ENSEMBLE_FIELDS))
+    for j, K in enumerate(iterations_list):
+        res = run_tasks_device(tasks, objects, psf_sets, int(K), total_brightness, dtype, device, acceleration=acceleration,
+                               tv_lambda=tv_lambda, tv_epsilon=tv_epsilon)
+        try:
+            out[j] = ensemble_tasks(res, tasks, objects, total_brightness, maps=False)[4]
+        finally:
+            res.free()
+    return keys, out
 
 
 def split_flat(flat, shapes):
@@ -325,6 +497,30 @@ def run_and_score_tasks(tasks, objects, psf_sets, iterations, total_brightness=5
     return out, scores
 
 
+def run_score_reduce_tasks(tasks, objects, psf_sets, iterations, total_brightness=5e10, dtype='f32', device=0, scores=False, n_rings=None,
+                           acceleration=None, tv_lambda=None, tv_epsilon=0.1, n_sectors=None):
+    """run_tasks, with the ensemble of every (object, PSF set) of `tasks` reduced on the device before the one download
+    (ensemble_tasks(maps=False)), and -- scores=True -- every estimate scored as well (score_tasks).  Returns (estimates, scores,
+    keys, scalars): estimates and scores in task order (scores None with scores=False), the keys in order of first appearance in
+    the group-sorted tasks and their scalars [n_keys][6]."""
+    order = sort_by_group(tasks, objects)
+    sorted_tasks = [tasks[i] for i in order]
+    res = run_tasks_device(sorted_tasks, objects, psf_sets, iterations, total_brightness, dtype, device,
+                           acceleration=acceleration, tv_lambda=tv_lambda, tv_epsilon=tv_epsilon)
+    try:
+        sc = score_tasks(res, sorted_tasks, objects, total_brightness, n_rings, n_sectors) if scores else None
+        keys, _, _, _, scalars = ensemble_tasks(res, sorted_tasks, objects, total_brightness, maps=False)
+        est = res.download()
+    finally:
+        res.free()
+    out, out_scores = [None] * len(tasks), [None] * len(tasks) if scores else None
+    for k, i in enumerate(order):
+        out[i] = est[k]
+        if scores:
+            out_scores[i] = np.asarray(sc[k])
+    return out, out_scores, keys, scalars
+
+
 def pad_stack(images, shape):
     """Stack 2-D images of different sizes into one (n, shape[0], shape[1]) array, top-left aligned
     and zero filled."""
@@ -349,7 +545,7 @@ def shard_sweep(tasks, objects, psf_sets, iterations, world):
 
 def figure_2_sweep(objects, psf_sets, seeds, iterations, total_brightness=5e10, dtype='f32',
                    device=0, comm=None, info=None, acceleration=None, tv_lambda=None, tv_epsilon=0.1, scores=False, n_rings=None,
-                   n_sectors=None):
+                   n_sectors=None, ensemble=False):
     """The sweep, sharded over the ranks of `comm` (sharding.RcclComm, or anything with its
     interface) when given.  Returns (tasks, estimates) on rank 0 and (tasks, None) elsewhere;
     estimates is an array (n_tasks, ny, nx) when all objects share a shape, otherwise a list of
@@ -360,12 +556,25 @@ def figure_2_sweep(objects, psf_sets, seeds, iterations, total_brightness=5e10, 
     scores=True: every rank also scores its own shard on the device (score_tasks, `n_rings` rings) before the gather, the small
     score arrays travel through `comm.gather`, and the function returns (tasks, estimates, scores) -- scores [n_tasks][R][5] in task
     order (a list when ring counts differ) on rank 0, None elsewhere.  The estimates are those of scores=False.  n_sectors = S:
-    the scores are angle-resolved, [n_tasks][R][S][5] (score_tasks)."""
+    the scores are angle-resolved, [n_tasks][R][S][5] (score_tasks).
+    ensemble=True: every rank also reduces the (object, PSF set) operating points of its own shard over their seeds on the device
+    (ensemble_tasks(maps=False)); only the [6] scalars per key travel, through `comm.gather`, and the function returns one more
+    element, (keys, scalars) on rank 0 -- the keys rank by rank, within a rank in order of first appearance in its shard, scalars
+    [n_keys][6] -- and None elsewhere.  The estimates are those of ensemble=False.  A partition that puts the seeds of one key on
+    different ranks raises ValueError naming the key: partial statistics are not merged."""
     tasks = make_tasks(objects, psf_sets, seeds)
     world = comm.world if comm is not None else 1
     rank = comm.rank if comm is not None else 0
     shards, costs = shard_sweep(tasks, objects, psf_sets, iterations, world)
     mine = [tasks[i] for i in shards[rank]]
+    if ensemble:
+        owner = {}
+        for r, sh in enumerate(shards):
+            for i in sh:
+                if owner.setdefault(tasks[i][:2], r) != r:
+                    raise ValueError('the partition put the seeds of %r on ranks %d and %d; an ensemble is reduced on one rank'
+                                     % (tasks[i][:2], owner[tasks[i][:2]], r))
+    mine_keys, mine_ens = [], np.zeros((0, quality.ENSEMBLE_FIELDS))
     shapes = [tuple(objects[o].shape[-2:]) for o, _, _ in tasks]
     pix = [sum(shapes[i][0] * shapes[i][1] for i in sh) for sh in shards]
     if info is not None:
@@ -378,10 +587,16 @@ def figure_2_sweep(objects, psf_sets, seeds, iterations, total_brightness=5e10, 
             info['unresolved_predictions_this_rank'] = unresolved_total(reset=True)
         if scores and mine:
             mine_scores = score_tasks(res, mine, objects, total_brightness, n_rings, n_sectors)
+        if ensemble and mine:
+            mine_keys, _, _, _, mine_ens = ensemble_tasks(res, mine, objects, total_brightness, maps=False)
         flat = comm.gather_device(res, pix, 0)       # root: host float64, rank-major; others: None
         res.free()
     else:
-        if scores:
+        if ensemble:
+            local, mine_scores, mine_keys, mine_ens = run_score_reduce_tasks(
+                mine, objects, psf_sets, iterations, total_brightness, dtype, device, scores, n_rings, acceleration=acceleration,
+                tv_lambda=tv_lambda, tv_epsilon=tv_epsilon, n_sectors=n_sectors) if mine else ([], [], mine_keys, mine_ens)
+        elif scores:
             local, mine_scores = run_and_score_tasks(mine, objects, psf_sets, iterations, total_brightness, dtype, device, n_rings,
                                                      acceleration=acceleration, tv_lambda=tv_lambda, tv_epsilon=tv_epsilon,
                                                      n_sectors=n_sectors) if mine else ([], [])
@@ -408,12 +623,22 @@ def figure_2_sweep(objects, psf_sets, seeds, iterations, total_brightness=5e10, 
                 all_scores[i] = np.asarray(sflat[o:o + k]).reshape((rings[i],) + cell)
                 o += k
             all_scores = _pack_stats(all_scores)
+    ens = None
+    if ensemble:
+        per_rank = [ensemble_keys([tasks[i] for i in sh])[0] for sh in shards]       # what every rank reduces, known everywhere
+        at = {k: j for j, k in enumerate(mine_keys)}
+        mine_ens = np.asarray(mine_ens, dtype=np.float64).reshape(-1, quality.ENSEMBLE_FIELDS)[[at[k] for k in per_rank[rank]]]
+        eflat = np.ascontiguousarray(mine_ens).ravel()
+        if comm is not None:
+            eflat = comm.gather(eflat, [len(k) * quality.ENSEMBLE_FIELDS for k in per_rank], 0)
+        if eflat is not None:
+            ens = ([k for ks in per_rank for k in ks], np.asarray(eflat).reshape(-1, quality.ENSEMBLE_FIELDS))
     if flat is None:
-        return (tasks, None, None) if scores else (tasks, None)
+        return ((tasks, None, None) if scores else (tasks, None)) + ((None,) if ensemble else ())
     parts = split_flat(np.asarray(flat), [shapes[i] for i in order])
     est = [None] * len(tasks)
     for k, i in enumerate(order):
         est[i] = parts[k]
     if len(set(shapes)) == 1:
         est = np.stack(est) if est else np.zeros((0,) + (shapes[0] if shapes else (0, 0)))
-    return (tasks, est, all_scores) if scores else (tasks, est)
+    return ((tasks, est, all_scores) if scores else (tasks, est)) + ((ens,) if ensemble else ())
