@@ -302,6 +302,36 @@ int rl_batch_run(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_iters, i
  * ONE download.  line_sted_figure_2.py:39-57 is a loop of such runs: one per (PSF set, test image).                       */
 int rl_batch_submit(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_iters, int rng_kind, void* dev_out, int out_dtype);
 
+/* ---- iteration checkpoints: line_sted_figure_2.py's record_iteration at the save points of logarithmic_progress ------------
+ * Richardson-Lucy on Poisson data is semi-convergent: the answer of a sweep is a curve over the iteration count.  This is
+ * rl_batch_submit with k_iters = k_list[n_k - 1] -- the same enqueued cycle per task: staging, class sharing, keyed Poisson
+ * draws, slices, lanes, every loop, Biggs-Andrews and RL-TV as they are -- that takes the estimate out at every count of
+ * k_list (host array, strictly increasing, k_list[0] >= 1) and scores it there.  Nothing is decided on the device: the launch
+ * sequence is known on the host when the call is made.
+ *   dev_out    NULL, or a host array of n_k device pointers, each NULL or [n_tasks][ny][nx] of out_dtype: checkpoint j of task t is
+ *              the estimate after k_list[j] iterations, written where rl_batch_submit with k_list[j] would have written its
+ *              result -- and bit for bit what it would have written, for the same tasks on the same plan, on every plan type, both
+ *              element types and both opt-in modes (iterate(a) then iterate(b) is iterate(a + b))
+ *   trace_dev  NULL, or a host array of n_k device pointers, each NULL or float64 [n_tasks][RL_TRACE_FIELDS]: six sums over the
+ *              image's ny * nx pixels, x the estimate at that checkpoint, T the task's scaled object as the plan's object buffer
+ *              holds it (the plan's element type), every value widened to float64 before any arithmetic, no contraction:
+ *                  0 sum x    1 sum T    2 sum x*x    3 sum T*T    4 sum x*T    5 sum (x-T)*(x-T)
+ *              Field 5 is formed per pixel from the difference, not from fields 2 to 4.  The sums run in the fixed order of
+ *              csrc/accel_kernels.hpp -- thread in increasing order, binary tree over 256 threads, workgroups in increasing order;
+ *              the split is decided by ny * nx and the element type alone; no floating-point atomics -- so a trace is bit-identical
+ *              from run to run and a function of the task's estimate and object only.
+ * Both pointer arrays are read during the call only.  A checkpoint is taken inside the slice's loop on the lane's stream, behind
+ * the iteration that completes k_list[j] (and the accelerated step's reduction); no lane join is added between checkpoints, and
+ * the frame-pair loop drops its last spectrum at the last iteration of the run only.  A short last chunk writes its real tasks
+ * only.  The plan's state after the call is that of rl_batch_submit with the last count.  The per-workgroup partials are the
+ * plan's, allocated on the first call with a trace and counted in rl_deconv_info's device_bytes.
+ * RL_ERR_INVALID: NULL handle, NULL tasks with n_tasks > 0, negative n_tasks, NULL k_list, n_k < 1, k_list[0] < 1, a list that
+ * is not strictly increasing, an unknown rng_kind, a dev_out with a bad out_dtype, a task without an object, an image id that is
+ * too large.                                                                                                                 */
+#define RL_TRACE_FIELDS 6
+int rl_batch_submit_checkpoints(rl_deconv* h, const rl_task* tasks, int n_tasks, const int* k_list, int n_k, int rng_kind,
+                                void* const* dev_out, int out_dtype, double* const* trace_dev);
+
 /* Device memory owned by the caller: the result buffer of a sweep (rl_batch_submit), the operands of rl_comm_gather_device.
  * rl_device_download: n elements of `dtype` -> host float64 (blocking; synchronises the context first).                   */
 int rl_device_alloc(rl_ctx* ctx, size_t bytes, void** dev_out);

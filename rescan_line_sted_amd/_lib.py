@@ -90,6 +90,7 @@ PROTOTYPES = {
     'rl_deconv_dims': (_i, [_vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)]),
     'rl_batch_run': (_i, [_vp, _vp, _i, _i, _i, _dp]),
     'rl_batch_submit': (_i, [_vp, _vp, _i, _i, _i, _vp, _i]),
+    'rl_batch_submit_checkpoints': (_i, [_vp, _vp, _i, _c.POINTER(_i), _i, _i, _c.POINTER(_vp), _i, _c.POINTER(_vp)]),
     'rl_device_alloc': (_i, [_vp, _c.c_size_t, _c.POINTER(_vp)]),
     'rl_device_free': (_i, [_vp, _vp]),
     'rl_device_download': (_i, [_vp, _vp, _i, _c.c_size_t, _dp]),
@@ -447,6 +448,10 @@ class DeconvPlan:
         """rl_batch_submit: the same cycle per task, ENQUEUED -- returns once the objects are staged; the estimates go to device
         memory at `dev_out` (a ctypes.c_void_p / address: n tasks x ny x nx elements of out_dtype, unpadded; None: nowhere).
         Synchronise the context before reading them."""
+        tasks, objs = self._tasks(objects, total_brightness, seeds, image_ids)
+        check(lib.rl_batch_submit(self.handle, _c.cast(tasks, _vp), len(objs), int(iterations), rng, dev_out, DTYPES[out_dtype]))
+
+    def _tasks(self, objects, total_brightness, seeds, image_ids):
         n = len(objects)
         tb = np.broadcast_to(np.asarray(0.0 if total_brightness is None else total_brightness, dtype=np.float64), (n,))
         seeds = np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (n,))
@@ -458,7 +463,26 @@ class DeconvPlan:
             tasks[i].total_brightness = float(tb[i])
             tasks[i].seed = int(seeds[i])
             tasks[i].image_id = int(ids[i])
-        check(lib.rl_batch_submit(self.handle, _c.cast(tasks, _vp), n, int(iterations), rng, dev_out, DTYPES[out_dtype]))
+        return tasks, objs
+
+    def batch_submit_checkpoints(self, objects, total_brightness, seeds, image_ids, iterations_list, dev_outs, out_dtype='f32',
+                                 trace_devs=None, rng=RNG_PHILOX):
+        """rl_batch_submit_checkpoints: batch_submit with iterations_list[-1] iterations that takes the estimate out after every
+        count of `iterations_list` (strictly increasing, from 1).  dev_outs: None, or one device address per count (None entries
+        allowed), each n tasks x ny x nx elements of out_dtype; trace_devs likewise, each n tasks x TRACE_FIELDS float64 (the six
+        sums of include/rlsted.h).  Synchronise the context before reading either."""
+        ks = [int(k) for k in iterations_list]
+        n_k = len(ks)
+
+        def pointers(devs):
+            if devs is None:
+                return None
+            if len(devs) != n_k:
+                raise ValueError('%d device addresses for %d checkpoints' % (len(devs), n_k))
+            return (_vp * n_k)(*[d.value if isinstance(d, _vp) else d for d in devs])
+        tasks, objs = self._tasks(objects, total_brightness, seeds, image_ids)
+        check(lib.rl_batch_submit_checkpoints(self.handle, _c.cast(tasks, _vp), len(objs), (_i * max(n_k, 1))(*ks), n_k, rng,
+                                              pointers(dev_outs), DTYPES[out_dtype], pointers(trace_devs)))
 
     def bench_cycles(self, k, reps, rng=RNG_PHILOX, seed=0):
         ms = _c.c_double()

@@ -17,6 +17,7 @@
 
 #include "accel_kernels.hpp"
 #include "aux_kernels.hpp"
+#include "checkpoint_kernels.hpp"
 #include "conv_kernels.hpp"
 #include "kernel_table.hpp"
 #include "object_classes.hpp"
@@ -1063,9 +1064,31 @@ struct rl_deconv {
     }
     // the Poisson draw of a whole cycle: one seed for the batch, or -- rl_batch_submit -- a Philox key per frame (device arrays of B entries)
     struct Draw { int rng_kind; uint64_t seed; const unsigned long long* key_seeds; const unsigned* key_ids; };
+    // ---- iteration checkpoints (rl_batch_submit_checkpoints, checkpoint_kernels.hpp): after the iteration that completes k_list[j] a
+    // slice casts its frames' estimates to out[j] and leaves their six sums against obj in trace[j] -- both already at the chunk's
+    // first task, either may be NULL -- on the slice's own stream, for the chunk's nt real frames only.  The per-workgroup partials
+    // [B][blocks][6] are the plan's: a slice writes its own frames' part, and launches that reuse it follow each other in stream order.
+    struct Checkpoints { const int* k_list; int n_k; void* const* out; int out_dtype; double* const* trace; int nt; };
+    double* cp_part = nullptr;
+    int ensure_checkpoint_part() {
+        if (cp_part) return RL_OK;
+        return alloc(&cp_part, (size_t)B * checkpoint_blocks(n_img(), esize(dtype)) * kCheckpointFields * sizeof(double));
+    }
+    int take_checkpoint(const Checkpoints& cp, int j, int f0, int nf) {
+        const int frames = std::min(f0 + nf, cp.nt) - f0;
+        void* dst = cp.out ? cp.out[j] : nullptr;
+        double* tr = cp.trace ? cp.trace[j] : nullptr;
+        if (frames <= 0 || (!dst && !tr)) return RL_OK;
+        const size_t o = (size_t)f0 * n_img();
+        double* part = tr ? cp_part + (size_t)f0 * checkpoint_blocks(n_img(), esize(dtype)) * kCheckpointFields : nullptr;
+        HIP_TRY(checkpoint_take(dtype, off(est, o), off(obj, o), cp.out_dtype, dst ? (char*)dst + o * esize(cp.out_dtype) : nullptr, part,
+                                n_img(), frames, cur()));
+        if (tr) HIP_TRY(checkpoint_totals(dtype, part, n_img(), frames, tr + (size_t)f0 * kCheckpointFields, cur()));
+        return RL_OK;
+    }
     // (optionally restart from est = 1 and) run k iterations, slice by slice.  draw: one whole simulate + deconvolve cycle -- each
     // slice first computes noiseless = H(obj) and draws its measurement.  cycle_follows: another cycle follows at once (rl_deconv_bench_cycles).
-    int run_slices(int k, bool restart, const Draw* draw = nullptr, bool cycle_follows = false) {
+    int run_slices(int k, bool restart, const Draw* draw = nullptr, bool cycle_follows = false, const Checkpoints* cp = nullptr) {
         const int cf = chunk_frames();
         const int slices = (B + cf - 1) / cf;
         const int nl = slices < opt.lanes ? slices : opt.lanes;
@@ -1166,10 +1189,12 @@ struct rl_deconv {
             // Frame pairs: the last iteration of a run of >= 4 does not transform its estimate forward again (1 of 2 row
             // transforms of that launch, the spectrum store); an rl_deconv_iterate that continues rebuilds it with one ROW_FWD.
             const bool drop = pair && k >= 4;
+            int cp_next = 0;   // (est holds x_{i+1} behind every kind of step: the accelerated one ends with its REDUCE, the regularised one with its APPLY)
             for (int i = 0; i < k && rc == RL_OK; ++i) {
                 if (accel) rc = accel_step(f0, nf, acc_steps + i, shortcut && i == 0, restart && i == 0);
                 else if (tv_on()) rc = tv_iterate({f0, nf, shortcut && i == 0, restart && i == 0, /* drop_spectrum */ pair}, i > 0 || tv_sum_valid, true);
                 else rc = iterate_chunk({f0, nf, shortcut && i == 0, restart && i == 0, drop && i == k - 1, ones_first && i == 0});
+                if (cp && rc == RL_OK && cp_next < cp->n_k && cp->k_list[cp_next] == i + 1) rc = take_checkpoint(*cp, cp_next++, f0, nf);
             }
         }
         active = nullptr;
@@ -1930,7 +1955,10 @@ int rl_deconv_dims(const rl_deconv* h, int* batch, int* n_psf, int* ny, int* nx)
     return RL_OK;
 }
 
-int rl_batch_submit(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_iters, int rng_kind, void* dev_out, int out_dtype) {
+// rl_batch_submit and rl_batch_submit_checkpoints: `ck` (its k_list ends with k_iters; out / trace are the caller's arrays, offset
+// chunk by chunk here) replaces the cast of the final estimate by the checkpoints inside the slices' loops
+static int batch_submit(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_iters, int rng_kind, void* dev_out, int out_dtype,
+                        const rl_deconv::Checkpoints* ck) {
     if (!h || (!tasks && n_tasks > 0)) return fail(RL_ERR_INVALID, "NULL argument");
     if (n_tasks < 0 || k_iters < 0) return fail(RL_ERR_INVALID, "negative count");
     if (rng_kind != RL_RNG_NONE && rng_kind != RL_RNG_PHILOX) return fail(RL_ERR_INVALID, "unknown rng_kind");
@@ -1944,6 +1972,9 @@ int rl_batch_submit(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_iters
     const int B = h->B;
     const size_t n = h->n_img();
     hipStream_t s = h->ctx->stream;
+    std::vector<void*> ck_out;
+    std::vector<double*> ck_trace;
+    if (ck && ck->trace) RL_TRY(h->ensure_checkpoint_part());
     for (int t0 = 0; t0 < n_tasks; t0 += B) {
         const int nt = std::min(B, n_tasks - t0);
         rl_deconv::BatchSlot& sl = h->bslot[h->batch_chunks++ % 2];
@@ -2013,15 +2044,47 @@ int rl_batch_submit(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_iters
         }
         h->have_obj = true;
         const rl_deconv::Draw draw{rng_kind, 0, d_seeds, d_ids};
-        const int rc = h->run_slices(k_iters, true, &draw);   // per slice: H(obj), keyed Poisson draws, estimate = 1, k iterations
+        rl_deconv::Checkpoints cp{};
+        if (ck) {   // the chunk's part of every checkpoint's destination
+            cp = *ck;
+            cp.nt = nt;
+            if (ck->out) {
+                ck_out.assign(ck->out, ck->out + ck->n_k);
+                for (void*& p : ck_out)
+                    if (p) p = (char*)p + (size_t)t0 * n * esize(out_dtype);
+                cp.out = ck_out.data();
+            }
+            if (ck->trace) {
+                ck_trace.assign(ck->trace, ck->trace + ck->n_k);
+                for (double*& p : ck_trace)
+                    if (p) p += (size_t)t0 * kCheckpointFields;
+                cp.trace = ck_trace.data();
+            }
+        }
+        const int rc = h->run_slices(k_iters, true, &draw, false, ck ? &cp : nullptr);   // per slice: H(obj), keyed Poisson draws, estimate = 1, k iterations
         HIP_TRY(hipEventRecord(sl.freed, s));
         sl.used = true;
         RL_TRY(rc);
         h->have_meas = true;
-        if (dev_out)
+        if (dev_out && !ck)
             HIP_TRY(aux_cast(h->dtype, h->est, out_dtype, (char*)dev_out + (size_t)t0 * n * esize(out_dtype), (size_t)nt * n, s));
     }
     return RL_OK;
+}
+
+int rl_batch_submit(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_iters, int rng_kind, void* dev_out, int out_dtype) {
+    return batch_submit(h, tasks, n_tasks, k_iters, rng_kind, dev_out, out_dtype, nullptr);
+}
+
+int rl_batch_submit_checkpoints(rl_deconv* h, const rl_task* tasks, int n_tasks, const int* k_list, int n_k, int rng_kind,
+                                void* const* dev_out, int out_dtype, double* const* trace_dev) {
+    if (!k_list) return fail(RL_ERR_INVALID, "NULL k_list");
+    if (n_k < 1 || k_list[0] < 1) return fail(RL_ERR_INVALID, "k_list must hold at least one count >= 1");
+    for (int j = 1; j < n_k; ++j)
+        if (k_list[j] <= k_list[j - 1]) return fail(RL_ERR_INVALID, "k_list must be strictly increasing");
+    const rl_deconv::Checkpoints ck{k_list, n_k, dev_out, dev_out ? out_dtype : RL_F64, trace_dev, 0};
+    // (batch_submit checks the rest; `dev_out` there only stands for "out_dtype is used")
+    return batch_submit(h, tasks, n_tasks, k_list[n_k - 1], rng_kind, (void*)dev_out, out_dtype, &ck);
 }
 
 int rl_batch_run(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_iters, int rng_kind, double* estimates_out) {

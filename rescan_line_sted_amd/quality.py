@@ -353,3 +353,29 @@ def ssnr_from(mean_stats, spectrum, n):
     noise = spectrum[..., 2] / float(n)
     ok = (spectrum[..., 0] > 0) & (noise > 0)
     return np.where(ok, mean_stats[..., 1] / np.where(ok, noise, 1.0), np.nan)
+
+
+# ------------------------------------------------------------------ iteration checkpoints
+TRACE_FIELDS = 6
+
+
+def trace_metrics(trace, n_pixels):
+    """The error measures a checkpoint trace holds (include/rlsted.h rl_batch_submit_checkpoints): trace [..., 6] = the pixel sums of
+    x, T, x^2, T^2, x T and (x - T)^2 of an estimate x against its scaled object T; n_pixels a number or an array that broadcasts
+    against trace[..., 0].  Returns a dict of arrays of that shape:
+        mse    f5 / n
+        nrmse  sqrt(f5 / f3)
+        ncc    the centred normalised correlation (n f4 - f0 f1) / sqrt((n f2 - f0^2) (n f3 - f1^2))
+        flux   f0 / f1
+    nan where a denominator is not positive."""
+    t = np.asarray(trace, dtype=np.float64)
+    if t.shape[-1] != TRACE_FIELDS:
+        raise ValueError('expected [..., %d] sums; got shape %r' % (TRACE_FIELDS, t.shape))
+    f = [t[..., c] for c in range(TRACE_FIELDS)]
+    n = np.broadcast_to(np.asarray(n_pixels, dtype=np.float64), f[0].shape)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        den = (n * f[2] - f[0] * f[0]) * (n * f[3] - f[1] * f[1])
+        return {'mse': np.where(n > 0, f[5] / n, np.nan),
+                'nrmse': np.where(f[3] > 0, np.sqrt(f[5] / f[3]), np.nan),
+                'ncc': np.where(den > 0, (n * f[4] - f[0] * f[1]) / np.sqrt(den), np.nan),
+                'flux': np.where(f[1] != 0, f[0] / f[1], np.nan)}

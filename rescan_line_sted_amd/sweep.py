@@ -380,17 +380,16 @@ def bias_variance_spectrum(res, tasks, objects, total_brightness=5e10, n_rings=N
     return keys, counts, _pack_stats(spectrum), _pack_stats(mean_stats)
 
 
-def bias_variance_vs_iterations(objects, psf_sets, seeds, iterations_list, total_brightness=5e10, dtype='f32', device=0,
-                                acceleration=None, tv_lambda=None, tv_epsilon=0.1):
-    """The semi-convergence picture: the ensemble scalars of every (object, PSF set) over `seeds` after K iterations, for every K
-    of `iterations_list`.  Runs run_tasks_device once per K on the group-sorted tasks and reduces each run with
-    ensemble_tasks(maps=False).  A task's noise depends only on its Philox key (seed, object id), so every K deconvolves the SAME
-    measurements, each time from ones: nothing is carried from one K to the next, and the cost is sum(iterations_list)
-    iterations per task, not max(iterations_list).  Returns (keys, out): out [len(iterations_list)][n_keys][6], row j what
-    ensemble_tasks gives for a sweep of iterations_list[j] iterations -- sum bias^2 (field 3) against sum variance (field 2)."""
-    tasks = make_tasks(objects, psf_sets, seeds)
-    tasks = [tasks[i] for i in sort_by_group(tasks, objects)]
-    keys = ensemble_keys(tasks)[0]
+def _increasing_from_one(iterations_list):
+    ks = [int(k) for k in iterations_list]
+    return len(ks) > 0 and ks[0] >= 1 and all(b > a for a, b in zip(ks, ks[1:])) and all(k == K for k, K in zip(ks, iterations_list))
+
+
+def _bias_variance_one_sweep_per_k(tasks, keys, objects, psf_sets, iterations_list, total_brightness, dtype, device, acceleration,
+                                   tv_lambda, tv_epsilon):
+    """bias_variance_vs_iterations without checkpoints: run_tasks_device once per K, each time from ones on the same measurements
+    -- sum(iterations_list) iterations per task.  What a list that is not strictly increasing from 1 gets, and what the tests
+    hold the one-sweep form against."""
     out = np.zeros((len(iterations_list), len(keys), quality.ENSEMBLE_FIELDS))
     for j, K in enumerate(iterations_list):
         res = run_tasks_device(tasks, objects, psf_sets, int(K), total_brightness, dtype, device, acceleration=acceleration,
@@ -398,6 +397,34 @@ def bias_variance_vs_iterations(objects, psf_sets, seeds, iterations_list, total
         try:
             out[j] = ensemble_tasks(res, tasks, objects, total_brightness, maps=False)[4]
         finally:
+            res.free()
+    return out
+
+
+def bias_variance_vs_iterations(objects, psf_sets, seeds, iterations_list, total_brightness=5e10, dtype='f32', device=0,
+                                acceleration=None, tv_lambda=None, tv_epsilon=0.1):
+    """The semi-convergence picture: the ensemble scalars of every (object, PSF set) over `seeds` after K iterations, for every K
+    of `iterations_list`.  A strictly increasing list that starts at 1 or above runs ONE sweep of max(iterations_list) iterations
+    on the group-sorted tasks that takes a checkpoint at every K (run_tasks_checkpoints_device) and reduces each checkpoint with
+    ensemble_tasks(maps=False): a checkpoint is bit for bit the estimate of a sweep of K iterations, so the numbers are those of
+    one sweep per K at max(iterations_list) iterations per task.  Any other list runs run_tasks_device once per K, each time from
+    ones on the SAME measurements (a task's noise depends only on its Philox key (seed, object id)), at sum(iterations_list)
+    iterations per task.  Returns (keys, out): out [len(iterations_list)][n_keys][6], row j what
+    ensemble_tasks gives for a sweep of iterations_list[j] iterations -- sum bias^2 (field 3) against sum variance (field 2)."""
+    tasks = make_tasks(objects, psf_sets, seeds)
+    tasks = [tasks[i] for i in sort_by_group(tasks, objects)]
+    keys = ensemble_keys(tasks)[0]
+    if not _increasing_from_one(iterations_list):
+        return keys, _bias_variance_one_sweep_per_k(tasks, keys, objects, psf_sets, iterations_list, total_brightness, dtype, device,
+                                                    acceleration, tv_lambda, tv_epsilon)
+    out = np.zeros((len(iterations_list), len(keys), quality.ENSEMBLE_FIELDS))
+    results, _ = run_tasks_checkpoints_device(tasks, objects, psf_sets, iterations_list, total_brightness, dtype, device,
+                                              acceleration=acceleration, tv_lambda=tv_lambda, tv_epsilon=tv_epsilon, trace=False)
+    try:
+        for j, res in enumerate(results):
+            out[j] = ensemble_tasks(res, tasks, objects, total_brightness, maps=False)[4]
+    finally:
+        for res in results:
             res.free()
     return keys, out
 
@@ -448,6 +475,87 @@ def run_tasks_device(tasks, objects, psf_sets, iterations, total_brightness=5e10
     for st in used:
         Context.get(device, st).synchronize()
     return res
+
+
+def run_tasks_checkpoints_device(tasks, objects, psf_sets, iterations_list, total_brightness=5e10, dtype='f32', device=0,
+                                 max_frames_per_plan=256, streams=SWEEP_STREAMS, timing=None, acceleration=None, tv_lambda=None,
+                                 tv_epsilon=0.1, estimates=True, trace=True):
+    """run_tasks_device with iterations_list[-1] iterations that takes every task's estimate out after each K of `iterations_list`
+    (strictly increasing, from 1) inside the enqueued run (`rl_batch_submit_checkpoints`): the same grouping, plan cache and
+    contexts, one synchronisation.  Returns (results, trace): `results` a list of len(iterations_list) DeviceResults, entry j bit for
+    bit what run_tasks_device gives with iterations_list[j] (None with estimates=False); `trace` a host array
+    [len(iterations_list)][n_tasks][quality.TRACE_FIELDS] in task order, the six sums of every checkpoint against the task's scaled
+    object (quality.trace_metrics reads it; None with trace=False) -- one small download from a device buffer.  With
+    estimates=False a sweep can trace every iteration, range(1, K + 1), without storing an image."""
+    import time
+    t_start = time.perf_counter()
+    ks = [int(k) for k in iterations_list]
+    n_k, n_tasks = len(ks), len(tasks)
+    ids = object_ids(objects)
+    shapes = [objects[o].shape[-2:] for o, _, _ in tasks]
+    results = [DeviceResults(shapes, dtype, device) for _ in ks] if estimates else None
+    ctx = Context.get(device)
+    trace_dev = ctypes.c_void_p()
+    row = n_tasks * quality.TRACE_FIELDS
+    if trace:
+        check(lib.rl_device_alloc(ctx.handle, max(n_k * row, 1) * 8, ctypes.byref(trace_dev)))
+    try:
+        groups = {}
+        for idx, key in enumerate(task_groups(tasks, objects)):
+            groups.setdefault(key, []).append(idx)
+        used = set()
+        n_sub = 0
+        for (p, shape), idxs in groups.items():
+            for start in range(0, len(idxs), max_frames_per_plan):
+                part = idxs[start:start + max_frames_per_plan]
+                stream = n_sub % max(1, streams)
+                n_sub += 1
+                plan = plan_for(psf_sets[p], len(part), shape, dtype, device, stream, acceleration, tv_lambda, tv_epsilon)
+                used.add(stream)
+                frames = [np.ascontiguousarray(np.asarray(objects[tasks[i][0]], dtype=np.float64).reshape(shape)) for i in part]
+                for a, b in _consecutive_runs(part, None):
+                    plan.batch_submit_checkpoints(
+                        frames[a:b], total_brightness, [tasks[i][2] for i in part[a:b]], [ids[tasks[i][0]] for i in part[a:b]], ks,
+                        [r.address(part[a]) for r in results] if estimates else None, dtype,
+                        [trace_dev.value + (j * row + part[a] * quality.TRACE_FIELDS) * 8 for j in range(n_k)] if trace else None,
+                        rng=RNG_PHILOX)
+        if timing is not None:
+            timing['enqueue_s'] = time.perf_counter() - t_start
+        for st in used:
+            Context.get(device, st).synchronize()
+        out = None
+        if trace:
+            out = np.zeros((n_k, n_tasks, quality.TRACE_FIELDS))
+            if n_k * row:
+                check(lib.rl_device_download(ctx.handle, trace_dev, DTYPES['f64'], n_k * row, ptr(out)))
+    except Exception:
+        for r in results or ():
+            r.free()
+        raise
+    finally:
+        if trace_dev:
+            check(lib.rl_device_free(ctx.handle, trace_dev))
+    return results, out
+
+
+def best_iterations(trace, iterations_list):
+    """Per task, the K of `iterations_list` at which the squared error against the scaled object (field 5 of the trace
+    [n_k][n_tasks][6] of run_tasks_checkpoints_device) is smallest; the first such K on a tie."""
+    trace = np.asarray(trace, dtype=np.float64)
+    return np.asarray([int(k) for k in iterations_list])[np.argmin(trace[..., 5], axis=0)]
+
+
+def error_vs_iterations(objects, psf_sets, seeds, iterations_list, total_brightness=5e10, dtype='f32', device=0, acceleration=None,
+                        tv_lambda=None, tv_epsilon=0.1):
+    """The error curve of every (object, PSF set, seed) over `iterations_list` from ONE sweep of iterations_list[-1] iterations that
+    stores no image: (tasks, metrics), the group-sorted tasks and quality.trace_metrics of their trace, each entry
+    [len(iterations_list)][n_tasks]."""
+    tasks = make_tasks(objects, psf_sets, seeds)
+    tasks = [tasks[i] for i in sort_by_group(tasks, objects)]
+    _, trace = run_tasks_checkpoints_device(tasks, objects, psf_sets, iterations_list, total_brightness, dtype, device,
+                                            acceleration=acceleration, tv_lambda=tv_lambda, tv_epsilon=tv_epsilon, estimates=False)
+    n_pixels = np.array([objects[o].shape[-2] * objects[o].shape[-1] for o, _, _ in tasks], dtype=np.float64)
+    return tasks, quality.trace_metrics(trace, n_pixels)
 
 
 def _consecutive_runs(part, res):
