@@ -11,6 +11,6 @@ if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
 from rescan_line_sted_amd.line_sted_tools import (  # noqa: E402,F401
-    Deconvolver, logarithmic_progress, simulate, deconvolve, deconvolve_until)
+    Deconvolver, logarithmic_progress, simulate, deconvolve, deconvolve_until, deconvolve_tiled)
 from rescan_line_sted_amd.psf import (  # noqa: E402,F401
     psf_report, generate_psfs, tune_psf, get_width)

@@ -224,6 +224,14 @@ int rl_deconv_bench_cycles(rl_deconv* h, int k, int reps, int rng_kind, uint64_t
  * loads may read and discard): never write there, never assume the next buffer starts right behind. */
 int rl_deconv_device_ptr(rl_deconv* h, int which, void** ptr, size_t* n_elements, int* dtype);
 
+/* The caller has written a complete new measurement, all batch * n_psf images, into the buffer of rl_deconv_device_ptr(which = 1)
+ * on the device (rl_tile_gather, rl_device_upload, a kernel of its own on the context's stream).  Leaves the plan exactly where
+ * rl_deconv_set_measurement leaves it, without the upload: it holds a measurement -- also a plan that never saw
+ * rl_deconv_set_measurement or rl_deconv_simulate, which otherwise answers rl_deconv_iterate with RL_ERR_STATE -- and the next
+ * Richardson-Lucy run starts from ones.  The frames' levels (the pairing guard of rl_deconv_strategy) and the negative-pixel flag
+ * are measured on the device before that run. */
+int rl_deconv_measurement_written(rl_deconv* h);
+
 /* Convolution strategy the plan chose for its PSF set: separable == 1: every view
  * is rank 1 (p = u v^T; the 0 / 90 degree line PSFs) and small, H / H_t run as direct row + column stencils;
  * separable == 2: the views are small but not rank 1 and H / H_t run as a direct 2-D stencil (py * px multiply-adds
@@ -340,6 +348,9 @@ int rl_device_download(rl_ctx* ctx, const void* dev, int dtype, size_t n_element
 /* host float64 -> n elements of `dtype` at a device address of this GPU (a caller's buffer, or a plan buffer handed out by
  * rl_deconv_device_ptr -- the zero-copy way to replace a measurement: the plan re-measures its frames' levels before the next run). */
 int rl_device_upload(rl_ctx* ctx, void* dev, int dtype, size_t n_elements, const double* host);
+/* Stream-ordered device-to-device copy of `bytes` bytes on the context's stream (it does not wait): what moves a chunk's estimates
+ * from a plan buffer into a caller's store.  The ranges must not overlap (RL_ERR_INVALID). */
+int rl_device_copy(rl_ctx* ctx, void* dst_dev, const void* src_dev, size_t bytes);
 
 /* ---- multi-GPU: one process per GPU, frames sharded over ranks -----------------
  * The reference is single process; independent simulations shard with no
@@ -530,6 +541,48 @@ int rl_ring_sector_stats(rl_ctx* ctx, const void* a_dev, int a_dtype, const int6
 int rl_ensemble_stats(rl_ctx* ctx, const void* src_dev, int src_dtype, const int64_t* member_offsets, const int32_t* group_ptr,
                       int n_groups, const void* truth_dev, int truth_dtype, const int64_t* truth_offsets,
                       const double* truth_scale, size_t n_pixels, double* mean_dev, double* var_dev, double* out);
+
+/* ---- tiled Richardson-Lucy: images of any size as overlapping tiles of an ordinary plan ----
+ * An image axis of n pixels is cut into tiles of `tile` pixels that overlap by at least `overlap`; every tile is deconvolved as a
+ * frame of a plan of the tile's shape, zero-extended at its border exactly as an image is at its own, and the estimates are
+ * blended with weights that are 0 in a margin of `margin` pixels at every interior tile edge and ramp linearly to 1 across the
+ * rest of the overlap.  Plain Richardson-Lucy from ones moves information 2 * (max(py, px) / 2) pixels
+ * per iteration, so with margin >= 2 * k * (max(py, px) / 2) the blend of k-iteration tile estimates IS the whole-image estimate
+ * up to rounding; smaller margins trade accuracy for speed.  Biggs-Andrews and RL-TV use per-frame sums: they run per tile.
+ *
+ * rl_tile_axis (host only): 0 < overlap < tile.  n <= tile: one tile of n pixels at 0.  Otherwise s = tile - overlap,
+ * *count = ceil((n - tile) / s) + 1 tiles of `tile` pixels at origins[i] = (i * (n - tile)) / (*count - 1) (integer division):
+ * the first at 0, the last at n - tile, none overhangs.  origins: *count values, or NULL to ask for the count alone.
+ * rl_tile_weights (host only): 0 <= margin, 2 * margin < overlap; origins as rl_tile_axis gave them (any non-decreasing list from
+ * 0 to n - t whose neighbours overlap by more than 2 * margin is accepted; t = min(tile, n)).  Raw weight of tile i at local j:
+ *     min(1, left, right),   left  = clamp((j - margin + 0.5) / R, 0, 1),       R  = origins[i-1] + t - origins[i] - 2 margin   (i > 0)
+ *                            right = clamp((t - margin - j - 0.5) / R', 0, 1),  R' = origins[i] + t - origins[i+1] - 2 margin   (i < count-1)
+ * weights_out [count][t]: the raw weight over the sum of the raw weights of all tiles covering that pixel (summed in increasing i;
+ * positive everywhere, or RL_ERR_INVALID) -- per pixel the weights sum to 1.  first_out, count_out [n] (both or neither): first
+ * covering tile and number of covering tiles of every pixel; more than two tiles may cover one.  Any output may be NULL. */
+int rl_tile_axis(int n, int tile, int overlap, int* count, int* origins);
+int rl_tile_weights(int n, int tile, int overlap, int margin, int count, const int* origins, double* weights_out, int* first_out,
+                    int* count_out);
+/* rl_tile_gather: windows of src_dev [F][V][NY][NX] (src_dtype) -> dst_dev [n_slots][V][ty][tx] (dst_dtype), a plan's measurement
+ * buffer (rl_deconv_device_ptr which = 1 of a plan of n_slots frames of ty x tx; then rl_deconv_measurement_written).  slots: host,
+ * n_slots triples (frame, a_y, a_x), the window's frame and origin; frame = -1: a filler, written with ones, so that a short last
+ * chunk never iterates on stale data.  A plain copy, one rounding at most (f64 -> f32).  Enqueued on the context's stream; writes
+ * exactly n_slots * V * ty * tx values (never the slack behind a plan buffer).
+ * RL_ERR_INVALID: a NULL argument, a dtype that is neither, F / V / NY / NX / n_slots < 1, a tile larger than the image, a frame
+ * outside -1 .. F - 1, a window that overhangs the image, dst overlapping src.
+ * rl_tile_blend: tiles_dev [F][ny_tiles][nx_tiles][ty][tx] (tiles_dtype; tiles frame-major, then tile row, then tile column) ->
+ * out_dev [F][NY][NX] (out_dtype):
+ *     out[f][gy][gx] = sum_iy sum_ix (wy[iy][gy - origins_y[iy]] * wx[ix][gx - origins_x[ix]]) * tile value
+ * over the covering tiles, in float64, from 0.0, iy ascending outside, ix ascending inside, each term (wy * wx) * (double)e, no
+ * contraction, no atomics: a float64 output is bit-identical from run to run, an f32 output is that value rounded once.
+ * origins_y / origins_x, wy [ny_tiles][ty] / wx [nx_tiles][tx]: host arrays (rl_tile_axis, rl_tile_weights); the coverage tables
+ * are computed in the call and staged with them in a workspace kept in the context.  Synchronises the context's stream.
+ * RL_ERR_INVALID: a NULL argument, a dtype that is neither, a count < 1, a tile larger than the image, an origin outside
+ * 0 .. N - t or decreasing, a pixel no tile covers, out overlapping the tiles. */
+int rl_tile_gather(rl_ctx* ctx, const void* src_dev, int src_dtype, int F, int V, int NY, int NX, const int* slots, int n_slots,
+                   int ty, int tx, void* dst_dev, int dst_dtype);
+int rl_tile_blend(rl_ctx* ctx, const void* tiles_dev, int tiles_dtype, int F, int NY, int NX, int ny_tiles, int nx_tiles, int ty,
+                  int tx, const int* origins_y, const int* origins_x, const double* wy, const double* wx, void* out_dev, int out_dtype);
 
 /* ---- line_sted_figure_3.py: the scan-position-by-scan-position imaging simulator (:76-273) ----
  * rl_rotate_image: `rotate` (:382-391) for one [ny][nx] plane -- scipy.ndimage.rotate(order 3,

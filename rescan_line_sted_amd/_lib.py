@@ -10,6 +10,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RLSTED_LIB') or os.path.join(_HERE, '_lib', 'librlsted.so')   # RLSTED_LIB: a build variant (development)
+DEFAULT_DEVICE = int(os.environ.get('RLSTED_DEVICE', '0'))   # the GPU of every call that names none
 
 RL_F32, RL_F64 = 0, 1
 RNG_NONE, RNG_PHILOX = 0, 1
@@ -121,6 +122,12 @@ PROTOTYPES = {
     'rl_ring_count': (_i, [_i, _i]),
     'rl_ring_stats': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _vp, _i, _c.POINTER(_c.c_int64), _dp, _i, _i, _i, _i, _dp]),
     'rl_ring_sector_stats': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _vp, _i, _c.POINTER(_c.c_int64), _dp, _i, _i, _i, _i, _i, _dp]),
+    'rl_device_copy': (_i, [_vp, _vp, _vp, _c.c_size_t]),
+    'rl_deconv_measurement_written': (_i, [_vp]),
+    'rl_tile_axis': (_i, [_i, _i, _i, _c.POINTER(_i), _c.POINTER(_i)]),
+    'rl_tile_weights': (_i, [_i, _i, _i, _i, _i, _c.POINTER(_i), _dp, _c.POINTER(_i), _c.POINTER(_i)]),
+    'rl_tile_gather': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _c.POINTER(_i), _i, _i, _i, _vp, _i]),
+    'rl_tile_blend': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _c.POINTER(_i), _c.POINTER(_i), _dp, _dp, _vp, _i]),
     'rl_ensemble_stats': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int32), _i, _vp, _i, _c.POINTER(_c.c_int64), _dp,
                                _c.c_size_t, _vp, _vp, _dp]),
 }
@@ -311,6 +318,11 @@ class DeconvPlan:
     def set_measurement(self, noisy):
         noisy = as_f64(noisy).reshape(self.B, self.V, self.ny, self.nx)
         check(lib.rl_deconv_set_measurement(self.handle, ptr(noisy)))
+
+    def measurement_written(self):
+        """The measurement buffer (device_array('measurement')) was written on the device: set_measurement without the upload
+        (include/rlsted.h rl_deconv_measurement_written).  The next iterate starts from ones."""
+        check(lib.rl_deconv_measurement_written(self.handle))
 
     def iterate(self, k=1):
         check(lib.rl_deconv_iterate(self.handle, int(k)))

@@ -93,6 +93,9 @@ struct rl_ctx {
             if (work) (void)hipFree(work);
         }
     } ensemble;
+    // rl_tile_gather, rl_tile_blend (tile_api.cpp): a grow-only workspace for the slot list / the layout tables of a call; freed
+    // with the context
+    EnsembleWork tile;
 
     int device = 0;
     hipStream_t stream = nullptr;

@@ -1665,6 +1665,17 @@ int rl_deconv_set_measurement(rl_deconv* h, const double* noisy) {
     return RL_OK;
 }
 
+// rl_deconv_set_measurement without the upload: the caller wrote the buffer of rl_deconv_device_ptr(which = 1) on the device
+// (rl_tile_gather).  The frames' levels and the negative-pixel flag are measured there before the next run (refresh_meas_levels).
+int rl_deconv_measurement_written(rl_deconv* h) {
+    if (!h) return fail(RL_ERR_INVALID, "handle is NULL");
+    h->meas_level.clear();
+    h->meas_external = true;
+    h->have_meas = true;
+    h->est_ready = false;
+    return RL_OK;
+}
+
 int rl_deconv_set_estimate(rl_deconv* h, const double* estimate) {
     if (!h || !estimate) return fail(RL_ERR_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(h->ctx->device));

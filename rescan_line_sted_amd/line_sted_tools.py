@@ -31,6 +31,10 @@ default, None, is the reference's iteration.
 
 Stopping: `deconvolve_until` stops every frame of a batch by its own Poisson
 I-divergence, formed on the device.
+
+Large images: `deconvolve_tiled` (tiling.py) cuts images of any size into
+overlapping tiles of one plan and blends the tile estimates on the device
+(INTEGRATION.md section 5g).
 """
 import os
 import time
@@ -39,9 +43,10 @@ import numpy as np
 
 from . import _lib
 from ._lib import DeconvPlan, RNG_NONE, RNG_PHILOX
+from .tiling import deconvolve_tiled   # noqa: F401  (re-exported)
 
 _DEFAULT_DTYPE = os.environ.get('RLSTED_DTYPE', 'f64')
-_DEFAULT_DEVICE = int(os.environ.get('RLSTED_DEVICE', '0'))
+_DEFAULT_DEVICE = _lib.DEFAULT_DEVICE
 
 
 def _np_tif():
