@@ -1619,6 +1619,7 @@ int rl_deconv_simulate(rl_deconv* h, int rng_kind, uint64_t seed) {
     h->choose_loop(h->meas_level);
     h->have_meas = true;
     h->meas_external = false;
+    h->meas_negative = false;   // (Poisson draws + 1e-9: an earlier upload's negative pixels are gone)
     h->est_ready = false;
     return RL_OK;
 }
@@ -1901,6 +1902,7 @@ int rl_deconv_bench_cycles(rl_deconv* h, int k, int reps, int rng_kind, uint64_t
     hipStream_t s = h->ctx->stream;
     h->meas_level = h->obj_level;   // every cycle draws its measurement from the object
     h->choose_loop(h->meas_level);
+    h->meas_negative = false;       // (Poisson draws + 1e-9; before the first slice iterates: sub())
     HIP_TRY(hipEventRecord(h->ev0, s));
     for (int r = 0; r < reps; ++r) {
         // per slice of the batch: noiseless = H(obj), noisy = Poisson(noiseless) + 1e-9, est = 1,
@@ -2026,6 +2028,7 @@ static int batch_submit(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_i
         h->obj_level = level;
         h->meas_level = level;
         h->choose_loop(h->meas_level);
+        h->meas_negative = false;   // (the chunk draws its own measurement: Poisson draws + 1e-9)
         // tasks that share an object and a target are one class (object_classes.hpp); the lists of the slices' representatives ride in the header
         h->forget_classes();
         if (h->opt.share_objects && !h->sep) h->n_classes = classify_by_index(idx, scaled ? tb : nullptr, B, h->obj_class);
@@ -2229,6 +2232,7 @@ int rl_deconv_time_cycle(rl_deconv* h, int k, int rng_kind, uint64_t seed, doubl
     HIP_TRY(hipDeviceSynchronize());
     h->meas_level = h->obj_level;
     h->choose_loop(h->meas_level);
+    h->meas_negative = false;
     h->timed.clear();
     h->events_used = 0;
     h->timing = true;
