@@ -14,7 +14,9 @@
  * C contiguous.  Handles are opaque.  One call in flight per context.
  *
  * All image-like host arrays are float64 (the reference's dtype); the
- * arithmetic type on the device is chosen per plan (RL_F32 / RL_F64).
+ * arithmetic type on the device is chosen per plan (RL_F32 / RL_F64).  The
+ * one exception is the acquired-stack path (rl_stack_run): raw camera frames
+ * go in and estimates come out in the types its parameters name.
  */
 #ifndef RLSTED_H
 #define RLSTED_H
@@ -583,6 +585,80 @@ int rl_tile_gather(rl_ctx* ctx, const void* src_dev, int src_dtype, int F, int V
                    int ty, int tx, void* dst_dev, int dst_dtype);
 int rl_tile_blend(rl_ctx* ctx, const void* tiles_dev, int tiles_dtype, int F, int NY, int NX, int ny_tiles, int nx_tiles, int ty,
                   int tx, const int* origins_y, const int* origins_x, const double* wy, const double* wx, void* out_dev, int out_dtype);
+
+/* ---- acquired camera stacks: narrow ingest, narrow export, overlapped transfers ----
+ * load_data_from_tif (:514-518) hands a measured stack to the Deconvolver; cameras deliver uint16.  These calls move raw frames
+ * across PCIe in their own type and turn them into a plan's measurement on the device.
+ *
+ * rl_ingest: raw_dev holds src_images sensor frames of src_ny rows of src_pitch elements of raw_dtype (RL_RAW_*).  dst_dev
+ * [n_slots][V][ny][nx] of dst_dtype (RL_F32 / RL_F64) is a plan's measurement buffer (rl_deconv_device_ptr which = 1; then
+ * rl_deconv_measurement_written) or any device buffer of that size.  Slot b, view v is the window of ny x nx pixels at (y0, x0) of
+ * source image b * frame_stride + v * view_stride ([F][V] order: V, 1; the [V][F] order that record_data writes: 1, F).  Slots >=
+ * n_valid are fillers, written with ones (a short last chunk).  Per pixel, in float64, no contraction:
+ *     x = (double)raw;   d = dark_dev ? (double)dark_dev[y][x] : offset      (dark_dev: device float [ny][nx], window coordinates)
+ *     v = (x - d) * gain                                                     (two roundings)
+ *     saturated += saturation > 0 && x >= saturation
+ *     v not finite: invalid += 1, v = 0;     otherwise v < 0: clipped += 1, v = 0
+ *     out = (dst type)(v + epsilon)                                          (1e-9 mirrors load_data_from_tif)
+ * stats_dev: NULL, or device float64 [n_slots * V][RL_INGEST_FIELDS]: the sum of the stored values (widened to float64; a filler's
+ * is ny * nx), then the clipped, saturated and invalid counts.  The sum runs in the fixed order of csrc/ingest_kernels.hpp --
+ * thread, binary tree over 256 threads, workgroups in increasing order; the split is decided by ny and nx alone; no atomics -- and
+ * is bit-identical from run to run; the counts are exact.  Reads nothing outside the windows, writes exactly n_slots * V * ny * nx
+ * values (never the slack behind a plan buffer).  Enqueued on the context's stream.
+ * rl_export: est_dev [n][ny][nx] of est_dtype (RL_F32 / RL_F64) -> out_dev of out_dtype (RL_OUT_*): y = (double)e * scale; f32 /
+ * f64: y rounded once; u16: rint(y), ties to even, nan and y <= 0 give 0, y > 65535 gives 65535 and is counted.  stats_dev: NULL,
+ * or device float64 [n][RL_EXPORT_FIELDS]: the sum of (double)e in the same fixed order, the clamped count.  Enqueued.
+ * RL_ERR_INVALID (no kernel is launched): a NULL ctx / source / destination, an unknown dtype, a count < 1 (n_valid: outside 0 ..
+ * n_slots), a window that overhangs the sensor frame, a source image outside 0 .. src_images - 1 for a valid slot, gain not finite
+ * or <= 0, offset, scale or saturation nan, epsilon < 0 or not finite, a destination that overlaps a source. */
+#define RL_RAW_U8 0
+#define RL_RAW_U16 1
+#define RL_RAW_I16 2
+#define RL_RAW_F32 3
+#define RL_OUT_F32 0
+#define RL_OUT_F64 1
+#define RL_OUT_U16 2
+#define RL_ORDER_FRAME_VIEW 0
+#define RL_ORDER_VIEW_FRAME 1
+#define RL_INGEST_FIELDS 4
+#define RL_EXPORT_FIELDS 2
+int rl_ingest(rl_ctx* ctx, const void* raw_dev, int raw_dtype, int src_images, int src_ny, int src_pitch, int y0, int x0,
+              long long frame_stride, long long view_stride, int n_slots, int n_valid, int V, int ny, int nx,
+              const float* dark_dev, double offset, double gain, double epsilon, double saturation,
+              void* dst_dev, int dst_dtype, double* stats_dev);
+int rl_export(rl_ctx* ctx, const void* est_dev, int est_dtype, int n, int ny, int nx, double scale,
+              void* out_dev, int out_dtype, double* stats_dev);
+
+/* A stack pipeline on a plan: any number of frames through the plan's batch B, chunk by chunk, with the transfers overlapped.
+ * params: the sensor frame (src_ny rows of src_pitch elements, src_nx <= src_pitch of them pixels), the window origin (y0, x0) of the
+ * plan's ny x nx image in it, the camera (offset or a host dark map [ny][nx], gain, epsilon, saturation), the order of raw_host --
+ * RL_ORDER_FRAME_VIEW [n_frames][V] images, RL_ORDER_VIEW_FRAME [V][n_frames] -- and the output (out_dtype, out_scale).
+ * rl_stack_run: raw_host -> out_host [n_frames][ny][nx] of out_dtype after k_iters Richardson-Lucy iterations from ones per frame,
+ * in the plan's current modes (Biggs-Andrews, RL-TV).  Two slots, each a page-locked raw block, a device raw buffer, a device out
+ * buffer and a page-locked out block; a copy-in and a copy-out stream beside the context's.  Chunk i + 1 is uploaded before chunk i
+ * iterates; the context's stream runs rl_ingest, rl_deconv_measurement_written, rl_deconv_reset_estimate, rl_deconv_iterate and
+ * rl_export; chunk i is downloaded while chunk i + 1 iterates.  Page-locked raw_host / out_host (rl_host_alloc) are copied to and
+ * from directly, pageable ones through the slots' blocks.  A short last chunk is filled with ones frames.  ingest_stats
+ * [n_frames][V][RL_INGEST_FIELDS], export_stats [n_frames][RL_EXPORT_FIELDS], times_ms [4] = wall time of the call, summed event
+ * times of the uploads, of the compute stream's work, of the downloads: host arrays, any may be NULL.  The first failure ends the
+ * run; the call then waits for the copies still in flight before it returns, so the caller may let go of its arrays.  An array is
+ * copied directly only if its first and its last byte are page-locked.  The plan is left as after rl_deconv_iterate on the last
+ * chunk; it must outlive the stack.  rl_stack_destroy synchronises the three streams. */
+typedef struct rl_stack rl_stack;
+typedef struct rl_stack_params {
+    int raw_dtype, order, src_ny, src_nx, src_pitch, y0, x0;
+    double offset, gain, epsilon, saturation;
+    const float* dark;   /* host [ny][nx], or NULL: offset */
+    int out_dtype;
+    double out_scale;
+} rl_stack_params;
+int rl_stack_create(rl_deconv* plan, const rl_stack_params* params, rl_stack** out);
+int rl_stack_run(rl_stack* st, const void* raw_host, int n_frames, int k_iters, void* out_host, double* ingest_stats,
+                 double* export_stats, double* times_ms);
+int rl_stack_destroy(rl_stack* st);
+/* `bytes` bytes of any type from a host array to a device address of this GPU, as they are (raw camera data on its way to
+ * rl_ingest outside a pipeline: deconvolve_tiled with a camera).  Blocking: the host array may go away when it returns. */
+int rl_device_upload_bytes(rl_ctx* ctx, void* dev, const void* host, size_t bytes);
 
 /* ---- line_sted_figure_3.py: the scan-position-by-scan-position imaging simulator (:76-273) ----
  * rl_rotate_image: `rotate` (:382-391) for one [ny][nx] plane -- scipy.ndimage.rotate(order 3,

@@ -128,6 +128,13 @@ PROTOTYPES = {
     'rl_tile_weights': (_i, [_i, _i, _i, _i, _i, _c.POINTER(_i), _dp, _c.POINTER(_i), _c.POINTER(_i)]),
     'rl_tile_gather': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _c.POINTER(_i), _i, _i, _i, _vp, _i]),
     'rl_tile_blend': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _c.POINTER(_i), _c.POINTER(_i), _dp, _dp, _vp, _i]),
+    'rl_ingest': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _c.c_longlong, _c.c_longlong, _i, _i, _i, _i, _i, _vp, _c.c_double, _c.c_double,
+                       _c.c_double, _c.c_double, _vp, _i, _vp]),
+    'rl_export': (_i, [_vp, _vp, _i, _i, _i, _i, _c.c_double, _vp, _i, _vp]),
+    'rl_stack_create': (_i, [_vp, _vp, _c.POINTER(_vp)]),
+    'rl_stack_run': (_i, [_vp, _vp, _i, _i, _vp, _dp, _dp, _dp]),
+    'rl_stack_destroy': (_i, [_vp]),
+    'rl_device_upload_bytes': (_i, [_vp, _vp, _vp, _c.c_size_t]),
     'rl_ensemble_stats': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int32), _i, _vp, _i, _c.POINTER(_c.c_int64), _dp,
                                _c.c_size_t, _vp, _vp, _dp]),
 }

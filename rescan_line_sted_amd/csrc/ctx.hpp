@@ -16,6 +16,7 @@ namespace rl {
 std::string& last_error();                 // thread local
 int fail(int code, const std::string& msg);
 bool debug_sync();                         // RLSTED_DEBUG_SYNC set: sync + check after every launch
+rl_ctx* plan_ctx(rl_deconv* h);            // the context of a plan (rlsted.cpp)
 }  // namespace rl
 
 #define HIP_TRY(expr)                                                                                   \
@@ -96,6 +97,9 @@ struct rl_ctx {
     // rl_tile_gather, rl_tile_blend (tile_api.cpp): a grow-only workspace for the slot list / the layout tables of a call; freed
     // with the context
     EnsembleWork tile;
+    // rl_ingest, rl_export (stack_api.cpp): a grow-only workspace for the per-workgroup partials of a call's statistics; freed with
+    // the context
+    EnsembleWork ingest;
 
     int device = 0;
     hipStream_t stream = nullptr;

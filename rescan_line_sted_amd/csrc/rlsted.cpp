@@ -1231,6 +1231,11 @@ struct rl_deconv {
     }
 };
 
+namespace rl {
+// the context a plan was created on (ctx.hpp): what stack_api.cpp, which sees the plan through the C ABI only, enqueues on
+rl_ctx* plan_ctx(rl_deconv* h) { return h ? h->ctx : nullptr; }
+}  // namespace rl
+
 extern "C" {
 
 const char* rl_last_error(void) { return rl::last_error().c_str(); }

@@ -35,6 +35,10 @@ I-divergence, formed on the device.
 Large images: `deconvolve_tiled` (tiling.py) cuts images of any size into
 overlapping tiles of one plan and blends the tile estimates on the device
 (INTEGRATION.md section 5g).
+
+Acquired stacks: `deconvolve_stack` (stack.py) takes uint8 / uint16 / int16 /
+float32 camera frames as they are, forms the measurement on the device and
+overlaps the transfers with the iterations.
 """
 import os
 import time
@@ -44,6 +48,7 @@ import numpy as np
 from . import _lib
 from ._lib import DeconvPlan, RNG_NONE, RNG_PHILOX
 from .tiling import deconvolve_tiled   # noqa: F401  (re-exported)
+from .stack import CameraModel, deconvolve_stack   # noqa: F401  (re-exported)
 
 _DEFAULT_DTYPE = os.environ.get('RLSTED_DTYPE', 'f64')
 _DEFAULT_DEVICE = _lib.DEFAULT_DEVICE

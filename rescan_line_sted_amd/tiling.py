@@ -160,6 +160,28 @@ class _Device:
         self.src = self.alloc(measurement.size)
         check(lib.rl_device_upload(self.ctx.handle, self.src, self.code, measurement.size, _lib.ptr(measurement)))
 
+    def upload_raw(self, raw, camera):
+        """(F, V, NY, NX) camera data in its own dtype -> device as it is (rl_device_upload_bytes: no host copy), then ingested ONCE
+        (include/rlsted.h rl_ingest) into the full-size image of the plan's element type that gather() reads."""
+        from .stack import raw_code
+        F, V, NY, NX = self.src_shape = raw.shape
+
+        def narrow(a):
+            p = ctypes.c_void_p()
+            check(lib.rl_device_alloc(self.ctx.handle, a.nbytes, ctypes.byref(p)))
+            self.owned.append(p)
+            check(lib.rl_device_upload_bytes(self.ctx.handle, p, a.ctypes.data_as(ctypes.c_void_p), a.nbytes))
+            return p
+        raw_dev = narrow(raw)
+        dark_dev = None if camera.dark_map is None else narrow(camera.dark_map)
+        self.src = self.alloc(raw.size)
+        check(lib.rl_ingest(self.ctx.handle, raw_dev, raw_code(raw), F * V, NY, NX, 0, 0, V, 1, F, F, V, NY, NX, dark_dev, camera.dark,
+                            camera.gain, camera.epsilon, 0.0 if camera.saturation is None else camera.saturation, self.src, self.code, None))
+        for p in (raw_dev, dark_dev):
+            if p is not None:
+                self.owned.remove(p)
+                check(lib.rl_device_free(self.ctx.handle, p))      # (waits for the ingest)
+
     def gather(self, slots):
         F, V, NY, NX = self.src_shape
         check(lib.rl_tile_gather(self.ctx.handle, self.src, self.code, F, V, NY, NX, _ints(slots), len(slots), self.tile_shape[0],
@@ -200,7 +222,7 @@ class _Device:
 
 
 def deconvolve_tiled(measurement, psfs, iterations, tile=None, overlap=None, margin=None, dtype='f32', device=None, batch=None,
-                     acceleration=None, tv_lambda=None, tv_epsilon=0.1, until=None, keep_on_device=False):
+                     acceleration=None, tv_lambda=None, tv_epsilon=0.1, until=None, keep_on_device=False, camera=None):
     """`iterations` Richardson-Lucy iterations on images of any size, tile by tile: measurement (F, V, NY, NX) or (V, NY, NX).
     tile: one number or (y, x) (default_tile(psfs)); margin: pixels at every interior tile edge that do not contribute
     (DEFAULT_MARGIN; exact_margin(psfs, iterations) makes the result the whole-image one up to rounding); overlap: at least this
@@ -211,12 +233,20 @@ def deconvolve_tiled(measurement, psfs, iterations, tile=None, overlap=None, mar
     own divergence (DeconvPlan.iterate_until, `iterations` at most).
     Returns (estimate (F, NY, NX) float64, info); info: 'layout' (TileLayout), 'tiles', 'batch', 'chunks', 'unresolved' (the plan's
     count over all tiles), 'strategy' (DeconvPlan.strategy() of the tile plan on the last chunk) and, with until, 'iterations' (F, tiles down, tiles across).  keep_on_device=True: the estimate stays on
-    the GPU, a TiledResult (.download(); .dev, .dtype, .offsets, .shape for quality.ring_stats_device)."""
+    the GPU, a TiledResult (.download(); .dev, .dtype, .offsets, .shape for quality.ring_stats_device).
+    camera: None, or a stack.CameraModel -- the measurement is then camera data in its own dtype (uint8, uint16, int16, float32; a
+    dark map has the image's shape), uploaded as it is and turned into the measurement on the device, max((raw - dark) * gain, 0)
+    + epsilon in float64 rounded once to the plan's element type."""
     _lib.tv_params(tv_lambda, tv_epsilon)
     _lib.accel_mode(acceleration)
     if dtype not in DTYPES:
         raise ValueError("dtype must be 'f32' or 'f64'; got %r" % (dtype,))
-    measurement = np.ascontiguousarray(measurement, dtype=np.float64)
+    if camera is None:
+        measurement = np.ascontiguousarray(measurement, dtype=np.float64)
+    else:
+        from .stack import raw_code
+        raw_code(measurement)                                # (ValueError for a dtype that is not taken as it is)
+        measurement = np.ascontiguousarray(measurement)
     if measurement.ndim == 3:
         measurement = measurement[None]
     if measurement.ndim != 4 or 0 in measurement.shape:
@@ -233,6 +263,8 @@ def deconvolve_tiled(measurement, psfs, iterations, tile=None, overlap=None, mar
     margin = DEFAULT_MARGIN if margin is None else int(margin)
     layout = TileLayout((NY, NX), default_tile(psfs) if tile is None else tile, default_overlap(margin) if overlap is None else overlap,
                         margin)
+    if camera is not None:
+        camera.check_window(NY, NX)
     slots = layout.slots(F)
     tiles = len(slots)
     batch = min(tiles, 32) if batch is None else int(batch)
@@ -241,7 +273,10 @@ def deconvolve_tiled(measurement, psfs, iterations, tile=None, overlap=None, mar
     ty, tx = layout.tile_shape
     dev = _Device(psfs, batch, (ty, tx), dtype, _lib.DEFAULT_DEVICE if device is None else device, acceleration, tv_lambda, tv_epsilon)
     try:
-        dev.upload(measurement)
+        if camera is None:
+            dev.upload(measurement)
+        else:
+            dev.upload_raw(measurement, camera)
         store = dev.alloc(tiles * ty * tx)
         counts = np.zeros(tiles, dtype=np.int64)
         chunks = 0
