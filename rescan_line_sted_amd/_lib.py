@@ -87,6 +87,7 @@ PROTOTYPES = {
     'rl_deconv_strategy': (_i, [_vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)]),
     'rl_deconv_object_classes': (_i, [_vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)]),
     'rl_deconv_simulated_images': (_i, [_vp, _c.POINTER(_i)]),
+    'rl_deconv_draws_ahead': (_i, [_vp, _c.POINTER(_i)]),
     'rl_deconv_unresolved': (_i, [_vp, _c.POINTER(_c.c_uint64), _i]),
     'rl_deconv_dims': (_i, [_vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)]),
     'rl_batch_run': (_i, [_vp, _vp, _i, _i, _i, _dp]),
@@ -301,6 +302,13 @@ class DeconvPlan:
         cycle's sharing slices hold counts once, whatever the number of slices that draw from it."""
         a = _i()
         check(lib.rl_deconv_simulated_images(self.handle, ctypes.byref(a)))
+        return a.value
+
+    def draws_ahead(self):
+        """Slices of the last cycle whose Poisson draw ran on the draw stream, ahead of their lane (include/rlsted.h
+        rl_deconv_draws_ahead); 0 where every slice drew at the head of its lane."""
+        a = _i()
+        check(lib.rl_deconv_draws_ahead(self.handle, ctypes.byref(a)))
         return a.value
 
     def set_object(self, obj, total_brightness=None):

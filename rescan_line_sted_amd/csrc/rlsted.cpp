@@ -78,6 +78,14 @@ struct PlanOptions {
     // the tail of one slice's kernel (the last, partly filled round of workgroups) overlaps another
     // slice's kernels.  RLSTED_LANES=1: one slice after the other on the context's stream (at most kMaxLanes).
     int lanes = 2;
+    // RLSTED_DRAW_AHEAD=1: a sharing slice's Poisson draw goes to the context's stream -- idle while the lanes run --, one slice
+    // per lane ahead of the loops and RLSTED_DRAW_GRID workgroups wide (at most aux_kernels.hpp kPoissonGrid), beside the loop of
+    // the slice in front (rl_deconv::run_slices); unset: every slice draws at the head of its lane.  OFF by default: bench.py's
+    // lone plan gains nothing (46.44 ms off, 46.59 ms on, four alternating runs each), plans in a crowded process 0.4 - 0.7 ms --
+    // unless the context's stream shares a hardware queue with a lane (8 plans on 4 queues), where the same cycle takes
+    // 52 - 59 ms (DESIGN.md section 4 "Draws ahead", profiles/draw_ahead).  Grid, same tables: 64 .. 512 within 0.2 ms of each other.
+    bool draw_ahead = false;
+    int draw_grid = 128;
     bool inplace = true;         // RLSTED_INPLACE=0: single-view RL iterations spec_a -> spec_b -> spec_a instead of entirely in spec_a
     // RLSTED_COL_ORDER: column kernel work order, images per block of the tile order (fft_kernels.hip k_colconv):
     // 1 image-major ... >= images per launch: tile-major.  Measured at 512^2, 32-frame
@@ -118,6 +126,8 @@ PlanOptions plan_options(int dtype, int n_psf) {
         o.chunk_mb = atof(s);
     }
     o.lanes = std::min(std::max(number("RLSTED_LANES", o.lanes), 1), kMaxLanes);
+    o.draw_ahead = flag("RLSTED_DRAW_AHEAD", o.draw_ahead);
+    o.draw_grid = std::min(std::max(number("RLSTED_DRAW_GRID", o.draw_grid), 1), (int)kPoissonGrid);
     o.inplace = flag("RLSTED_INPLACE", o.inplace);
     o.col_order = std::max(number("RLSTED_COL_ORDER", o.col_order), 1);
     o.pair = flag("RLSTED_PAIR", dtype == RL_F32 && n_psf == 1);
@@ -874,6 +884,8 @@ struct rl_deconv {
             HIP_TRY(hipStreamCreateWithFlags(&lane_stream[l], hipStreamNonBlocking));
             HIP_TRY(hipEventCreateWithFlags(&lane_done[l], hipEventDisableTiming));
             HIP_TRY(hipEventCreateWithFlags(&lane_drawn[l], hipEventDisableTiming));
+            HIP_TRY(hipEventCreateWithFlags(&lane_begun[l], hipEventDisableTiming));
+            HIP_TRY(hipEventCreateWithFlags(&drawn_ahead[l], hipEventDisableTiming));
         }
         HIP_TRY(hipEventCreateWithFlags(&rates_ready, hipEventDisableTiming));
         return RL_OK;
@@ -974,6 +986,18 @@ struct rl_deconv {
     int last_sim_images = 0;               // images H was computed for in the last cycle (rl_deconv_simulated_images)
     bool noiseless_sparse = false;         // the last simulation left (some) slices' rates in noiseless_c only
     int last_shared_slices = 0, last_slices = 0;
+    // ---- draws ahead (run_slices): the sharing slices' draws and the class simulation go to the draw stream, which is the
+    // CONTEXT'S stream: it has nothing to do between the fork and the join of the lanes, whatever it holds is in front of the join
+    // by stream order (error paths included), and it has a hardware queue of its own.  A further stream does not: the runtime deals
+    // a process's streams to 4 hardware queues by default, the null stream, the context's and two lanes take them, and a fifth
+    // stream shares a queue with one of the lanes, where its waits stop that lane's launches -- measured, the headline on a stream
+    // of its own: 58.7 ms per cycle against the parent's 47.5 ms in a process with one plan (profiles/draw_ahead).
+    // lane_begun[l]: recorded on lane l in front of a slice's first iteration launch; drawn_ahead[l]: behind the draw of the slice
+    // that lane l takes next.
+    hipStream_t draw_stream() const { return ctx->stream; }
+    hipEvent_t lane_begun[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr}, drawn_ahead[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr};
+    bool lane_begun_set[kMaxLanes] = {false, false, false, false};   // by the cycle before, whose lanes are still open
+    int last_draws_ahead = 0;              // slices of the last cycle whose draw went to the draw stream (rl_deconv_draws_ahead)
     bool share_possible() const { return opt.share_objects && !sep && (int)obj_class.size() == B && n_classes < B; }
     // The layout for slices of cf frames from obj_class, its lists on the device -- `staged`: already there (rl_batch_submit puts
     // them into the chunk's block), otherwise uploaded here -- and the representatives' objects gathered from obj.  On the
@@ -1060,7 +1084,7 @@ struct rl_deconv {
             HIP_TRY(hipEventRecord(lane_done[l], lane_stream[l]));
             HIP_TRY(hipStreamWaitEvent(ctx->stream, lane_done[l], 0));
         }
-        return RL_OK;
+        return RL_OK;   // (a draw that the failed cycle enqueued and no lane waited for is on the context's stream itself)
     }
     // the Poisson draw of a whole cycle: one seed for the batch, or -- rl_batch_submit -- a Philox key per frame (device arrays of B entries)
     struct Draw { int rng_kind; uint64_t seed; const unsigned long long* key_seeds; const unsigned* key_ids; };
@@ -1103,7 +1127,28 @@ struct rl_deconv {
             RL_TRY(ensure_lanes());
             HIP_TRY(hipEventRecord(fork, ctx->stream));
             for (int l = 0; l < nl; ++l) HIP_TRY(hipStreamWaitEvent(lane_stream[l], fork, 0));
+            for (bool& b : lane_begun_set) b = false;   // (nothing of an earlier cycle is still running)
         }
+        // Draws ahead (RLSTED_DRAW_AHEAD=1; what it measured and why it is off by default: PlanOptions).  The sampler is bound by vector issue, the RL kernels by the memory system, yet a slice's full-width draw at
+        // the head of its lane floods every SIMD and the other lane's loop all but stops beside it.  So the draw of a SHARING slice sl
+        // -- it reads the class rates only -- goes to the draw stream (above), opt.draw_grid workgroups wide, behind the "begun" event of the
+        // slice IN FRONT of sl on its lane: it runs in the background of that slice's loop and is finished long before lane sl % nl
+        // wants it (the lane waits for drawn_ahead).  The begun event is the throttle -- the draw stream is never more than one slice
+        // per lane ahead of the loops -- and what frees `meas` of slice sl: the loop that read it last (the cycle before) precedes
+        // the slice in front on the same lane.  Across cycles whose lanes stay open the slice in front is the lane's last of the
+        // cycle before; a lane that holds ONE slice would draw into the measurement that slice still iterates on, and keeps its
+        // in-lane draw, as do the first slices of a cycle that follows nothing (no loop to hide behind) and slices that do not share.
+        // (Round 1 tried the simulation of all slices ahead of the RL lanes on a stream of its own and lost, 16.5 k against 17.2 k
+        // frames/s: 2.3 GB of per-frame simulation spectra streamed through the Infinity Cache with nothing bounding the run-ahead
+        // pushed the iterating slices' working sets out.  A sharing slice's draw reads one class image and writes its measurement,
+        // 33.5 MB at 512^2, and at most one per lane is ahead.)
+        const bool ahead = opt.draw_ahead && share && share_classes > 0 && nl > 1 && slices > nl;
+        std::vector<char> on_draw_stream((size_t)slices, 0);
+        for (int sl = 0; ahead && sl < slices; ++sl) {
+            const int on_lane = (slices - sl % nl + nl - 1) / nl;   // slices that go to this one's lane
+            on_draw_stream[(size_t)sl] = share_slices[(size_t)sl].nrep > 0 && (sl >= nl || (lane_begun_set[sl] && on_lane >= 2));
+        }
+        int draws_ahead = 0;
         if (draw) {   // one Poisson work list per slice: slices on different lanes run at the same time
             const size_t stride = (aux_poisson_workspace_bytes((size_t)cf * V * n_img()) + 255) / 256 * 256;
             if (slice_ws_bytes < stride * slices) {
@@ -1125,12 +1170,13 @@ struct rl_deconv {
             return e == hipSuccess ? RL_OK : fail(RL_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
         };
         // The cycle's class simulation: H of every class the sharing slices hold, once, on the stream that starts the cycle's first
-        // slice.  It replaces the rates the cycle before drew from, so it first waits for that cycle's last shared draw on every
+        // slice -- or, with draws ahead, on the draw stream: behind the last draw of the cycle before by stream order and beside that
+        // cycle's tail, not behind lane 0's last slice.  It replaces the rates the cycle before drew from, so it first waits for that cycle's last shared draw on every
         // lane (lanes that stay open between cycles do not meet otherwise); the other lanes wait for it before their first shared draw.
         bool lane_waits[kMaxLanes] = {false, false, false, false};   // lane l has yet to wait for rates_ready
         int lane_last_shared[kMaxLanes] = {-1, -1, -1, -1};          // the last sharing slice that goes to lane l
         if (share && share_classes > 0) {
-            active = nl > 1 ? lane_stream[0] : nullptr;
+            active = ahead ? draw_stream() : nl > 1 ? lane_stream[0] : nullptr;
             for (int l = 0; l < kMaxLanes && rc == RL_OK; ++l) {
                 if (!lane_drawn_set[l]) continue;
                 lane_drawn_set[l] = false;
@@ -1140,9 +1186,9 @@ struct rl_deconv {
             sim_images += share_classes * V;
             if (nl > 1 && rc == RL_OK) {
                 rc = hip_rc(hipEventRecord(rates_ready, cur()), "class simulation");
-                for (int l = 1; l < nl; ++l) lane_waits[l] = true;
-                for (int sl = 0; sl < slices; ++sl)
-                    if (share_slices[(size_t)sl].nrep > 0) lane_last_shared[sl % nl] = sl;
+                for (int l = ahead ? 0 : 1; l < nl; ++l) lane_waits[l] = true;
+                for (int sl = 0; sl < slices; ++sl)   // (in-lane draws; those on the draw stream precede the next simulation there)
+                    if (share_slices[(size_t)sl].nrep > 0 && !on_draw_stream[(size_t)sl]) lane_last_shared[sl % nl] = sl;
             }
         }
         auto simulate_slice = [&](int sl, int f0, int nf) -> int {
@@ -1150,11 +1196,32 @@ struct rl_deconv {
             const SliceShare ss = share ? share_slices[(size_t)sl] : SliceShare{};
             const void* rates = off(noiseless, (size_t)f0 * V * n_img());
             const int lane = nl > 1 ? sl % nl : 0;
-            if (ss.nrep > 0) {
-                if (lane_waits[lane]) {
-                    HIP_TRY(hipStreamWaitEvent(cur(), rates_ready, 0));
-                    lane_waits[lane] = false;
+            if (on_draw_stream[(size_t)sl]) {   // behind the class simulation by stream order: no wait for rates_ready
+                hipStream_t lane_s = cur();
+                active = draw_stream();
+                hipError_t e = hipStreamWaitEvent(draw_stream(), lane_begun[lane], 0);
+                if (e == hipSuccess) {
+                    TimedScope t(this, TK_POISSON, false);   // (records on cur(): the draw stream)
+                    e = aux_poisson(dtype, noiseless_c, off(meas, (size_t)f0 * V * n_img()), (unsigned)n_img(), (unsigned)(nf * V),
+                                    (unsigned)(f0 * V), draw->seed, draw->rng_kind, nullptr, draw_stream(),
+                                    draw->key_seeds ? draw->key_seeds + f0 : nullptr, draw->key_ids ? draw->key_ids + f0 : nullptr,
+                                    (unsigned)V, share_lists.rate_of + f0, (unsigned)opt.draw_grid);
                 }
+                active = lane_s;
+                if (e != hipSuccess) return fail(RL_ERR_HIP, std::string("Poisson kernels: ") + hipGetErrorString(e));
+                HIP_TRY(hipEventRecord(drawn_ahead[lane], draw_stream()));
+                HIP_TRY(hipStreamWaitEvent(lane_s, drawn_ahead[lane], 0));
+                ++shared_slices;
+                ++draws_ahead;
+                return RL_OK;
+            }
+            // (with draws ahead every lane waits once, a slice that does not share too: whatever the context's stream held before the
+            // class simulation -- accel_reset's memset -- then precedes the lane's loops of this cycle as it does when the lanes fork)
+            if ((ss.nrep > 0 || ahead) && lane_waits[lane]) {
+                HIP_TRY(hipStreamWaitEvent(cur(), rates_ready, 0));
+                lane_waits[lane] = false;
+            }
+            if (ss.nrep > 0) {
                 rates = noiseless_c;
                 ++shared_slices;
             } else {
@@ -1174,13 +1241,14 @@ struct rl_deconv {
             }
             return RL_OK;
         };
-        // (Round 1 also tried the simulation of all slices ahead of the RL lanes on a stream of its own: 16.5 k against 17.2 k
-        // frames/s -- 2.3 GB streamed through the memory system while the first slices iterate push their working sets out of the
-        // Infinity Cache.  Slice by slice on the RL lanes the same overlap happens between lanes.)
         for (int sl = 0, f0 = 0; f0 < B && rc == RL_OK; f0 += cf, ++sl) {
             const int nf = f0 + cf <= B ? cf : B - f0;
             active = nl > 1 ? lane_stream[sl % nl] : nullptr;
             if (draw) rc = simulate_slice(sl, f0, nf);
+            if (ahead && rc == RL_OK) {   // the throttle of the draw of the next slice on this lane
+                rc = hip_rc(hipEventRecord(lane_begun[sl % nl], cur()), "draw ahead");
+                lane_begun_set[sl % nl] = rc == RL_OK;
+            }
             const bool shortcut = restart && opt.ones_shortcut && spec_ones && k > 0 && !sep;
             // The plain loop's first iteration reads neither the estimate's spectrum (shortcut) nor -- est_one -- the estimate, and its
             // ROW_UPDATE writes every pixel of it: nothing is filled.  The accelerated and the regularised steps read est themselves.
@@ -1209,6 +1277,7 @@ struct rl_deconv {
         }
         RL_TRY(rc);
         if (draw) {
+            last_draws_ahead = draws_ahead;
             noiseless_sparse = shared_slices > 0;
             last_shared_slices = shared_slices;
             last_slices = slices;
@@ -1336,6 +1405,8 @@ int rl_deconv_destroy(rl_deconv* h) {
     for (int l = 0; l < kMaxLanes; ++l) {
         if (h->lane_done[l]) (void)hipEventDestroy(h->lane_done[l]);
         if (h->lane_drawn[l]) (void)hipEventDestroy(h->lane_drawn[l]);
+        if (h->lane_begun[l]) (void)hipEventDestroy(h->lane_begun[l]);
+        if (h->drawn_ahead[l]) (void)hipEventDestroy(h->drawn_ahead[l]);
         if (h->lane_stream[l]) (void)hipStreamDestroy(h->lane_stream[l]);
     }
     delete h;
@@ -1945,6 +2016,12 @@ int rl_deconv_object_classes(const rl_deconv* h, int* classes, int* shared_slice
     if (classes) *classes = (int)h->obj_class.size() == h->B ? h->n_classes : 0;
     if (shared_slices) *shared_slices = h->last_shared_slices;
     if (slices) *slices = h->last_slices;
+    return RL_OK;
+}
+
+int rl_deconv_draws_ahead(const rl_deconv* h, int* slices) {
+    if (!h || !slices) return fail(RL_ERR_INVALID, "NULL argument");
+    *slices = h->last_draws_ahead;
     return RL_OK;
 }
 

@@ -1,5 +1,7 @@
 """Manual helper (not a test): A/B of run-time switches (RLSTED_* read at plan creation) in ONE process, interleaved rounds.
     python3 tools/gpu/env_ab.py SIZE VIEWS BATCH "A=1,B=2" "A=0" ...      (each argument: one configuration's environment)
+OBJECT=astronaut in the environment of the tool itself: the headline's object (bench.py: astronaut 128 -> 512, np.kron x 4) instead of
+uniform noise -- a kernel whose cost follows the rates (the Poisson sampler) sees dark and bright regions only there.
 """
 import os
 import sys
@@ -15,6 +17,9 @@ n, V, B = (int(x) for x in sys.argv[1:4])
 g = np.load(os.path.join(ROOT, 'tests', 'golden', 'g8_fig2_psfs.npz'))
 psfs = [g['2p0x_lr/point_sted_psf'][0]] if V == 1 else [p[None] for p in g['2p0x_lr/line_sted_psfs'][:V, 0]]
 obj = np.random.default_rng(1234).random((n, n)) * 255
+if os.environ.get('OBJECT') == 'astronaut':
+    astronaut = np.load(os.path.join(ROOT, 'tests', 'golden', 'objects.npz'))['astronaut'].astype(np.float64)
+    obj = np.kron(astronaut, np.ones((1, n // 128, n // 128)))[0]
 plans = []
 for cfg in sys.argv[4:]:
     env = dict(kv.split('=') for kv in cfg.split(',') if kv)
