@@ -19,6 +19,7 @@
 #include "aux_kernels.hpp"
 #include "checkpoint_kernels.hpp"
 #include "conv_kernels.hpp"
+#include "cycle_schedule.hpp"
 #include "kernel_table.hpp"
 #include "object_classes.hpp"
 #include "ctx.hpp"
@@ -66,8 +67,6 @@ const int kLengths[] = {64, 192, 256, 576, 1152, 2304, 4608};
 
 size_t esize(int dtype) { return dtype == RL_F32 ? 4 : 8; }
 
-constexpr int kMaxLanes = 4;
-
 // Every RLSTED_* switch of a plan (RLSTED_DEBUG_SYNC is process wide: rl::debug_sync; RLSTED_SEP_TH: sep_kernels.hip).  Read once,
 // when the plan is created; nothing after plan_options() looks at the environment.  The defaults are the measured optimum.
 struct PlanOptions {
@@ -80,7 +79,7 @@ struct PlanOptions {
     int lanes = 2;
     // RLSTED_DRAW_AHEAD=1: a sharing slice's Poisson draw goes to the context's stream -- idle while the lanes run --, one slice
     // per lane ahead of the loops and RLSTED_DRAW_GRID workgroups wide (at most aux_kernels.hpp kPoissonGrid), beside the loop of
-    // the slice in front (rl_deconv::run_slices); unset: every slice draws at the head of its lane.  OFF by default: bench.py's
+    // the slice in front (cycle_schedule.hpp); unset: every slice draws at the head of its lane.  OFF by default: bench.py's
     // lone plan gains nothing (46.44 ms off, 46.59 ms on, four alternating runs each), plans in a crowded process 0.4 - 0.7 ms --
     // unless the context's stream shares a hardware queue with a lane (8 plans on 4 queues), where the same cycle takes
     // 52 - 59 ms (DESIGN.md section 4 "Draws ahead", profiles/draw_ahead).  Grid, same tables: 64 .. 512 within 0.2 ms of each other.
@@ -239,11 +238,34 @@ struct rl_deconv {
     // H_t views summed before the inverse transforms (one clamp of the sum instead of one per
     // view, ref:587): default for f32 plans, off for f64 (faithful); RLSTED_FUSE_VIEWS=0/1 overrides
     bool fuse_views = false;
-    hipStream_t lane_stream[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t lane_done[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t fork = nullptr;
+    // ---- streams and events: every one the plan creates comes from here and goes in rl_deconv_destroy
+    struct Handles {
+        std::vector<hipStream_t> streams;
+        std::vector<hipEvent_t> events;
+        int stream(hipStream_t* s) {
+            HIP_TRY(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+            streams.push_back(*s);
+            return RL_OK;
+        }
+        int event(hipEvent_t* e, unsigned flags = hipEventDisableTiming) {
+            HIP_TRY(hipEventCreateWithFlags(e, flags));
+            events.push_back(*e);
+            return RL_OK;
+        }
+    };
+    Handles handles;
+    // A lane of run_slices (cycle_schedule.hpp): its stream and the events recorded on it or for it -- done: its end, for the join;
+    // drawn: behind its last in-lane draw from the class rates, for the next cycle's class simulation; begun: in front of a slice's
+    // first iteration launch, and drawn_ahead: behind the draw, on the context's stream, of the slice the lane takes next (draws ahead).
+    struct Lane {
+        hipStream_t stream = nullptr;
+        hipEvent_t done = nullptr, drawn = nullptr, begun = nullptr, drawn_ahead = nullptr;
+    };
+    Lane lane[kMaxLanes];
+    hipEvent_t fork = nullptr, rates_ready = nullptr;   // the lanes leave the context's stream; the class rates are written
+    CycleSchedule schedule;                           // of the run at hand (kept: the list is rebuilt in place)
+    CycleState cycle_state;                           // what the last run left behind: lanes still open, events the next cycle waits for
     hipStream_t active = nullptr;                     // stream the kernel launch helpers use
-    bool lanes_open = false;                          // the lanes were left unjoined: between the back-to-back cycles of rl_deconv_bench_cycles
     void* slice_ws = nullptr;                         // per-slice Poisson work lists of run_slices()
     void *key_seeds = nullptr, *key_ids = nullptr;    // per-frame Philox keys of rl_deconv_simulate_keyed
     size_t slice_ws_bytes = 0, slice_ws_stride = 0;
@@ -271,12 +293,12 @@ struct rl_deconv {
     int ensure_batch_slots() {
         if (batch_slots_ready) return RL_OK;
         // (a call that failed half way is taken up where it stopped: every resource is created once, the destructor frees what exists)
-        if (!copy_stream) HIP_TRY(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
+        if (!copy_stream) RL_TRY(handles.stream(&copy_stream));
         for (BatchSlot& sl : bslot) {
             if (!sl.host) HIP_TRY(hipHostMalloc((void**)&sl.host, slot_host_bytes(), hipHostMallocDefault));
             if (!sl.dev) RL_TRY(alloc(&sl.dev, slot_host_bytes() + 8 + aux_sums_elems((size_t)B) * sizeof(double)));
-            if (!sl.uploaded) HIP_TRY(hipEventCreateWithFlags(&sl.uploaded, hipEventDisableTiming));
-            if (!sl.freed) HIP_TRY(hipEventCreateWithFlags(&sl.freed, hipEventDisableTiming));
+            if (!sl.uploaded) RL_TRY(handles.event(&sl.uploaded));
+            if (!sl.freed) RL_TRY(handles.event(&sl.freed));
         }
         batch_slots_ready = true;
         return RL_OK;
@@ -317,8 +339,7 @@ struct rl_deconv {
         if (!from_ones) {
             HIP_TRY(accel_extrapolate(dtype, off(est, o), off(acc_y, o), off(acc_x, o), part, acc_alpha + f0, n_img(), nf,
                                       s == 0 ? ACC_FRESH : 0, cur()));
-            if (pair) RL_TRY(row_pair(ROW_FWD, nf, nullptr, pair_spec(f0), off(est, o), nullptr, nullptr));
-            else if (!sep) RL_TRY(row(ROW_FWD, (unsigned)nf, nullptr, off(spec_a, (size_t)f0 * n_spec() * 2), off(est, o), nullptr, nullptr));
+            RL_TRY(est_spectrum(f0, nf));
         }
         const Iter it{f0, nf, first, from_ones, /* drop_spectrum */ pair};
         RL_TRY(tv_on() ? tv_iterate(it, /* have_sum */ false, /* rebuild_spectrum */ false) : iterate_chunk(it));   // (est = y_s: the sum is not of it)
@@ -348,9 +369,7 @@ struct rl_deconv {
         if (sep) {
             RL_TRY(sep_forward(est, scratch, sep_tmp(), B));
         } else {
-            RL_TRY(row(ROW_FWD, (unsigned)B, nullptr, spec_a, est, nullptr, nullptr));
-            RL_TRY(col(spec_a, spec_b, B, COL_H));
-            RL_TRY(row(ROW_INV, (unsigned)(B * V), spec_b, nullptr, nullptr, scratch, nullptr));
+            RL_TRY(forward_pass(est, scratch, B, spec_a, spec_b, nullptr));
             spec_valid = false;
         }
         HIP_TRY(stop_divergence(dtype, meas, scratch, stop_part, n_frame(), B, cur()));
@@ -396,8 +415,7 @@ struct rl_deconv {
         if (!it.from_ones) {
             if (!have_sum) HIP_TRY(tv_apply(dtype, off(est, o), nullptr, part, ny, nx, it.nf, TV_SUM_ONLY, cur()));
             HIP_TRY(tv_weight(dtype, off(est, o), off(tv_w, o), part, tv_lambda, tv_eps_rel, ny, nx, it.nf, cur()));
-            if (rebuild_spectrum && pair) RL_TRY(row_pair(ROW_FWD, it.nf, nullptr, pair_spec(it.f0), off(est, o), nullptr, nullptr));
-            else if (rebuild_spectrum && !sep) RL_TRY(row(ROW_FWD, (unsigned)it.nf, nullptr, est_spec(it.f0), off(est, o), nullptr, nullptr));
+            if (rebuild_spectrum) RL_TRY(est_spectrum(it.f0, it.nf));
         }
         RL_TRY(iterate_chunk(it));
         HIP_TRY(tv_apply(dtype, off(est, o), it.from_ones ? nullptr : off(tv_w, o), part, ny, nx, it.nf, it.from_ones ? TV_SUM_ONLY : 0, cur()));
@@ -428,6 +446,21 @@ struct rl_deconv {
             pair = want;
             spec_valid = false;   // spec_a holds the other layout's spectra
         }
+    }
+    // ---- state transitions, named after tests/plan_model.py
+    // set_measurement, for a measurement the plan draws from its object: the frames' levels follow the object's, and no pixel is
+    // negative (Poisson draws + 1e-9; an earlier upload's negative pixels are gone: sub()).  What else a caller sets differs.
+    void set_measurement_from_object() {
+        meas_level = obj_level;
+        choose_loop(meas_level);
+        meas_negative = false;
+    }
+    // set_estimate: est holds a point with no history; the next iterate rebuilds rowFFT(estimate)
+    int set_estimate() {
+        est_ready = true;
+        spec_valid = false;
+        tv_sum_valid = false;
+        return accel_reset();
     }
     // The measurement buffer was handed out (rl_deconv_device_ptr which = 1) and may have been written on the device: the per-frame
     // sums are recomputed there before the next run decides between the pair loop and the per-frame loop.
@@ -645,7 +678,7 @@ struct rl_deconv {
     hipEvent_t pool_event() {
         if (events_used == event_pool.size()) {
             hipEvent_t e = nullptr;
-            if (hipEventCreate(&e) != hipSuccess) return nullptr;
+            if (handles.event(&e, hipEventDefault) != RL_OK) return nullptr;
             event_pool.push_back(e);
         }
         return event_pool[events_used++];
@@ -828,67 +861,33 @@ struct rl_deconv {
         return RL_OK;
     }
 
-    // ---- frame chunks: run the whole K-iteration loop on a slice of the batch whose
-    // working set (spectra + measurement + estimate) fits the 256 MiB Infinity Cache,
-    // so the inter-kernel traffic is served on die instead of from HBM.
     char* off(void* base, size_t elems) const { return (char*)base + elems * esize(dtype); }
+    // frames of a slice of the batch (cycle_schedule.hpp: the rules and what they measured)
     int chunk_frames() const {
-        // per slice; `lanes` slices are in flight at once, together about the 256 MiB Infinity Cache
-        const double budget_mb = opt.chunk_mb_set ? opt.chunk_mb : (opt.lanes > 1 ? 108.0 : 288.0);
-        const double specs = one_buffer() ? 1.0 : 1.0 + V;   // spectra alive in an iteration
-        const double per_frame = (specs * 2.0 * n_spec() + (1.0 + V + (accel ? 3.0 : 0.0) + (tv_on() ? 1.0 : 0.0)) * n_img()) * esize(dtype);   // (+ x, y, g; + w)
-        // Frames of 32 MB and more (2048^2 up) do not live in the Infinity Cache whatever the slice: there the slice
-        // only has to fill the chip -- ~1 GB per slice measured best at 2048^2 (point 658 -> 713, 4 views 180 -> 192
-        // frames/s over 2-frame / 1-frame slices).
-        int c = (int)((!opt.chunk_mb_set && per_frame >= 32.0 * 1048576.0 ? 1024.0 : budget_mb) * 1048576.0 / per_frame);
-        // many views: at least 8 frames per slice when no budget was given -- fewer leave the column
-        // kernels (37 workgroups per 512^2 frame) too small to fill the chip (6 / 8 views: +10 % / +7 %)
-        if (!opt.chunk_mb_set && c < 8 && per_frame * 8.0 <= 300.0 * 1048576.0) c = 8;
-        // ... and enough frames for the column launches to fill the chip once (two 8-wave workgroups per CU): 512^2 has 37 column
-        // tiles per frame, so 16 frames -- measured 3 / 4 views 6968 -> 7826 / 5840 -> 6100 frames/s over 8-frame slices
-        if (!opt.chunk_mb_set && V > 1) {
-            const int cw = ty->C[dtype] > 0 ? ty->C[dtype] : 8, tiles = (kx + cw - 1) / cw;
-            const int need = ((512 + tiles - 1) / tiles + 7) / 8 * 8;
-            if (c < need && per_frame * need <= 300.0 * 1048576.0) c = need;
-        }
-        if (c < 1) c = 1;
-        if (c >= B) return B;
-        // equal slices (a short last slice would run its 4 launches per iteration nearly empty; slices BALANCED to within one frame --
-        // 6 6 5 5 5 5 instead of 6 6 6 6 6 2 for 32 frames -- measured +1 % at 2048^2 x 4 views and -1 % at 512^2 x 4 views, 250 frames: not done)
-        const int fit = c;                       // frames the budget holds
-        const int slices = (B + c - 1) / c;
-        c = (B + slices - 1) / slices;
-        if (c > 8) {                               // whole groups of 8 frames: up if that still fits the budget, down otherwise
-            const int up = (c + 7) / 8 * 8;
-            c = up <= fit ? up : std::max(8, fit / 8 * 8);
-        }
-        if (pair && (c & 1)) ++c;   // slices of whole frame pairs
-        return c >= B ? B : c;
+        return rl::chunk_frames({B, V, n_img(), n_spec(), esize(dtype), one_buffer(), accel != RL_ACCEL_NONE, tv_on(), pair, opt.chunk_mb_set,
+                                 opt.chunk_mb, opt.lanes, ty->C[dtype], kx});
+    }
+    // rowFFT(est) of frames [f0, f0 + nf) in the layout of the loop at hand (a stencil plan keeps no spectrum)
+    int est_spectrum(int f0, int nf) {
+        if (pair) return row_pair(ROW_FWD, nf, nullptr, pair_spec(f0), off(est, (size_t)f0 * n_img()), nullptr, nullptr);
+        if (!sep) return row(ROW_FWD, (unsigned)nf, nullptr, est_spec(f0), off(est, (size_t)f0 * n_img()), nullptr, nullptr);
+        return RL_OK;
     }
     // estimate = 1 (ref:522).  with_spectrum: also spec_a = rowFFT(estimate); the first iteration does not need
     // it when it takes H(1) from spec_ones (iterate_chunk(first = true)).
     int start_estimate_chunk(int f0, int nf, bool with_spectrum = true) {
         HIP_TRY(aux_fill(dtype, off(est, (size_t)f0 * n_img()), (size_t)nf * n_img(), 1.0, cur()));
-        if (with_spectrum && pair)
-            RL_TRY(row_pair(ROW_FWD, nf, nullptr, pair_spec(f0), off(est, (size_t)f0 * n_img()), nullptr, nullptr));
-        else if (with_spectrum && !sep)
-            RL_TRY(row(ROW_FWD, (unsigned)nf, nullptr, off(spec_a, (size_t)f0 * n_spec() * 2), off(est, (size_t)f0 * n_img()),
-                       nullptr, nullptr));
-        return RL_OK;
+        return with_spectrum ? est_spectrum(f0, nf) : RL_OK;
     }
     int ensure_lanes() {
         if (fork) return RL_OK;
-        HIP_TRY(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
+        RL_TRY(handles.event(&fork));
         // (equal priorities: lane 0 at the highest stream priority and lane 1 at the lowest measured 17.2 k against 18.1 k frames/s)
         for (int l = 0; l < opt.lanes; ++l) {
-            HIP_TRY(hipStreamCreateWithFlags(&lane_stream[l], hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&lane_done[l], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&lane_drawn[l], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&lane_begun[l], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&drawn_ahead[l], hipEventDisableTiming));
+            RL_TRY(handles.stream(&lane[l].stream));
+            for (hipEvent_t* e : {&lane[l].done, &lane[l].drawn, &lane[l].begun, &lane[l].drawn_ahead}) RL_TRY(handles.event(e));
         }
-        HIP_TRY(hipEventCreateWithFlags(&rates_ready, hipEventDisableTiming));
-        return RL_OK;
+        return handles.event(&rates_ready);
     }
     // ---- one iteration = four passes (stencil plans: sep_iterate).  Each pass picks its variant from the plan: the pair loop -- the
     // whole iteration in the pair spectra, in place --, one buffer -- one view: every pass maps a spectrum onto itself (a column tile /
@@ -939,9 +938,14 @@ struct rl_deconv {
     // split column pass, whose sums round differently from these whole-pass launches (the last bits of noiseless differ).
     int forward_object() {
         if (sep) return sep_forward(obj, noiseless, sep_tmp(), B);
-        RL_TRY(row(ROW_FWD, (unsigned)B, nullptr, spec_a, obj, nullptr, nullptr));
-        RL_TRY(col(spec_a, spec_b, B, COL_H));
-        return row(ROW_INV, (unsigned)(B * V), spec_b, nullptr, nullptr, noiseless, nullptr);
+        return forward_pass(obj, noiseless, B, spec_a, spec_b, nullptr);
+    }
+    // out [n * V] = H(x [n]) on the FFT path: ROW_FWD into the spectrum space a [n], the column pass a -> b [n * V], ROW_INV.
+    // xs: the parking space [n * V] of the split column pass; nullptr: the whole pass (forward_object: the two differ in the last bits)
+    int forward_pass(const void* x, void* out, int n, void* a, void* b, void* xs) {
+        RL_TRY(row(ROW_FWD, (unsigned)n, nullptr, a, x, nullptr, nullptr));
+        RL_TRY(xs ? col_split_pass(a, b, xs, n, COL_H) : col(a, b, n, COL_H));
+        return row(ROW_INV, (unsigned)(n * V), b, nullptr, nullptr, out, nullptr);
     }
     // noiseless = H(obj) on a slice
     int forward_slice(int f0, int nf) { return forward_frames(f0, nf, off(obj, (size_t)f0 * n_img()), off(noiseless, (size_t)f0 * V * n_img())); }
@@ -952,11 +956,7 @@ struct rl_deconv {
         // (frame pairs: the other lane's slice iterates in spec_a in the pair layout, whose slice boundaries are not
         // this layout's -- the simulation then stays in spec_b, in place)
         void* sa = !pair ? off(spec_a, (size_t)f0 * n_spec() * 2) : sb;
-        RL_TRY(row(ROW_FWD, (unsigned)nf, nullptr, sa, x, nullptr, nullptr));
-        if (col_split()) RL_TRY(col_split_pass(sa, sb, parked(f0), nf, COL_H));   // (the same values as the whole pass)
-        else RL_TRY(col(sa, sb, nf, COL_H));
-        RL_TRY(row(ROW_INV, (unsigned)(nf * V), sb, nullptr, nullptr, out, nullptr));
-        return RL_OK;
+        return forward_pass(x, out, nf, sa, sb, col_split() ? parked(f0) : nullptr);   // (a split plan: the split pass)
     }
     // ---- shared simulation (object_classes.hpp): frames that carry the same object are one class -- the benchmark's batch and a
     // sweep's seeds are one object many times over -- and a simulate + deconvolve cycle computes H(object) ONCE per class that its
@@ -978,36 +978,23 @@ struct rl_deconv {
     void *cls_spec_a = nullptr, *cls_spec_b = nullptr, *cls_spec_x = nullptr;   // [share_cap], [share_cap * V], [share_cap * V] (split plans)
     size_t share_cap = 0;
     int share_classes = 0;                 // compact images in use: the classes the sharing slices of the layout hold
-    // Order between the class simulation and the draws on other lanes (run_slices): the lanes wait for rates_ready before their first
-    // shared draw of a cycle; the simulation of the NEXT cycle waits for lane_drawn[l], recorded behind lane l's last shared draw.
-    hipEvent_t rates_ready = nullptr;
-    hipEvent_t lane_drawn[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr};
-    bool lane_drawn_set[kMaxLanes] = {false, false, false, false};
     int last_sim_images = 0;               // images H was computed for in the last cycle (rl_deconv_simulated_images)
     bool noiseless_sparse = false;         // the last simulation left (some) slices' rates in noiseless_c only
     int last_shared_slices = 0, last_slices = 0;
-    // ---- draws ahead (run_slices): the sharing slices' draws and the class simulation go to the draw stream, which is the
-    // CONTEXT'S stream: it has nothing to do between the fork and the join of the lanes, whatever it holds is in front of the join
-    // by stream order (error paths included), and it has a hardware queue of its own.  A further stream does not: the runtime deals
-    // a process's streams to 4 hardware queues by default, the null stream, the context's and two lanes take them, and a fifth
-    // stream shares a queue with one of the lanes, where its waits stop that lane's launches -- measured, the headline on a stream
-    // of its own: 58.7 ms per cycle against the parent's 47.5 ms in a process with one plan (profiles/draw_ahead).
-    // lane_begun[l]: recorded on lane l in front of a slice's first iteration launch; drawn_ahead[l]: behind the draw of the slice
-    // that lane l takes next.
-    hipStream_t draw_stream() const { return ctx->stream; }
-    hipEvent_t lane_begun[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr}, drawn_ahead[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr};
-    bool lane_begun_set[kMaxLanes] = {false, false, false, false};   // by the cycle before, whose lanes are still open
-    int last_draws_ahead = 0;              // slices of the last cycle whose draw went to the draw stream (rl_deconv_draws_ahead)
+    int last_draws_ahead = 0;              // slices of the last cycle whose draw went to the context's stream (rl_deconv_draws_ahead)
     bool share_possible() const { return opt.share_objects && !sep && (int)obj_class.size() == B && n_classes < B; }
-    // The layout for slices of cf frames from obj_class, its lists on the device -- `staged`: already there (rl_batch_submit puts
-    // them into the chunk's block), otherwise uploaded here -- and the representatives' objects gathered from obj.  On the
-    // context's stream; not while lanes are open.
-    int build_share(int cf, const ShareLists* staged) {
+    // The layout for slices of cf frames from obj_class, on the host: share_slices and the two lists.  Returns the compact images.
+    size_t layout_share(int cf) {
         share_cf = 0;
         noiseless_sparse = false;   // (whatever an earlier layout left is replaced by the simulation that follows)
         share_classes = 0;
         share_layout(obj_class, cf, share_slices, share_reps, share_rate);
-        const size_t total = (size_t)class_layout(obj_class, cf, share_slices, share_reps, share_rate);
+        return (size_t)class_layout(obj_class, cf, share_slices, share_reps, share_rate);
+    }
+    // ... and on the device: its lists -- `staged`: already there (rl_batch_submit puts them into the chunk's block), otherwise
+    // uploaded here -- and the representatives' objects gathered from obj.  On the context's stream; not while lanes are open.
+    int build_share(int cf, const ShareLists* staged) { return place_share(cf, layout_share(cf), staged); }
+    int place_share(int cf, size_t total, const ShareLists* staged) {
         if (total > share_cap) {   // (grow only; in groups of 8 images)
             HIP_TRY(hipDeviceSynchronize());
             share_cap = 0;
@@ -1051,10 +1038,7 @@ struct rl_deconv {
             HIP_TRY(hipStreamSynchronize(ctx->stream));   // (the zeroed slack, before another stream's kernels read past the end)
         }
         void* sa = !pair ? cls_spec_a : sb;   // (as forward_frames does)
-        RL_TRY(row(ROW_FWD, (unsigned)n, nullptr, sa, obj_c, nullptr, nullptr));
-        if (col_split()) RL_TRY(col_split_pass(sa, sb, cls_spec_x, n, COL_H));
-        else RL_TRY(col(sa, sb, n, COL_H));
-        return row(ROW_INV, (unsigned)(n * V), sb, nullptr, nullptr, noiseless_c, nullptr);
+        return forward_pass(obj_c, noiseless_c, n, sa, sb, col_split() ? cls_spec_x : nullptr);
     }
     // the object was (or may have been) replaced: nothing is known about its frames until somebody classifies them
     void forget_classes() {
@@ -1076,16 +1060,19 @@ struct rl_deconv {
         noiseless_sparse = false;
         return RL_OK;
     }
-    int join_open_lanes() {   // after a failed cycle between deferred joins
-        if (!lanes_open) return RL_OK;
-        lanes_open = false;
-        for (int l = 0; l < kMaxLanes; ++l) {
-            if (!lane_stream[l]) continue;
-            HIP_TRY(hipEventRecord(lane_done[l], lane_stream[l]));
-            HIP_TRY(hipStreamWaitEvent(ctx->stream, lane_done[l], 0));
+    // Behind a run that failed: the context's stream continues after every lane, and nothing of that run is left for a later one
+    // to wait for -- it is all in front of whatever the context's stream takes next.  (A draw that the failed cycle enqueued and
+    // no lane waited for is on the context's stream itself.)
+    int join_lanes() {
+        cycle_state = CycleState{};
+        for (const Lane& l : lane) {
+            if (!l.stream) continue;
+            HIP_TRY(hipEventRecord(l.done, l.stream));
+            HIP_TRY(hipStreamWaitEvent(ctx->stream, l.done, 0));
         }
-        return RL_OK;   // (a draw that the failed cycle enqueued and no lane waited for is on the context's stream itself)
+        return RL_OK;
     }
+    int join_open_lanes() { return cycle_state.lanes_open ? join_lanes() : RL_OK; }   // after a failed cycle between deferred joins
     // the Poisson draw of a whole cycle: one seed for the batch, or -- rl_batch_submit -- a Philox key per frame (device arrays of B entries)
     struct Draw { int rng_kind; uint64_t seed; const unsigned long long* key_seeds; const unsigned* key_ids; };
     // ---- iteration checkpoints (rl_batch_submit_checkpoints, checkpoint_kernels.hpp): after the iteration that completes k_list[j] a
@@ -1110,178 +1097,127 @@ struct rl_deconv {
         if (tr) HIP_TRY(checkpoint_totals(dtype, part, n_img(), frames, tr + (size_t)f0 * kCheckpointFields, cur()));
         return RL_OK;
     }
+    // ---- a run over the slices (cycle_schedule.hpp decides what goes to which stream and behind which event; here it is enqueued)
+    struct Run { int k; bool restart; const Draw* draw; const Checkpoints* cp; int cf; };
+    hipStream_t stream_of(int s) const { return s == kCtxStream ? ctx->stream : lane[s].stream; }
+    hipEvent_t event_of(const StreamOp& op) const {
+        const Lane& l = lane[op.lane];
+        switch (op.event) {
+            case EventKind::FORK: return fork;
+            case EventKind::RATES_READY: return rates_ready;
+            case EventKind::DONE: return l.done;
+            case EventKind::DRAWN: return l.drawn;
+            case EventKind::BEGUN: return l.begun;
+            case EventKind::DRAWN_AHEAD: return l.drawn_ahead;
+            case EventKind::NONE: break;
+        }
+        return nullptr;
+    }
+    // A slice's Poisson draw.  shared: every frame draws from its class's rates, which the class simulation left in the compact buffer.
+    // ahead: on the context's stream, opt.draw_grid workgroups wide and without a work list.
+    int draw_slice(const Draw& d, int sl, int f0, int nf, bool shared, bool ahead) {
+        void* ws = ahead ? nullptr : (char*)slice_ws + (size_t)sl * slice_ws_stride;   // this slice's Poisson work list
+        TimedScope t(this, TK_POISSON, false);   // (records on cur())
+        const hipError_t e = aux_poisson(dtype, shared ? noiseless_c : off(noiseless, (size_t)f0 * V * n_img()), off(meas, (size_t)f0 * V * n_img()),
+                                         (unsigned)n_img(), (unsigned)(nf * V), (unsigned)(f0 * V), d.seed, d.rng_kind, ws, cur(),
+                                         d.key_seeds ? d.key_seeds + f0 : nullptr, d.key_ids ? d.key_ids + f0 : nullptr, (unsigned)V,
+                                         shared ? share_lists.rate_of + f0 : nullptr, ahead ? (unsigned)opt.draw_grid : (unsigned)kPoissonGrid);
+        return e == hipSuccess ? RL_OK : fail(RL_ERR_HIP, std::string("Poisson kernels: ") + hipGetErrorString(e));
+    }
+    // (start the estimate of a slice and) its k iterations, with their checkpoints
+    int loop_slice(const Run& r, int f0, int nf) {
+        const int k = r.k;
+        const bool restart = r.restart;
+        const bool shortcut = restart && opt.ones_shortcut && spec_ones && k > 0 && !sep;
+        // The plain loop's first iteration reads neither the estimate's spectrum (shortcut) nor -- est_one -- the estimate, and its
+        // ROW_UPDATE writes every pixel of it: nothing is filled.  The accelerated and the regularised steps read est themselves.
+        const bool ones_first = shortcut && !accel && !tv_on();
+        if (restart && !ones_first) RL_TRY(start_estimate_chunk(f0, nf, !shortcut));
+        // Frame pairs: the last iteration of a run of >= 4 does not transform its estimate forward again (1 of 2 row
+        // transforms of that launch, the spectrum store); an rl_deconv_iterate that continues rebuilds it with one ROW_FWD.
+        const bool drop = pair && k >= 4;
+        int cp_next = 0;   // (est holds x_{i+1} behind every kind of step: the accelerated one ends with its REDUCE, the regularised one with its APPLY)
+        for (int i = 0; i < k; ++i) {
+            if (accel) RL_TRY(accel_step(f0, nf, acc_steps + i, shortcut && i == 0, restart && i == 0));
+            else if (tv_on()) RL_TRY(tv_iterate({f0, nf, shortcut && i == 0, restart && i == 0, /* drop_spectrum */ pair}, i > 0 || tv_sum_valid, true));
+            else RL_TRY(iterate_chunk({f0, nf, shortcut && i == 0, restart && i == 0, drop && i == k - 1, ones_first && i == 0}));
+            if (r.cp && cp_next < r.cp->n_k && r.cp->k_list[cp_next] == i + 1) RL_TRY(take_checkpoint(*r.cp, cp_next++, f0, nf));
+        }
+        return RL_OK;
+    }
+    int enqueue(const StreamOp& op, const Run& r) {
+        const int f0 = op.slice * r.cf, nf = f0 + r.cf <= B ? r.cf : B - f0;
+        active = stream_of(op.stream);   // (what the launch helpers of a WORK use)
+        switch (op.op) {
+            case OpKind::WAIT: HIP_TRY(hipStreamWaitEvent(active, event_of(op), 0)); return RL_OK;
+            case OpKind::RECORD: HIP_TRY(hipEventRecord(event_of(op), active)); return RL_OK;
+            case OpKind::WORK: break;
+        }
+        switch (op.work) {
+            case WorkKind::CLASS_SIM: return forward_classes(share_classes);
+            case WorkKind::SIMULATE_SLICE: return forward_slice(f0, nf);
+            case WorkKind::DRAW_IN_LANE: return draw_slice(*r.draw, op.slice, f0, nf, op.shared, false);
+            case WorkKind::DRAW_AHEAD: return draw_slice(*r.draw, op.slice, f0, nf, op.shared, true);
+            case WorkKind::LOOP: return loop_slice(r, f0, nf);
+            case WorkKind::NONE: break;
+        }
+        return fail(RL_ERR_STATE, "internal: a stream operation without a kind");
+    }
     // (optionally restart from est = 1 and) run k iterations, slice by slice.  draw: one whole simulate + deconvolve cycle -- each
     // slice first computes noiseless = H(obj) and draws its measurement.  cycle_follows: another cycle follows at once (rl_deconv_bench_cycles).
     int run_slices(int k, bool restart, const Draw* draw = nullptr, bool cycle_follows = false, const Checkpoints* cp = nullptr) {
         const int cf = chunk_frames();
-        const int slices = (B + cf - 1) / cf;
-        const int nl = slices < opt.lanes ? slices : opt.lanes;
-        // Lanes stay open between the back-to-back cycles of rl_deconv_bench_cycles (cycle_follows): slice s of every cycle
-        // goes to the same lane, so stream order alone keeps each slice's buffers consistent and the lanes need not meet.
-        const bool keep_open = cycle_follows && nl > 1;
         if (accel && restart) RL_TRY(accel_reset());   // each run from ones (a task of rl_batch_run included) starts a fresh history
         // the slices' representatives (a layout for another slice size is rebuilt; not between cycles whose lanes are still running)
-        if (draw && share_possible() && share_cf != cf && !lanes_open) RL_TRY(build_share(cf, nullptr));
-        const bool share = draw && share_possible() && share_cf == cf;
-        if (nl > 1 && !lanes_open) {
-            RL_TRY(ensure_lanes());
-            HIP_TRY(hipEventRecord(fork, ctx->stream));
-            for (int l = 0; l < nl; ++l) HIP_TRY(hipStreamWaitEvent(lane_stream[l], fork, 0));
-            for (bool& b : lane_begun_set) b = false;   // (nothing of an earlier cycle is still running)
-        }
-        // Draws ahead (RLSTED_DRAW_AHEAD=1; what it measured and why it is off by default: PlanOptions).  The sampler is bound by vector issue, the RL kernels by the memory system, yet a slice's full-width draw at
-        // the head of its lane floods every SIMD and the other lane's loop all but stops beside it.  So the draw of a SHARING slice sl
-        // -- it reads the class rates only -- goes to the draw stream (above), opt.draw_grid workgroups wide, behind the "begun" event of the
-        // slice IN FRONT of sl on its lane: it runs in the background of that slice's loop and is finished long before lane sl % nl
-        // wants it (the lane waits for drawn_ahead).  The begun event is the throttle -- the draw stream is never more than one slice
-        // per lane ahead of the loops -- and what frees `meas` of slice sl: the loop that read it last (the cycle before) precedes
-        // the slice in front on the same lane.  Across cycles whose lanes stay open the slice in front is the lane's last of the
-        // cycle before; a lane that holds ONE slice would draw into the measurement that slice still iterates on, and keeps its
-        // in-lane draw, as do the first slices of a cycle that follows nothing (no loop to hide behind) and slices that do not share.
-        // (Round 1 tried the simulation of all slices ahead of the RL lanes on a stream of its own and lost, 16.5 k against 17.2 k
-        // frames/s: 2.3 GB of per-frame simulation spectra streamed through the Infinity Cache with nothing bounding the run-ahead
-        // pushed the iterating slices' working sets out.  A sharing slice's draw reads one class image and writes its measurement,
-        // 33.5 MB at 512^2, and at most one per lane is ahead.)
-        const bool ahead = opt.draw_ahead && share && share_classes > 0 && nl > 1 && slices > nl;
-        std::vector<char> on_draw_stream((size_t)slices, 0);
-        for (int sl = 0; ahead && sl < slices; ++sl) {
-            const int on_lane = (slices - sl % nl + nl - 1) / nl;   // slices that go to this one's lane
-            on_draw_stream[(size_t)sl] = share_slices[(size_t)sl].nrep > 0 && (sl >= nl || (lane_begun_set[sl] && on_lane >= 2));
-        }
-        int draws_ahead = 0;
+        if (draw && share_possible() && share_cf != cf && !cycle_state.lanes_open) RL_TRY(build_share(cf, nullptr));
+        CycleInputs in;
+        in.B = B; in.cf = cf; in.lanes = opt.lanes; in.V = V;
+        in.draws = draw != nullptr;
+        in.share = share_possible() && share_cf == cf;
+        in.share_classes = share_classes;
+        in.share_slices = share_slices.data();
+        in.draw_ahead = opt.draw_ahead;
+        in.cycle_follows = cycle_follows;
+        in.before = cycle_state;
+        cycle_schedule(in, schedule);
+        if (schedule.forks) RL_TRY(ensure_lanes());
         if (draw) {   // one Poisson work list per slice: slices on different lanes run at the same time
             const size_t stride = (aux_poisson_workspace_bytes((size_t)cf * V * n_img()) + 255) / 256 * 256;
-            if (slice_ws_bytes < stride * slices) {
+            if (slice_ws_bytes < stride * schedule.slices) {
                 HIP_TRY(hipDeviceSynchronize());
                 slice_ws_bytes = 0;
                 RL_TRY(release(&slice_ws));
-                RL_TRY(alloc(&slice_ws, stride * slices));
-                slice_ws_bytes = stride * slices;
+                RL_TRY(alloc(&slice_ws, stride * schedule.slices));
+                slice_ws_bytes = stride * schedule.slices;
             }
             slice_ws_stride = stride;
         }
-        int rc = RL_OK;
         struct ActiveGuard {   // whatever path leaves this function, the launch helpers are back on the context's stream
             hipStream_t& a;
             ~ActiveGuard() { a = nullptr; }
         } active_guard{active};
-        int shared_slices = 0, sim_images = 0;
-        auto hip_rc = [&](hipError_t e, const char* what) -> int {
-            return e == hipSuccess ? RL_OK : fail(RL_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-        };
-        // The cycle's class simulation: H of every class the sharing slices hold, once, on the stream that starts the cycle's first
-        // slice -- or, with draws ahead, on the draw stream: behind the last draw of the cycle before by stream order and beside that
-        // cycle's tail, not behind lane 0's last slice.  It replaces the rates the cycle before drew from, so it first waits for that cycle's last shared draw on every
-        // lane (lanes that stay open between cycles do not meet otherwise); the other lanes wait for it before their first shared draw.
-        bool lane_waits[kMaxLanes] = {false, false, false, false};   // lane l has yet to wait for rates_ready
-        int lane_last_shared[kMaxLanes] = {-1, -1, -1, -1};          // the last sharing slice that goes to lane l
-        if (share && share_classes > 0) {
-            active = ahead ? draw_stream() : nl > 1 ? lane_stream[0] : nullptr;
-            for (int l = 0; l < kMaxLanes && rc == RL_OK; ++l) {
-                if (!lane_drawn_set[l]) continue;
-                lane_drawn_set[l] = false;
-                rc = hip_rc(hipStreamWaitEvent(cur(), lane_drawn[l], 0), "class simulation");
-            }
-            if (rc == RL_OK) rc = forward_classes(share_classes);
-            sim_images += share_classes * V;
-            if (nl > 1 && rc == RL_OK) {
-                rc = hip_rc(hipEventRecord(rates_ready, cur()), "class simulation");
-                for (int l = ahead ? 0 : 1; l < nl; ++l) lane_waits[l] = true;
-                for (int sl = 0; sl < slices; ++sl)   // (in-lane draws; those on the draw stream precede the next simulation there)
-                    if (share_slices[(size_t)sl].nrep > 0 && !on_draw_stream[(size_t)sl]) lane_last_shared[sl % nl] = sl;
-            }
-        }
-        auto simulate_slice = [&](int sl, int f0, int nf) -> int {
-            // a sharing slice: every frame draws from its class's rates, which the class simulation above left in the compact buffer
-            const SliceShare ss = share ? share_slices[(size_t)sl] : SliceShare{};
-            const void* rates = off(noiseless, (size_t)f0 * V * n_img());
-            const int lane = nl > 1 ? sl % nl : 0;
-            if (on_draw_stream[(size_t)sl]) {   // behind the class simulation by stream order: no wait for rates_ready
-                hipStream_t lane_s = cur();
-                active = draw_stream();
-                hipError_t e = hipStreamWaitEvent(draw_stream(), lane_begun[lane], 0);
-                if (e == hipSuccess) {
-                    TimedScope t(this, TK_POISSON, false);   // (records on cur(): the draw stream)
-                    e = aux_poisson(dtype, noiseless_c, off(meas, (size_t)f0 * V * n_img()), (unsigned)n_img(), (unsigned)(nf * V),
-                                    (unsigned)(f0 * V), draw->seed, draw->rng_kind, nullptr, draw_stream(),
-                                    draw->key_seeds ? draw->key_seeds + f0 : nullptr, draw->key_ids ? draw->key_ids + f0 : nullptr,
-                                    (unsigned)V, share_lists.rate_of + f0, (unsigned)opt.draw_grid);
-                }
-                active = lane_s;
-                if (e != hipSuccess) return fail(RL_ERR_HIP, std::string("Poisson kernels: ") + hipGetErrorString(e));
-                HIP_TRY(hipEventRecord(drawn_ahead[lane], draw_stream()));
-                HIP_TRY(hipStreamWaitEvent(lane_s, drawn_ahead[lane], 0));
-                ++shared_slices;
-                ++draws_ahead;
-                return RL_OK;
-            }
-            // (with draws ahead every lane waits once, a slice that does not share too: whatever the context's stream held before the
-            // class simulation -- accel_reset's memset -- then precedes the lane's loops of this cycle as it does when the lanes fork)
-            if ((ss.nrep > 0 || ahead) && lane_waits[lane]) {
-                HIP_TRY(hipStreamWaitEvent(cur(), rates_ready, 0));
-                lane_waits[lane] = false;
-            }
-            if (ss.nrep > 0) {
-                rates = noiseless_c;
-                ++shared_slices;
-            } else {
-                RL_TRY(forward_slice(f0, nf));
-                sim_images += nf * V;
-            }
-            void* ws = (char*)slice_ws + (size_t)sl * slice_ws_stride;   // this slice's Poisson work list
-            TimedScope t(this, TK_POISSON, false);
-            hipError_t e = aux_poisson(dtype, rates, off(meas, (size_t)f0 * V * n_img()),
-                                       (unsigned)n_img(), (unsigned)(nf * V), (unsigned)(f0 * V), draw->seed, draw->rng_kind, ws, cur(),
-                                       draw->key_seeds ? draw->key_seeds + f0 : nullptr, draw->key_ids ? draw->key_ids + f0 : nullptr, (unsigned)V,
-                                       ss.nrep > 0 ? share_lists.rate_of + f0 : nullptr);
-            if (e != hipSuccess) return fail(RL_ERR_HIP, std::string("Poisson kernels: ") + hipGetErrorString(e));
-            if (lane_last_shared[lane] == sl) {   // (several lanes only)
-                HIP_TRY(hipEventRecord(lane_drawn[lane], cur()));
-                lane_drawn_set[lane] = true;
-            }
-            return RL_OK;
-        };
-        for (int sl = 0, f0 = 0; f0 < B && rc == RL_OK; f0 += cf, ++sl) {
-            const int nf = f0 + cf <= B ? cf : B - f0;
-            active = nl > 1 ? lane_stream[sl % nl] : nullptr;
-            if (draw) rc = simulate_slice(sl, f0, nf);
-            if (ahead && rc == RL_OK) {   // the throttle of the draw of the next slice on this lane
-                rc = hip_rc(hipEventRecord(lane_begun[sl % nl], cur()), "draw ahead");
-                lane_begun_set[sl % nl] = rc == RL_OK;
-            }
-            const bool shortcut = restart && opt.ones_shortcut && spec_ones && k > 0 && !sep;
-            // The plain loop's first iteration reads neither the estimate's spectrum (shortcut) nor -- est_one -- the estimate, and its
-            // ROW_UPDATE writes every pixel of it: nothing is filled.  The accelerated and the regularised steps read est themselves.
-            const bool ones_first = shortcut && !accel && !tv_on();
-            if (restart && rc == RL_OK && !ones_first) rc = start_estimate_chunk(f0, nf, !shortcut);
-            // Frame pairs: the last iteration of a run of >= 4 does not transform its estimate forward again (1 of 2 row
-            // transforms of that launch, the spectrum store); an rl_deconv_iterate that continues rebuilds it with one ROW_FWD.
-            const bool drop = pair && k >= 4;
-            int cp_next = 0;   // (est holds x_{i+1} behind every kind of step: the accelerated one ends with its REDUCE, the regularised one with its APPLY)
-            for (int i = 0; i < k && rc == RL_OK; ++i) {
-                if (accel) rc = accel_step(f0, nf, acc_steps + i, shortcut && i == 0, restart && i == 0);
-                else if (tv_on()) rc = tv_iterate({f0, nf, shortcut && i == 0, restart && i == 0, /* drop_spectrum */ pair}, i > 0 || tv_sum_valid, true);
-                else rc = iterate_chunk({f0, nf, shortcut && i == 0, restart && i == 0, drop && i == k - 1, ones_first && i == 0});
-                if (cp && rc == RL_OK && cp_next < cp->n_k && cp->k_list[cp_next] == i + 1) rc = take_checkpoint(*cp, cp_next++, f0, nf);
-            }
+        const Run run{k, restart, draw, cp, cf};
+        int rc = RL_OK;   // the first failure: no further work is enqueued behind it, the join is
+        for (const StreamOp& op : schedule.ops) {
+            if (rc != RL_OK && !op.join) continue;
+            const int r = enqueue(op, run);
+            if (rc == RL_OK) rc = r;
         }
         active = nullptr;
-        if (nl > 1 && (!keep_open || rc != RL_OK)) {   // join, also on errors: the context's stream continues after every lane
-            for (int l = 0; l < nl; ++l) {
-                HIP_TRY(hipEventRecord(lane_done[l], lane_stream[l]));
-                HIP_TRY(hipStreamWaitEvent(ctx->stream, lane_done[l], 0));
-            }
-            lanes_open = false;
-        } else if (nl > 1) {
-            lanes_open = true;
+        if (rc != RL_OK) {
+            const std::string keep = rl::last_error();
+            if (!schedule.joins) (void)join_lanes();   // (lanes that were to stay open)
+            cycle_state = CycleState{};
+            rl::last_error() = keep;
+            return rc;
         }
-        RL_TRY(rc);
+        cycle_state = schedule.after;
         if (draw) {
-            last_draws_ahead = draws_ahead;
-            noiseless_sparse = shared_slices > 0;
-            last_shared_slices = shared_slices;
-            last_slices = slices;
-            last_sim_images = sim_images;
+            last_draws_ahead = schedule.draws_ahead;
+            noiseless_sparse = schedule.shared_slices > 0;
+            last_shared_slices = schedule.shared_slices;
+            last_slices = schedule.slices;
+            last_sim_images = schedule.sim_images;
         }
         if (restart) {
             est_ready = true;
@@ -1387,28 +1323,12 @@ int rl_deconv_destroy(rl_deconv* h) {
     (void)hipSetDevice(h->ctx->device);
     // nothing of this plan may still be running when its buffers go away (slice and copy streams included)
     (void)hipStreamSynchronize(h->ctx->stream);
-    for (hipStream_t s : h->lane_stream)
-        if (s) (void)hipStreamSynchronize(s);
-    if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
+    for (hipStream_t s : h->handles.streams) (void)hipStreamSynchronize(s);
     for (const rl_deconv::Owned& o : h->owned) (void)hipFree(o.p);
-    for (rl_deconv::BatchSlot& sl : h->bslot) {
+    for (rl_deconv::BatchSlot& sl : h->bslot)
         if (sl.host) (void)hipHostFree(sl.host);
-        if (sl.uploaded) (void)hipEventDestroy(sl.uploaded);
-        if (sl.freed) (void)hipEventDestroy(sl.freed);
-    }
-    if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    for (hipEvent_t e : h->event_pool) (void)hipEventDestroy(e);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->fork) (void)hipEventDestroy(h->fork);
-    if (h->rates_ready) (void)hipEventDestroy(h->rates_ready);
-    for (int l = 0; l < kMaxLanes; ++l) {
-        if (h->lane_done[l]) (void)hipEventDestroy(h->lane_done[l]);
-        if (h->lane_drawn[l]) (void)hipEventDestroy(h->lane_drawn[l]);
-        if (h->lane_begun[l]) (void)hipEventDestroy(h->lane_begun[l]);
-        if (h->drawn_ahead[l]) (void)hipEventDestroy(h->drawn_ahead[l]);
-        if (h->lane_stream[l]) (void)hipStreamDestroy(h->lane_stream[l]);
-    }
+    for (hipEvent_t e : h->handles.events) (void)hipEventDestroy(e);
+    for (hipStream_t s : h->handles.streams) (void)hipStreamDestroy(s);
     delete h;
     return RL_OK;
 }
@@ -1478,8 +1398,8 @@ static int deconv_build(rl_deconv* h, const double* psfs) {
     for (const Req& r : reqs) RL_TRY(h->alloc(r.p, r.n, rl_deconv::SLACK));
     RL_TRY(h->alloc(&h->unresolved, sizeof(unsigned long long), rl_deconv::UNCOUNTED));
     HIP_TRY(hipMemsetAsync(h->unresolved, 0, sizeof(unsigned long long), ctx->stream));
-    HIP_TRY(hipEventCreate(&h->ev0));
-    HIP_TRY(hipEventCreate(&h->ev1));
+    RL_TRY(h->handles.event(&h->ev0, hipEventDefault));
+    RL_TRY(h->handles.event(&h->ev1, hipEventDefault));
 
     // A point-symmetric PSF (every PSF of the reference: symmetric "to 1e-15") has a real spectrum.
     // Where the imaginary parts are rounding noise (<= 1e-12 of the largest value; in f32 they vanish against
@@ -1691,11 +1611,9 @@ int rl_deconv_simulate(rl_deconv* h, int rng_kind, uint64_t seed) {
     HIP_TRY(aux_poisson(h->dtype, h->noiseless, h->meas, (unsigned)h->n_img(), (unsigned)(h->B * h->V), 0, seed, rng_kind,
                         h->scratch, h->ctx->stream));
     HIP_TRY(hipStreamSynchronize(h->ctx->stream));
-    h->meas_level = h->obj_level;   // the measurement's level follows the object's
-    h->choose_loop(h->meas_level);
+    h->set_measurement_from_object();
     h->have_meas = true;
     h->meas_external = false;
-    h->meas_negative = false;   // (Poisson draws + 1e-9: an earlier upload's negative pixels are gone)
     h->est_ready = false;
     return RL_OK;
 }
@@ -1716,11 +1634,9 @@ int rl_deconv_simulate_keyed(rl_deconv* h, int rng_kind, const uint64_t* seeds, 
                         h->scratch, h->ctx->stream, (const unsigned long long*)h->key_seeds, (const unsigned*)h->key_ids,
                         (unsigned)h->V));
     HIP_TRY(hipStreamSynchronize(h->ctx->stream));   // the host arrays may go away
-    h->meas_level = h->obj_level;
-    h->choose_loop(h->meas_level);
-    h->meas_external = false;
-    h->meas_negative = false;   // (Poisson draws + 1e-9)
+    h->set_measurement_from_object();
     h->have_meas = true;
+    h->meas_external = false;
     h->est_ready = false;
     return RL_OK;
 }
@@ -1757,11 +1673,7 @@ int rl_deconv_set_estimate(rl_deconv* h, const double* estimate) {
     if (!h || !estimate) return fail(RL_ERR_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(h->ctx->device));
     RL_TRY(h->upload(estimate, h->est, (size_t)h->B * h->n_img()));
-    h->est_ready = true;
-    h->spec_valid = false;   // the next iterate rebuilds rowFFT(estimate)
-    h->tv_sum_valid = false;
-    RL_TRY(h->accel_reset());   // a set estimate is a point with no history
-    return RL_OK;
+    return h->set_estimate();
 }
 
 int rl_deconv_set_acceleration(rl_deconv* h, int mode) {
@@ -1815,13 +1727,9 @@ int rl_deconv_reset_estimate(rl_deconv* h) {
 // rl_deconv_iterate between its events: k iterations on the whole batch, from ones if the plan holds no estimate
 static int iterate_batch(rl_deconv* h, int k) {
     bool restart = !h->est_ready;
-    // (an accelerated or a regularised plan transforms its point inside the loop instead)
-    if (!restart && !h->spec_valid && h->pair && !h->accel && !h->tv_on()) {
-        RL_TRY(h->row_pair(ROW_FWD, h->B, nullptr, h->spec_a, h->est, nullptr, nullptr));
-        h->spec_valid = true;
-    }
-    if (!restart && !h->spec_valid && !h->sep && !h->accel && !h->tv_on()) {   // H / H_t were called in between: rebuild rowFFT(est)
-        RL_TRY(h->row(ROW_FWD, (unsigned)h->B, nullptr, h->spec_a, h->est, nullptr, nullptr));
+    // H / H_t were called in between: rebuild rowFFT(est) (an accelerated or a regularised plan transforms its point inside the loop instead)
+    if (!restart && !h->spec_valid && !h->sep && !h->accel && !h->tv_on()) {
+        RL_TRY(h->est_spectrum(0, h->B));
         h->spec_valid = true;
     }
     return h->run_slices(k, restart);
@@ -1891,10 +1799,7 @@ int rl_deconv_iterate_until(rl_deconv* h, int k_max, int check_every, int rule, 
     }
     // the latched estimates become the plan's estimate, as a set estimate does: a point without history
     HIP_TRY(hipMemcpyAsync(h->est, h->stop_result, (size_t)h->B * h->n_img() * esize(h->dtype), hipMemcpyDeviceToDevice, s));
-    h->est_ready = true;
-    h->spec_valid = false;
-    h->tv_sum_valid = false;
-    RL_TRY(h->accel_reset());
+    RL_TRY(h->set_estimate());
     for (int f = 0; f < h->B; ++f) {
         if (iterations_out) iterations_out[f] = state[f].iterations;
         if (divergence_out) divergence_out[f] = state[f].d_latched;
@@ -1935,9 +1840,7 @@ int rl_forward(rl_deconv* h, const double* x, double* out) {
         RL_TRY(h->sep_forward(xin, res, h->sep_tmp(), h->B));
         return h->download(res, out, (size_t)h->B * h->V * h->n_img());
     }
-    RL_TRY(h->row(ROW_FWD, (unsigned)h->B, nullptr, h->spec_a, xin, nullptr, nullptr));
-    RL_TRY(h->col(h->spec_a, h->spec_b, h->B, rl_deconv::COL_H));
-    RL_TRY(h->row(ROW_INV, (unsigned)(h->B * h->V), h->spec_b, nullptr, nullptr, h->scratch, nullptr));
+    RL_TRY(h->forward_pass(xin, h->scratch, h->B, h->spec_a, h->spec_b, nullptr));
     h->spec_valid = false;
     return h->download(h->scratch, out, (size_t)h->B * h->V * h->n_img());
 }
@@ -1976,9 +1879,7 @@ int rl_deconv_bench_cycles(rl_deconv* h, int k, int reps, int rng_kind, uint64_t
     if (k < 0 || reps < 1) return fail(RL_ERR_INVALID, "bad k / reps");
     HIP_TRY(hipSetDevice(h->ctx->device));
     hipStream_t s = h->ctx->stream;
-    h->meas_level = h->obj_level;   // every cycle draws its measurement from the object
-    h->choose_loop(h->meas_level);
-    h->meas_negative = false;       // (Poisson draws + 1e-9; before the first slice iterates: sub())
+    h->set_measurement_from_object();   // every cycle draws its measurement from the object (before the first slice iterates: sub())
     HIP_TRY(hipEventRecord(h->ev0, s));
     for (int r = 0; r < reps; ++r) {
         // per slice of the batch: noiseless = H(obj), noisy = Poisson(noiseless) + 1e-9, est = 1,
@@ -2108,17 +2009,14 @@ static int batch_submit(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_i
             for (int f = 0; f < B; ++f) level[f] = usum[idx[f]];
         }
         h->obj_level = level;
-        h->meas_level = level;
-        h->choose_loop(h->meas_level);
-        h->meas_negative = false;   // (the chunk draws its own measurement: Poisson draws + 1e-9)
+        h->set_measurement_from_object();   // (the chunk draws its own measurement)
         // tasks that share an object and a target are one class (object_classes.hpp); the lists of the slices' representatives ride in the header
         h->forget_classes();
         if (h->opt.share_objects && !h->sep) h->n_classes = classify_by_index(idx, scaled ? tb : nullptr, B, h->obj_class);
         const bool share = h->share_possible();
         const int cf = h->chunk_frames();
+        const size_t share_total = share ? h->layout_share(cf) : 0;
         if (share) {
-            share_layout(h->obj_class, cf, h->share_slices, h->share_reps, h->share_rate);
-            class_layout(h->obj_class, cf, h->share_slices, h->share_reps, h->share_rate);
             std::copy(h->share_reps.begin(), h->share_reps.end(), lists);
             std::copy(h->share_rate.begin(), h->share_rate.end(), lists + B);
         }
@@ -2136,7 +2034,7 @@ static int batch_submit(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_i
         HIP_TRY(aux_scale_convert_indexed(h->dtype, d_objs, d_idx, uniq.size(), h->obj, n, (size_t)B, scaled ? d_tb : nullptr, d_sums, s));
         if (share) {
             const rl_deconv::ShareLists staged{d_idx + B, d_idx + 2 * B};
-            RL_TRY(h->build_share(cf, &staged));
+            RL_TRY(h->place_share(cf, share_total, &staged));
         }
         h->have_obj = true;
         const rl_deconv::Draw draw{rng_kind, 0, d_seeds, d_ids};
@@ -2312,9 +2210,7 @@ int rl_deconv_time_cycle(rl_deconv* h, int k, int rng_kind, uint64_t seed, doubl
     if (h->sep) return fail(RL_ERR_UNSUPPORTED, "per-kernel timing covers the FFT strategy; this plan runs the separable stencils");
     HIP_TRY(hipSetDevice(h->ctx->device));
     HIP_TRY(hipDeviceSynchronize());
-    h->meas_level = h->obj_level;
-    h->choose_loop(h->meas_level);
-    h->meas_negative = false;
+    h->set_measurement_from_object();
     h->timed.clear();
     h->events_used = 0;
     h->timing = true;
