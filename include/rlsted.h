@@ -672,6 +672,54 @@ int rl_stack_destroy(rl_stack* st);
  * rl_ingest outside a pipeline: deconvolve_tiled with a camera).  Blocking: the host array may go away when it returns. */
 int rl_device_upload_bytes(rl_ctx* ctx, void* dev, const void* host, size_t bytes);
 
+/* ---- registration of views and frames: translation estimates and sub-pixel shifts on the device ----
+ * SIGN CONVENTION: the shift of an image is the displacement d of its content relative to the reference, B[y + d] ~ A[y].  The peak
+ * of the correlation surface of rl_register_sums is at d, and rl_shift_images with that d undoes it.
+ *
+ * rl_register_sums: correlation sums of n_pairs image pairs over a window of integer displacements.  ref_dev / mov_dev: device
+ * buffers of dtype ref_dtype / mov_dtype (RL_F32 / RL_F64, they may differ); pair i is the reference image A at ELEMENT offset
+ * ref_offsets[i] and the moving image B at mov_offsets[i], both [ny][nx] (host arrays [n_pairs]; any offset >= 0, no alignment
+ * assumed; many pairs may share one reference; the buffers may be the same).  R: search radius, 1 .. 32.  M: margin, M >= R, with
+ * ny - 2 M >= 8 and nx - 2 M >= 8.  With the interior I = [M, ny - M) x [M, nx - M), for every d = (dy, dx) in [-R, R]^2:
+ *     S_b(d) = sum_I B[y+dy][x+dx]      S_bb(d) = sum_I B[y+dy][x+dx]^2      S_ab(d) = sum_I A[y][x] B[y+dy][x+dx]
+ * sums_out: host [n_pairs][(2 R + 1)^2][RL_REGISTER_FIELDS] = S_b, S_bb, S_ab at index (dy + R) (2 R + 1) + dx + R;  ref_out: host
+ * [n_pairs][2] = S_a = sum_I A, S_aa = sum_I A^2.  Every sum has (ny - 2 M)(nx - 2 M) terms.
+ * ARITHMETIC: every value is widened exactly to float64; a product enters its sum through one fused multiply-add.  With
+ * W = 2 R + 1, nd = W^2, TY = 16 for R <= 16 and 8 above, G = 1 for nd >= 256 and otherwise the largest power of two with G <= TY
+ * and G nd <= 256, h = TY / G: the interior's rows are cut into strips of h rows from y = M on, ceil((ny - 2 M) / TY) G of them (the
+ * last may be short or empty), its columns into blocks of 32 from x = M on.  A strip's sum for one d starts at 0.0 and takes the
+ * column blocks in increasing order, inside a block the strip's rows in increasing order, inside a row the columns in increasing
+ * order, per pixel S_b = S_b + b; S_bb = fma(b, b, S_bb); S_ab = fma(a, b, S_ab).  A pair's sum is (((0.0 + strip_0) + strip_1) +
+ * ...) over the strips in increasing order.  S_a and S_aa: per image row from 0.0 over the interior's columns in increasing order
+ * (S_a + a; fma(a, a, S_aa)), then (((0.0 + row_M) + row_{M+1}) + ...), followed by + 0.0 for the rows that complete the last TY.
+ * No floating-point atomics: bit-identical from run to run, and a pair's result does not depend on the other pairs of the call.
+ * Nothing outside an image is read.  Pairs are processed in chunks whose partial sums stay under a fixed cap; the workspace is kept
+ * in the context and freed with it.  Synchronises the context's stream.
+ * RL_ERR_INVALID (no kernel is launched): a NULL argument, a dtype that is neither, n_pairs < 1, R outside 1 .. 32, M < R, an
+ * interior smaller than 8 x 8, a negative offset.
+ *
+ * rl_shift_images: src_dev [n][ny][nx] of src_dtype -> dst_dev [n][ny][nx] of dst_dtype (RL_F32 / RL_F64 each; no overlap):
+ *     dst[i] = max(scipy.ndimage.shift(src[i], (-sy_i, -sx_i), order = order, mode = 'mirror'), floor)
+ * with shifts: host [n][2] = (sy, sx): dst[i][y][x] samples the spline of image i at (y + sy, x + sx), whole-sample mirror
+ * boundaries in the prefilter and in the evaluation; any finite |shift| <= 1e9.  order: 1 or 3.  floor: any double but nan
+ * (-infinity: none).  Computed in float64 with one rounding to the destination type.  Along an axis, prefilter and evaluation of a
+ * translation are one finite impulse response on the mirror extension: order 1 the taps (1 - t, t), an integer shift the tap 1.0
+ * alone -- a bit-exact copy of the displaced pixels; order 3 the 64 taps of csrc/register_kernels.hpp, the prefilter's impulse
+ * response sqrt(3) z^|k| (z = sqrt(3) - 2) cut at |k| = 30, where the dropped tail is at most 8.8e-18 max|src| per axis.  The taps
+ * are formed on the host in long double; a pixel is g_0 v_0, then fma(g_m, v_m, .) for m = 1, 2, ...; x first, then y.
+ * stats_out: NULL, or host [n][RL_SHIFT_FIELDS] = the count of pixels raised to `floor`, the float64 sum of the stored image in
+ * the fixed order of csrc/register_kernels.hpp (thread, binary tree over 256 threads, workgroups in increasing order; no atomics).
+ * Writes exactly n * ny * nx values.  Images are processed in chunks whose float64 intermediate stays under a fixed cap, in the
+ * context's workspace.  Synchronises the context's stream.
+ * RL_ERR_INVALID (no kernel is launched): a NULL ctx / source / shifts / destination, a dtype that is neither, n, ny or nx < 1, an
+ * order that is neither, floor nan, a shift that is not finite or beyond 1e9, a destination that overlaps the source. */
+#define RL_REGISTER_FIELDS 3
+#define RL_SHIFT_FIELDS 2
+int rl_register_sums(rl_ctx* ctx, const void* ref_dev, int ref_dtype, const int64_t* ref_offsets, const void* mov_dev, int mov_dtype,
+                     const int64_t* mov_offsets, int n_pairs, int ny, int nx, int R, int M, double* sums_out, double* ref_out);
+int rl_shift_images(rl_ctx* ctx, const void* src_dev, int src_dtype, int n, int ny, int nx, const double* shifts, int order,
+                    double floor, void* dst_dev, int dst_dtype, double* stats_out);
+
 /* ---- line_sted_figure_3.py: the scan-position-by-scan-position imaging simulator (:76-273) ----
  * rl_rotate_image: `rotate` (:382-391) for one [ny][nx] plane -- scipy.ndimage.rotate(order 3,
  * mode 'nearest', reshape=False) about the centre; clip != 0 clips to [0, 1.1 * max(in)].  Host in / out. */

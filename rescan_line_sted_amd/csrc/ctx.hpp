@@ -100,6 +100,9 @@ struct rl_ctx {
     // rl_ingest, rl_export (stack_api.cpp): a grow-only workspace for the per-workgroup partials of a call's statistics; freed with
     // the context
     EnsembleWork ingest;
+    // rl_register_sums, rl_shift_images (register_api.cpp): a grow-only workspace for a call's offsets, taps, partials, totals
+    // and the shift's float64 intermediate; freed with the context
+    EnsembleWork reg;
 
     int device = 0;
     hipStream_t stream = nullptr;

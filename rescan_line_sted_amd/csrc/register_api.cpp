@@ -1,0 +1,128 @@
+// register_api.cpp -- C ABI of the registration primitives (include/rlsted.h: rl_register_sums, rl_shift_images): validation, the
+// shift's taps (formed on the host in long double, register_kernels.hpp shift_taps), the chunking under the workspace caps and the
+// launches of register_kernels.hip.  Only offsets and taps go up and the sums and statistics come down.  No kernel is launched on
+// bad arguments.
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "ctx.hpp"
+#include "register_kernels.hpp"
+
+using namespace rl;
+
+namespace {
+constexpr size_t kRegSumWorkBytes = (size_t)256 << 20;     // the partials of the pairs in flight; a larger single pair runs alone
+constexpr size_t kShiftWorkBytes = (size_t)512 << 20;      // the float64 intermediates of the images in flight
+
+size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+bool float_dtype_ok(int d) { return d == RL_F32 || d == RL_F64; }
+size_t float_size(int d) { return d == RL_F32 ? sizeof(float) : sizeof(double); }
+bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    return (const char*)a < (const char*)b + b_bytes && (const char*)b < (const char*)a + a_bytes;
+}
+
+int reg_workspace(rl_ctx* ctx, size_t bytes, char** out) {
+    if (bytes > ctx->reg.work_bytes) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (ctx->reg.work) (void)hipFree(ctx->reg.work);
+        ctx->reg.work = nullptr;
+        ctx->reg.work_bytes = 0;
+        HIP_TRY(hipMalloc(&ctx->reg.work, bytes));
+        ctx->reg.work_bytes = bytes;
+    }
+    *out = (char*)ctx->reg.work;
+    return RL_OK;
+}
+}  // namespace
+
+extern "C" int rl_register_sums(rl_ctx* ctx, const void* ref_dev, int ref_dtype, const int64_t* ref_offsets, const void* mov_dev,
+                                int mov_dtype, const int64_t* mov_offsets, int n_pairs, int ny, int nx, int R, int M, double* sums_out,
+                                double* ref_out) {
+    if (!ctx || !ref_dev || !ref_offsets || !mov_dev || !mov_offsets || !sums_out || !ref_out) return fail(RL_ERR_INVALID, "NULL argument");
+    if (!float_dtype_ok(ref_dtype) || !float_dtype_ok(mov_dtype)) return fail(RL_ERR_INVALID, "dtypes must be RL_F32 or RL_F64");
+    if (n_pairs < 1) return fail(RL_ERR_INVALID, "n_pairs must be at least 1");
+    if (R < 1 || R > kRegMaxR) return fail(RL_ERR_INVALID, "the search radius must lie in 1 .. 32");
+    if (M < R) return fail(RL_ERR_INVALID, "the margin must be at least the search radius");
+    if (ny < 1 || nx < 1 || (long long)ny - 2LL * M < 8 || (long long)nx - 2LL * M < 8)
+        return fail(RL_ERR_INVALID, "the interior must be at least 8 x 8 pixels: ny - 2 M >= 8 and nx - 2 M >= 8");
+    for (int i = 0; i < n_pairs; ++i)
+        if (ref_offsets[i] < 0 || mov_offsets[i] < 0) return fail(RL_ERR_INVALID, "pair " + std::to_string(i) + ": negative offset");
+    static_assert(kRegFields == RL_REGISTER_FIELDS && kShiftFields == RL_SHIFT_FIELDS, "the header's field counts");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const RegGeom g = reg_geom(ny, nx, R, M);
+    const size_t per_tot = (size_t)g.nd * kRegFields + 2, per_part = reg_part_doubles(g);
+    const size_t chunk = std::min<size_t>((size_t)n_pairs, std::max<size_t>(1, kRegSumWorkBytes / (per_part * sizeof(double))));
+    const size_t off_bytes = round_up((size_t)n_pairs * sizeof(long long), 256);
+    const size_t tot_bytes = round_up(chunk * per_tot * sizeof(double), 256);
+    char* w = nullptr;
+    RL_TRY(reg_workspace(ctx, 2 * off_bytes + tot_bytes + chunk * per_part * sizeof(double), &w));
+    long long* a_off = (long long*)w;
+    long long* b_off = (long long*)(w + off_bytes);
+    double* tot = (double*)(w + 2 * off_bytes);
+    double* part = (double*)(w + 2 * off_bytes + tot_bytes);
+    static_assert(sizeof(long long) == sizeof(int64_t), "offsets are copied as they are");
+    HIP_TRY(hipMemcpyAsync(a_off, ref_offsets, (size_t)n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(b_off, mov_offsets, (size_t)n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    std::vector<double> host(chunk * per_tot);
+    for (size_t first = 0; first < (size_t)n_pairs; first += chunk) {
+        const size_t n = std::min(chunk, (size_t)n_pairs - first);
+        RegSumArgs a;
+        a.a = ref_dev; a.b = mov_dev; a.a_off = a_off + first; a.b_off = b_off + first; a.part = part; a.tot = tot; a.pairs = (int)n; a.g = g;
+        HIP_TRY(register_sums(ref_dtype, mov_dtype, a, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(host.data(), tot, n * per_tot * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (size_t i = 0; i < n; ++i) {
+            const double* t = host.data() + i * per_tot;
+            std::copy(t, t + (size_t)g.nd * kRegFields, sums_out + (first + i) * g.nd * kRegFields);
+            ref_out[(first + i) * 2] = t[(size_t)g.nd * kRegFields];
+            ref_out[(first + i) * 2 + 1] = t[(size_t)g.nd * kRegFields + 1];
+        }
+    }
+    return RL_OK;
+}
+
+extern "C" int rl_shift_images(rl_ctx* ctx, const void* src_dev, int src_dtype, int n, int ny, int nx, const double* shifts, int order,
+                               double floor, void* dst_dev, int dst_dtype, double* stats_out) {
+    if (!ctx || !src_dev || !shifts || !dst_dev) return fail(RL_ERR_INVALID, "NULL argument");
+    if (!float_dtype_ok(src_dtype) || !float_dtype_ok(dst_dtype)) return fail(RL_ERR_INVALID, "dtypes must be RL_F32 or RL_F64");
+    if (n < 1 || ny < 1 || nx < 1) return fail(RL_ERR_INVALID, "n, ny and nx must be at least 1");
+    if (order != 1 && order != 3) return fail(RL_ERR_INVALID, "order must be 1 or 3");
+    if (std::isnan(floor)) return fail(RL_ERR_INVALID, "floor is nan");
+    for (size_t i = 0; i < 2 * (size_t)n; ++i)
+        if (!(std::fabs(shifts[i]) <= 1e9)) return fail(RL_ERR_INVALID, "image " + std::to_string(i / 2) + ": the shift must be finite, at most 1e9 pixels");
+    const size_t n_pix = (size_t)ny * nx;
+    if (overlaps(src_dev, (size_t)n * n_pix * float_size(src_dtype), dst_dev, (size_t)n * n_pix * float_size(dst_dtype)))
+        return fail(RL_ERR_INVALID, "the destination overlaps the source");
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<ShiftImage> table((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        shift_taps(shifts[2 * (size_t)i], order, ny, table[i].gy, &table[i].oy, &table[i].nty);
+        shift_taps(shifts[2 * (size_t)i + 1], order, nx, table[i].gx, &table[i].ox, &table[i].ntx);
+    }
+    const int nb = shift_blocks_y(ny) * shift_blocks_x(nx);
+    const size_t chunk = std::min<size_t>((size_t)n, std::max<size_t>(1, kShiftWorkBytes / (n_pix * sizeof(double))));
+    const size_t table_bytes = round_up((size_t)n * sizeof(ShiftImage), 256), stats_bytes = round_up((size_t)n * kShiftFields * sizeof(double), 256);
+    const size_t part_bytes = round_up(chunk * nb * kShiftFields * sizeof(double), 256);
+    char* w = nullptr;
+    RL_TRY(reg_workspace(ctx, table_bytes + stats_bytes + part_bytes + chunk * n_pix * sizeof(double), &w));
+    ShiftImage* table_dev = (ShiftImage*)w;
+    double* stats = (double*)(w + table_bytes);
+    double* part = (double*)(w + table_bytes + stats_bytes);
+    double* tmp = (double*)(w + table_bytes + stats_bytes + part_bytes);
+    HIP_TRY(hipMemcpyAsync(table_dev, table.data(), (size_t)n * sizeof(ShiftImage), hipMemcpyHostToDevice, ctx->stream));
+    for (size_t first = 0; first < (size_t)n; first += chunk) {
+        ShiftArgs a;
+        a.src = (const char*)src_dev + first * n_pix * float_size(src_dtype);
+        a.dst = (char*)dst_dev + first * n_pix * float_size(dst_dtype);
+        a.img = table_dev + first;
+        a.part = stats_out ? part : nullptr;
+        a.n = (int)std::min(chunk, (size_t)n - first);
+        a.ny = ny; a.nx = nx; a.floor = floor;
+        HIP_TRY(shift_images(src_dtype, dst_dtype, a, tmp, stats_out ? stats + first * kShiftFields : nullptr, ctx->stream));
+    }
+    if (stats_out) HIP_TRY(hipMemcpyAsync(stats_out, stats, (size_t)n * kShiftFields * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));   // (the taps' table is the call's own)
+    return RL_OK;
+}

@@ -39,6 +39,11 @@ overlapping tiles of one plan and blends the tile estimates on the device
 Acquired stacks: `deconvolve_stack` (stack.py) takes uint8 / uint16 / int16 /
 float32 camera frames as they are, forms the measurement on the device and
 overlaps the transfers with the iterations.
+
+Drift: `deconvolve_stack_registered` (registration.py) estimates the translation
+of every view and frame of such a stack on the device and undoes it before the
+iterations; `estimate_shifts` and `shift_images` are its two steps on their own
+(INTEGRATION.md section 5i).
 """
 import os
 import time
@@ -49,6 +54,7 @@ from . import _lib
 from ._lib import DeconvPlan, RNG_NONE, RNG_PHILOX
 from .tiling import deconvolve_tiled   # noqa: F401  (re-exported)
 from .stack import CameraModel, deconvolve_stack   # noqa: F401  (re-exported)
+from .registration import deconvolve_stack_registered, estimate_shifts, shift_images   # noqa: F401  (re-exported)
 
 _DEFAULT_DTYPE = os.environ.get('RLSTED_DTYPE', 'f64')
 _DEFAULT_DEVICE = _lib.DEFAULT_DEVICE

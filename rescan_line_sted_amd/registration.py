@@ -1,0 +1,391 @@
+"""Registration of the views and frames of acquired stacks on the device, in front of Richardson-Lucy (INTEGRATION.md section 5i,
+DESIGN.md section 4k).
+
+The V views of a frame are recorded one after the other and a time series runs for minutes: the sample drifts between exposures.
+Multi-view Richardson-Lucy multiplies the back-projections of all views, so a view that is off by a pixel or two is not averaged
+away.  estimate_shifts finds translations from normalised cross-correlation over a window of integer displacements plus a parabola
+(include/rlsted.h rl_register_sums), shift_images undoes them with the scipy-compatible B-spline (rl_shift_images), and
+deconvolve_stack_registered puts both between the narrow ingest of deconvolve_stack and the plan -- the data never leaves the device.
+
+SIGN CONVENTION, used everywhere: the shift of an image is the displacement d of its content relative to the reference,
+image[y + d] ~ reference[y].  The correlation surface peaks at d, and shift_images(image, d) undoes it.
+
+    estimates, info = deconvolve_stack_registered(raw, psfs, iterations, camera=CameraModel(dark=100.0, gain=0.46))
+"""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from ._lib import DTYPES, check, lib
+from .stack import INGEST_FIELDS, ORDERS, CameraModel, _stack_shape, raw_code
+
+MAX_RADIUS = 32                       # rl_register_sums
+_NP = {'f32': np.float32, 'f64': np.float64}
+_I64P = ctypes.POINTER(ctypes.c_int64)
+
+
+# ---- host logic: NCC, peak, parabola -----------------------------------------------------------------------------------------------
+def ncc_surface(sums, ref, n):
+    """NCC(d) = (S_ab - S_a S_b / n) / sqrt((S_aa - S_a^2 / n)(S_bb - S_b^2 / n)) in float64 from one pair's sums [W * W][3] and
+    (S_a, S_aa); returns (surface [W][W], flat) -- flat: a variance that is not positive, the surface is then zeros."""
+    sums = np.asarray(sums, dtype=np.float64)
+    W = int(round(np.sqrt(sums.shape[0])))
+    sa, saa = float(ref[0]), float(ref[1])
+    va = saa - sa * sa / n
+    vb = sums[:, 1] - sums[:, 0] * sums[:, 0] / n
+    if not va > 0.0 or not np.all(vb > 0.0):
+        return np.zeros((W, W)), True
+    return ((sums[:, 2] - sa * sums[:, 0] / n) / np.sqrt(va * vb)).reshape(W, W), False
+
+
+def surface_peak(c):
+    """(shift [2] = integer peak + parabola, peak value, at_limit) of a surface [W][W]: the first maximum in row-major order; a
+    separable three-point parabola per axis, delta = (c- - c+) / (2 (c- - 2 c0 + c+)); a peak on the window's border: delta = 0."""
+    W = c.shape[0]
+    R = W // 2
+    iy, ix = divmod(int(np.argmax(c)), W)
+    if iy in (0, W - 1) or ix in (0, W - 1):
+        return np.array([iy - R, ix - R], dtype=np.float64), float(c[iy, ix]), True
+    delta = []
+    for m, z, p in ((c[iy - 1, ix], c[iy, ix], c[iy + 1, ix]), (c[iy, ix - 1], c[iy, ix], c[iy, ix + 1])):
+        den = m - 2.0 * z + p
+        delta.append(0.5 * (m - p) / den if den != 0.0 else 0.0)
+    return np.array([iy - R + delta[0], ix - R + delta[1]]), float(c[iy, ix]), False
+
+
+def _check_search(ny, nx, max_shift, refine, margin):
+    max_shift, refine = int(max_shift), int(refine)
+    if not 1 <= max_shift <= MAX_RADIUS:
+        raise ValueError('max_shift must lie in 1 .. %d; got %r' % (MAX_RADIUS, max_shift))
+    if refine < 0:
+        raise ValueError('refine must be at least 0')
+    margin = max_shift + 2 if margin is None else int(margin)
+    if margin < max_shift + (2 if refine else 0):
+        raise ValueError('margin must be at least max_shift%s; got %d' % (' + 2 (mirrored border content stays outside the sums)' if refine else '', margin))
+    if ny - 2 * margin < 8 or nx - 2 * margin < 8:
+        raise ValueError('a %d x %d image leaves no 8 x 8 interior inside a margin of %d' % (ny, nx, margin))
+    return max_shift, refine, margin
+
+
+def _estimate(dev, ref, ref_offsets, mov, mov_offsets, ny, nx, max_shift, refine, margin, scratch, surfaces=False):
+    """Stages 1 - 5 for the pairs (ref at ref_offsets[i], mov at mov_offsets[i]) through dev.sums / dev.shift; scratch: a float64
+    buffer of len(pairs) images (refine > 0).  Returns (shifts (N, 2), info)."""
+    N = len(mov_offsets)
+    n = (ny - 2 * margin) * (nx - 2 * margin)
+    shifts, value = np.zeros((N, 2)), np.zeros(N)
+    at_limit, flat = np.zeros(N, dtype=bool), np.zeros(N, dtype=bool)
+    S, A = dev.sums(ref, ref_offsets, mov, mov_offsets, ny, nx, max_shift, margin)
+    kept = []
+    for i in range(N):
+        c, flat[i] = ncc_surface(S[i], A[i], n)
+        if surfaces:
+            kept.append(c)
+        if not flat[i]:
+            shifts[i], value[i], at_limit[i] = surface_peak(c)
+    for _ in range(refine):
+        live = np.flatnonzero(~flat)
+        if live.size == 0:
+            break
+        # every moving image by its current estimate into the scratch buffer (order 3, no floor), then a 3 x 3 window
+        dev.gather_shift(mov, [mov_offsets[i] for i in live], ny, nx, shifts[live], scratch)
+        S, A = dev.sums(ref, [ref_offsets[i] for i in live], scratch, [k * ny * nx for k in range(live.size)], ny, nx, 1, margin)
+        for k, i in enumerate(live):
+            c, f = ncc_surface(S[k], A[k], n)
+            if not f:
+                d, value[i], _ = surface_peak(c)
+                shifts[i] += d
+    info = {'ncc': value, 'at_limit': at_limit, 'flat': flat}
+    if surfaces:
+        info['surfaces'] = np.stack(kept)
+    return shifts, info
+
+
+# ---- the device ----------------------------------------------------------------------------------------------------------------------
+class _Buffer:
+    """A device allocation of `elements` values of dtype 'f32' / 'f64' (or raw bytes: dtype None)."""
+
+    def __init__(self, ptr, elements, dtype):
+        self.ptr, self.elements, self.dtype = ptr, elements, dtype
+
+    def at(self, element):
+        return ctypes.c_void_p(self.ptr.value + element * np.dtype(_NP[self.dtype]).itemsize)
+
+
+class _Device:
+    """What the registration does on the GPU, one method per step (the CPU tests drive the wrappers with a numpy stand-in).  A plan
+    is made only when PSFs are given."""
+
+    def __init__(self, psfs=None, batch=0, shape=None, dtype='f32', device=0, acceleration=None, tv_lambda=None, tv_epsilon=0.1):
+        self.plan = None
+        if psfs is not None:
+            self.plan = _lib.DeconvPlan(psfs, batch, shape[0], shape[1], dtype=dtype, device=device, acceleration=acceleration,
+                                        tv_lambda=tv_lambda, tv_epsilon=tv_epsilon)
+            self.ctx = self.plan.ctx
+        else:
+            self.ctx = _lib.Context.get(device, 0)
+        self.owned = []
+
+    def alloc(self, elements, dtype):
+        p = ctypes.c_void_p()
+        size = 1 if dtype is None else np.dtype(_NP[dtype]).itemsize
+        check(lib.rl_device_alloc(self.ctx.handle, max(int(elements) * size, 1), ctypes.byref(p)))
+        self.owned.append(p)
+        return _Buffer(p, int(elements), dtype)
+
+    def upload(self, buf, array, byte_offset=0):
+        """A host array's bytes as they are (rl_device_upload_bytes)."""
+        array = np.ascontiguousarray(array)
+        check(lib.rl_device_upload_bytes(self.ctx.handle, ctypes.c_void_p(buf.ptr.value + byte_offset), array.ctypes.data_as(ctypes.c_void_p),
+                                         array.nbytes))
+
+    def download(self, buf, elements, element_offset=0):
+        out = np.empty(int(elements), dtype=np.float64)
+        check(lib.rl_device_download(self.ctx.handle, buf.at(element_offset), DTYPES[buf.dtype], int(elements), _lib.ptr(out)))
+        return out
+
+    def copy(self, dst, dst_element, src, src_element, elements):
+        assert dst.dtype == src.dtype
+        check(lib.rl_device_copy(self.ctx.handle, dst.at(dst_element), src.at(src_element), int(elements) * np.dtype(_NP[src.dtype]).itemsize))
+
+    def measurement(self):
+        """The plan's measurement buffer [batch][V][ny][nx] (rl_deconv_device_ptr which = 1)."""
+        p, n, dt = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_int()
+        check(lib.rl_deconv_device_ptr(self.plan.handle, 1, ctypes.byref(p), ctypes.byref(n), ctypes.byref(dt)))
+        return _Buffer(p, self.plan.B * self.plan.V * self.plan.ny * self.plan.nx, 'f32' if dt.value == _lib.RL_F32 else 'f64')
+
+    def ingest(self, raw, code, images, sensor, origin, frame_stride, view_stride, n_slots, n_valid, V, shape, camera, dark, dst, stats):
+        """rl_ingest of a chunk's raw frames into dst (the staging buffer, not the plan's); stats: a float64 buffer [n_slots * V][4]."""
+        check(lib.rl_ingest(self.ctx.handle, raw.ptr, code, images, sensor[0], sensor[1], origin[0], origin[1], frame_stride, view_stride, n_slots,
+                            n_valid, V, shape[0], shape[1], None if dark is None else dark.ptr, camera.dark, camera.gain, camera.epsilon,
+                            0.0 if camera.saturation is None else camera.saturation, dst.ptr, DTYPES[dst.dtype], stats.ptr))
+
+    def sums(self, ref, ref_offsets, mov, mov_offsets, ny, nx, R, M):
+        """rl_register_sums: (S [pairs][(2R+1)^2][3], A [pairs][2])."""
+        n = len(mov_offsets)
+        W = 2 * R + 1
+        ro, mo = np.ascontiguousarray(ref_offsets, dtype=np.int64), np.ascontiguousarray(mov_offsets, dtype=np.int64)
+        S, A = np.empty((n, W * W, 3)), np.empty((n, 2))
+        check(lib.rl_register_sums(self.ctx.handle, ref.ptr, DTYPES[ref.dtype], ro.ctypes.data_as(_I64P), mov.ptr, DTYPES[mov.dtype],
+                                   mo.ctypes.data_as(_I64P), n, ny, nx, R, M, _lib.ptr(S), _lib.ptr(A)))
+        return S, A
+
+    def shift(self, src, src_element, n, ny, nx, shifts, order, floor, dst, dst_element=0):
+        """rl_shift_images on n consecutive images; returns the statistics [n][2] (raised, sum)."""
+        sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(n, 2)
+        stats = np.empty((n, 2))
+        check(lib.rl_shift_images(self.ctx.handle, src.at(src_element), DTYPES[src.dtype], n, ny, nx, _lib.ptr(sh), order,
+                                  -np.inf if floor is None else float(floor), dst.at(dst_element), DTYPES[dst.dtype], _lib.ptr(stats)))
+        return stats
+
+    def gather_shift(self, src, offsets, ny, nx, shifts, dst):
+        """The images at the element offsets of src, each by its shift (order 3, no floor), to consecutive images of dst; runs of
+        consecutive images go through one call."""
+        offsets, k = list(offsets), 0
+        while k < len(offsets):
+            m = 1
+            while k + m < len(offsets) and offsets[k + m] == offsets[k] + m * ny * nx:
+                m += 1
+            self.shift(src, offsets[k], m, ny, nx, shifts[k:k + m], 3, None, dst, k * ny * nx)
+            k += m
+
+    def iterate(self, iterations):
+        """The measurement buffer was written on the device: from ones, `iterations` iterations; returns the estimates (B, ny, nx)."""
+        check(lib.rl_deconv_measurement_written(self.plan.handle))
+        check(lib.rl_deconv_reset_estimate(self.plan.handle))
+        check(lib.rl_deconv_iterate(self.plan.handle, int(iterations)))
+        return self.plan.estimate()
+
+    def unresolved(self):
+        return self.plan.unresolved()
+
+    def strategy(self):
+        return self.plan.strategy()
+
+    def close(self):
+        for p in self.owned:
+            lib.rl_device_free(self.ctx.handle, p)
+        self.owned = []
+
+
+def _float_images(a, name):
+    a = np.asarray(a)
+    if a.dtype not in (np.float32, np.float64):
+        raise ValueError('%s must be float32 or float64 (taken without conversion); got %s' % (name, a.dtype))
+    return np.ascontiguousarray(a), ('f32' if a.dtype == np.float32 else 'f64')
+
+
+# ---- public ----------------------------------------------------------------------------------------------------------------------------
+def estimate_shifts(images, reference, max_shift=8, refine=1, margin=None, device=None, surfaces=False):
+    """The translation of every image relative to its reference.  images: (N, ny, nx) or (ny, nx), float32 or float64; reference:
+    (ny, nx), shared, or (N, ny, nx).  max_shift: the search radius in pixels, 1 .. 32.  refine: passes that shift the image by
+    the current estimate (order 3) and add the parabola offset of a 3 x 3 window.  margin: pixels at every border kept out of the
+    sums (default, and at least with refine > 0, max_shift + 2).  Returns (shifts (N, 2) float64 (dy, dx), info) with info['ncc']
+    (the peak value), 'at_limit' (the integer peak lay on the window's border: no sub-pixel part, the drift may be larger), 'flat' (an
+    image without variance: shift 0) and, with surfaces=True, 'surfaces' (N, W, W)."""
+    images, dt = _float_images(images, 'images')
+    reference, rdt = _float_images(reference, 'reference')
+    if images.ndim == 2:
+        images = images[None]
+    if images.ndim != 3 or 0 in images.shape:
+        raise ValueError('images: expected (N, ny, nx) or (ny, nx); got shape %s' % (images.shape,))
+    N, ny, nx = images.shape
+    if reference.shape not in ((ny, nx), (N, ny, nx)):
+        raise ValueError('reference: expected %s or %s; got shape %s' % ((ny, nx), (N, ny, nx), reference.shape))
+    max_shift, refine, margin = _check_search(ny, nx, max_shift, refine, margin)
+    dev = _Device(device=_lib.DEFAULT_DEVICE if device is None else device)
+    try:
+        mov, ref = dev.alloc(images.size, dt), dev.alloc(reference.size, rdt)
+        dev.upload(mov, images)
+        dev.upload(ref, reference)
+        scratch = dev.alloc(images.size, 'f64') if refine else None
+        n_pix = ny * nx
+        return _estimate(dev, ref, [i * n_pix if reference.ndim == 3 else 0 for i in range(N)], mov, [i * n_pix for i in range(N)], ny, nx,
+                         max_shift, refine, margin, scratch, surfaces)
+    finally:
+        dev.close()
+
+
+def shift_images(images, shifts, order=3, floor=None, device=None):
+    """max(scipy.ndimage.shift(images[i], -shifts[i], order=order, mode='mirror'), floor) for every image, on the device: image i
+    sampled at (y + sy_i, x + sx_i) -- shifts as estimate_shifts returns them undo the displacement.  images: (N, ny, nx) or (ny, nx),
+    float32 or float64; the result has the same dtype (computed in float64, rounded once).  order: 3 (cubic B-spline) or 1 (bilinear;
+    with integer shifts a bit-exact copy of the displaced pixels).  floor: None or the least value of the output."""
+    images, dt = _float_images(images, 'images')
+    single = images.ndim == 2
+    if single:
+        images = images[None]
+    if images.ndim != 3 or 0 in images.shape:
+        raise ValueError('images: expected (N, ny, nx) or (ny, nx); got shape %s' % (images.shape,))
+    N, ny, nx = images.shape
+    shifts = np.asarray(shifts, dtype=np.float64)
+    if shifts.shape != ((2,) if single else (N, 2)) and shifts.shape != (N, 2):
+        raise ValueError('shifts: expected shape %s; got %s' % ((N, 2), shifts.shape))
+    if not np.all(np.isfinite(shifts)):
+        raise ValueError('shifts must be finite')
+    if order not in (1, 3):
+        raise ValueError('order must be 1 or 3; got %r' % (order,))
+    dev = _Device(device=_lib.DEFAULT_DEVICE if device is None else device)
+    try:
+        src, dst = dev.alloc(images.size, dt), dev.alloc(images.size, dt)
+        dev.upload(src, images)
+        dev.shift(src, 0, N, ny, nx, shifts.reshape(N, 2), order, floor, dst)
+        out = dev.download(dst, images.size).astype(images.dtype).reshape(images.shape)      # (exact: the values are of that type)
+        return out[0] if single else out
+    finally:
+        dev.close()
+
+
+def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame-view', roi=None, dtype='f32', batch=None, shifts=None,
+                                register=('views', 'frames'), max_shift=8, refine=1, interp=3, acceleration=None, tv_lambda=None,
+                                tv_epsilon=0.1, device=None):
+    """deconvolve_stack with every image registered on the device before the iterations.  raw, camera, order, roi, dtype, batch,
+    acceleration, tv_lambda, tv_epsilon: exactly those of deconvolve_stack.
+    register: 'frames' in it -- image (f, v) is registered to image (0, v), the same PSF: drift over time; 'views' in it -- image
+    (0, v) is registered to image (0, 0) (every PSF here is point-symmetric, so the correlation of two different blurs of one object
+    still peaks at the true displacement); the shift applied to (f, v) is the sum of the two.  shifts: an (F, V, 2) array skips the
+    estimation.  max_shift, refine: as for estimate_shifts (the margin is max_shift + 2).  interp: 3 (cubic B-spline) or 1
+    (bilinear); interpolating noisy counts correlates neighbouring pixels -- where the Poisson statistics must be kept exactly, run
+    once for info['shifts'] and again with shifts=np.rint(...) and interp=1, which only moves pixels.
+    Per chunk of `batch` frames, on the context's stream: upload of the raw bytes, rl_ingest into a staging buffer, the estimate,
+    rl_shift_images (floor = camera.epsilon) into the plan's measurement buffer, the iterations from ones, download.  The ingested
+    images of frame 0 stay on the device as the references for the whole call.  There is NO overlap of transfers with the iterations
+    and no u16 export in this path: the estimates come back as float64.
+    Returns (estimates (F, ny, nx) float64, info); info: the ingest statistics of deconvolve_stack ('level', 'clipped', 'saturated',
+    'invalid', each (F, V)), 'shifts' (F, V, 2) as applied, 'ncc', 'at_limit', 'flat' (F, V) of the frame estimates, 'view_ncc',
+    'view_at_limit', 'view_flat' (V,) of the view estimates, 'raised' (F, V) pixels raised to camera.epsilon by the shift, 'unresolved',
+    'strategy', 'chunks', 'batch'."""
+    _lib.tv_params(tv_lambda, tv_epsilon)
+    _lib.accel_mode(acceleration)
+    if dtype not in DTYPES:
+        raise ValueError("dtype must be 'f32' or 'f64'; got %r" % (dtype,))
+    if order not in ORDERS:
+        raise ValueError("order must be 'frame-view' or 'view-frame'; got %r" % (order,))
+    if interp not in (1, 3):
+        raise ValueError('interp must be 1 or 3; got %r' % (interp,))
+    register = (register,) if isinstance(register, str) else tuple(register)
+    if any(r not in ('views', 'frames') for r in register):
+        raise ValueError("register: any of 'views', 'frames'; got %r" % (register,))
+    code = raw_code(raw)
+    raw = np.ascontiguousarray(raw)
+    if 0 in raw.shape:
+        raise ValueError('raw is empty: shape %s' % (raw.shape,))
+    V = len(psfs)
+    F, sy, sx = _stack_shape(raw, V, order)
+    y0, x0, ny, nx = (0, 0, sy, sx) if roi is None else (int(v) for v in roi)
+    if ny < 1 or nx < 1 or y0 < 0 or x0 < 0 or y0 + ny > sy or x0 + nx > sx:
+        raise ValueError('roi %s overhangs the %d x %d sensor frame' % ((y0, x0, ny, nx), sy, sx))
+    if int(iterations) < 0:
+        raise ValueError('iterations must be at least 0')
+    camera = CameraModel() if camera is None else camera
+    camera.check_window(ny, nx)
+    batch = min(F, 256) if batch is None else int(batch)
+    if batch < 1:
+        raise ValueError('batch must be at least 1')
+    given = None
+    if shifts is not None:
+        given = np.asarray(shifts, dtype=np.float64)
+        if given.shape != (F, V, 2) or not np.all(np.isfinite(given)):
+            raise ValueError('shifts: expected finite values of shape %s; got shape %s' % ((F, V, 2), given.shape))
+    elif register:
+        max_shift, refine, margin = _check_search(ny, nx, max_shift, refine, None)
+    frames = raw.reshape((F, V, sy, sx) if order == 'frame-view' else (V, F, sy, sx))
+    n_pix, img_bytes = ny * nx, sy * sx * raw.dtype.itemsize
+    dev = _Device(psfs, batch, (ny, nx), dtype, _lib.DEFAULT_DEVICE if device is None else device, acceleration, tv_lambda, tv_epsilon)
+    try:
+        raw_dev = dev.alloc(batch * V * img_bytes, None)
+        staging, refs = dev.alloc(batch * V * n_pix, dtype), dev.alloc(V * n_pix, dtype)
+        stats_dev = dev.alloc(batch * V * INGEST_FIELDS, 'f64')
+        scratch = dev.alloc(batch * V * n_pix, 'f64') if given is None and register and refine else None
+        dark = None
+        if camera.dark_map is not None:
+            dark = dev.alloc(n_pix, 'f32')
+            dev.upload(dark, camera.dark_map)
+        meas = dev.measurement()
+        out = np.empty((F, ny, nx))
+        ingest_stats, applied, raised = np.zeros((F, V, INGEST_FIELDS)), np.zeros((F, V, 2)), np.zeros((F, V), dtype=np.int64)
+        value, at_limit, flat = np.zeros((F, V)), np.zeros((F, V), dtype=bool), np.zeros((F, V), dtype=bool)
+        view_shift, view_info = np.zeros((V, 2)), {'ncc': np.zeros(V), 'at_limit': np.zeros(V, dtype=bool), 'flat': np.zeros(V, dtype=bool)}
+        for first in range(0, F, batch):
+            nt = min(batch, F - first)
+            if order == 'frame-view':                            # one piece [nt][V]
+                dev.upload(raw_dev, frames[first:first + nt])
+                fs, vs = V, 1
+            else:                                                # V pieces [nt], view v of the chunk at device image v * nt
+                for v in range(V):
+                    dev.upload(raw_dev, frames[v, first:first + nt], v * nt * img_bytes)
+                fs, vs = 1, nt
+            dev.ingest(raw_dev, code, nt * V, (sy, sx), (y0, x0), fs, vs, batch, nt, V, (ny, nx), camera, dark, staging, stats_dev)
+            ingest_stats[first:first + nt] = dev.download(stats_dev, nt * V * INGEST_FIELDS).reshape(nt, V, INGEST_FIELDS)
+            if first == 0:
+                dev.copy(refs, 0, staging, 0, V * n_pix)
+            chunk = np.zeros((batch, V, 2))                      # (fillers: no shift)
+            if given is not None:
+                chunk[:nt] = given[first:first + nt]
+            else:
+                if first == 0 and 'views' in register and V > 1:
+                    view_shift[1:], vi = _estimate(dev, refs, [0] * (V - 1), refs, [v * n_pix for v in range(1, V)], ny, nx, max_shift, refine,
+                                                   margin, scratch)
+                    for k in view_info:
+                        view_info[k][1:] = vi[k]
+                if 'frames' in register:
+                    pairs = [(f, v) for f in range(nt) for v in range(V) if first + f > 0]      # (frame 0 is its own reference)
+                    if pairs:
+                        s, fi = _estimate(dev, refs, [v * n_pix for _, v in pairs], staging, [(f * V + v) * n_pix for f, v in pairs], ny, nx,
+                                          max_shift, refine, margin, scratch)
+                        for k, (f, v) in enumerate(pairs):
+                            chunk[f, v] = s[k]
+                            value[first + f, v], at_limit[first + f, v], flat[first + f, v] = fi['ncc'][k], fi['at_limit'][k], fi['flat'][k]
+                chunk[:nt] += view_shift
+            st = dev.shift(staging, 0, batch * V, ny, nx, chunk.reshape(-1, 2), interp, camera.epsilon, meas)
+            applied[first:first + nt] = chunk[:nt]
+            raised[first:first + nt] = st[:, 0].reshape(batch, V)[:nt].astype(np.int64)
+            out[first:first + nt] = dev.iterate(iterations)[:nt]
+        info = {'level': ingest_stats[:, :, 0].copy(), 'clipped': ingest_stats[:, :, 1].astype(np.int64),
+                'saturated': ingest_stats[:, :, 2].astype(np.int64), 'invalid': ingest_stats[:, :, 3].astype(np.int64),
+                'shifts': applied, 'ncc': value, 'at_limit': at_limit, 'flat': flat, 'view_ncc': view_info['ncc'],
+                'view_at_limit': view_info['at_limit'], 'view_flat': view_info['flat'], 'raised': raised,
+                'unresolved': dev.unresolved(), 'strategy': dev.strategy(), 'chunks': -(-F // batch), 'batch': batch}
+        return out, info
+    finally:
+        dev.close()
