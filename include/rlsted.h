@@ -720,6 +720,37 @@ int rl_register_sums(rl_ctx* ctx, const void* ref_dev, int ref_dtype, const int6
 int rl_shift_images(rl_ctx* ctx, const void* src_dev, int src_dtype, int n, int ny, int nx, const double* shifts, int order,
                     double floor, void* dst_dev, int dst_dtype, double* stats_out);
 
+/* rl_register_xcorr: the coarse stage of the registration -- the cross-correlation of n_pairs image pairs through the transform,
+ * for any search radius: a few 2-D FFTs per pair whatever R.  It PROPOSES an integer displacement; rl_register_sums, the exact
+ * float64 window, judges it.  Addressing as rl_register_sums: ref_dev / mov_dev device buffers of ref_dtype / mov_dtype (RL_F32 /
+ * RL_F64, each its own), pair i = the ny x nx image at element offset ref_offsets[i] / mov_offsets[i] (host arrays, >= 0, no
+ * alignment assumed); many pairs may share a reference, the two buffers may be one.  Sign convention as above: the peak is at d
+ * with B[y + d] ~ A[y].
+ * Per pair: a = A - mean(A), b = B - mean(B), the means over the whole image in float64 (order below), the centred values rounded
+ * to float32; both zero-extended to Ly x Lx, Ly the smallest of 64, 192, 256, 576, 1152 with Ly >= ny + R and Lx likewise from nx
+ * (the axes independently; equality allowed: no lag |d| <= R wraps around).  For d in [-R, R]^2
+ *     C(d) = sum a[y][x] b[y + dy][x + dx]   over the pixels where both lie inside the image (float32 transforms),
+ *     v(d) = (double)C(d) / ((ny - |dy|)(nx - |dx|))   -- the overlap normalisation, without which zero extension pulls the peak to 0.
+ * The peak is the first maximum of v in row-major order, compared in float64.  On their way into the transform a and b are each
+ * scaled by an exact power of two to a norm in [1, 2) (from E_a, E_b below) and the window is scaled back in float64: the packed
+ * transform's rounding error is then relative to ||a|| ||b|| however different the two images' brightness, and any input range fits.
+ * peaks_out: host [n_pairs][RL_XCORR_FIELDS] = dy, dx, v at the peak, E_a = sum a^2, E_b = sum b^2, sum of v over the window, sum of
+ * v^2 over the window.  E_a or E_b not positive: d = (0, 0) and v = 0 (a flat image).  surface_out: NULL, or host
+ * [n_pairs][2 R + 1][2 R + 1] float32 = v, index (dy + R, dx + R) -- for tests and diagnostics.
+ * FIXED ORDER (csrc/xcorr_kernels.hpp), no atomics: a mean and an energy are 256 strided partial sums (element t, t + 256, ... in
+ * increasing order from 0.0; the energy with fma(a, a, .) on the float32-rounded centred value widened again) joined by a halving
+ * tree; the window sums run per window row over its columns in increasing order from 0.0 (s + v; q + v v, two roundings), then over the rows
+ * in increasing order.  Results are bit-identical from run to run, a pair's result does not depend on the other pairs of the call,
+ * and nothing outside an image is read.  Error of C against exact arithmetic: tests/xcorr_reference.py derives
+ *     |C_dev - C| <= kappa eps_f32 (log2 Ly + log2 Lx) ||a||_2 ||b||_2.
+ * Pairs are processed in chunks whose spectra stay under a fixed cap, in the context's workspace.  Synchronises the context's stream.
+ * RL_ERR_INVALID (no kernel is launched): a NULL ctx / buffer / offsets / peaks_out, a dtype that is neither, n_pairs < 1, ny or
+ * nx < 1, R < 1, R > min(ny, nx) / 2, ny + R or nx + R > 1152 (the lengths 2304 and 4608 have a column geometry of their own and
+ * are not served), a negative offset. */
+#define RL_XCORR_FIELDS 7
+int rl_register_xcorr(rl_ctx* ctx, const void* ref_dev, int ref_dtype, const int64_t* ref_offsets, const void* mov_dev, int mov_dtype,
+                      const int64_t* mov_offsets, int n_pairs, int ny, int nx, int R, double* peaks_out, float* surface_out);
+
 /* ---- line_sted_figure_3.py: the scan-position-by-scan-position imaging simulator (:76-273) ----
  * rl_rotate_image: `rotate` (:382-391) for one [ny][nx] plane -- scipy.ndimage.rotate(order 3,
  * mode 'nearest', reshape=False) about the centre; clip != 0 clips to [0, 1.1 * max(in)].  Host in / out. */

@@ -1,5 +1,5 @@
-// kernel_variants.hpp -- the ONLY statement of which instantiations of k_colconv, k_colconv_outer, k_rowpass and k_rowpair
-// exist and of which one a launch gets.  Free of HIP: fft_kernels.hip launches and prepares through it, the host emulators
+// kernel_variants.hpp -- the ONLY statement of which instantiations of k_colconv, k_colconv_outer, k_rowpass, k_rowpair and
+// k_xcorr exist and of which one a launch gets.  Free of HIP: fft_kernels.hip launches and prepares through it, the host emulators
 // (tests/emu) run and list their bodies through it.  Per family:
 //   - a list, one row per instantiation, with the condition under which the row exists for a length and type;
 //   - a tag type per row and for_each_<family>(f), the walk every reader uses: f(tag) for each row that exists, until f
@@ -223,6 +223,40 @@ inline bool select_rowpair(int nx_special, int mode, int nx, int V, bool sub_one
     if (nx_special != 0 && nx == nx_special && V == 1 && sub_one && mode != ROW_FWD) k = {mode, nx_special, 1};
     else k = {mode, 0, -1};
     return true;
+}
+
+// ---------------------------------------------------------------------------------------------- k_xcorr
+// The transform kernels of the coarse registration stage (xcorr_kernels.hpp: XC_ROW = 0, XC_COL = 1, XC_INV = 2), f32 only, on
+// the row geometry CfgFor<L>::Cfg.  One row per (length, stage); the lengths whose column pass has a geometry of its own
+// (ColCfgFor<2304>, ColCfgFor<4608>) have no rows: rl_register_xcorr refuses them.
+#define RL_XCORR_LENGTHS(X) X(64) X(192) X(256) X(576) X(1152)
+
+struct XcKey {
+    int L, stage;
+    constexpr bool operator==(const XcKey& o) const { return L == o.L && stage == o.stage; }
+};
+template <int L_, int STAGE_>
+struct XcVariant {
+    static constexpr int L = L_, STAGE = STAGE_;
+    static constexpr XcKey key() { return {L, STAGE}; }
+};
+template <class F>
+bool for_each_xcorr(F&& f) {
+#define X(LEN)                                   \
+    if (f(XcVariant<LEN, 0>{})) return true;     \
+    if (f(XcVariant<LEN, 1>{})) return true;     \
+    if (f(XcVariant<LEN, 2>{})) return true;
+    RL_XCORR_LENGTHS(X)
+#undef X
+    return false;
+}
+// the smallest length with a row that holds n samples (n = image side + search radius); 0: none
+inline int select_xcorr(long long n) {
+#define X(LEN) \
+    if (n <= LEN) return LEN;
+    RL_XCORR_LENGTHS(X)
+#undef X
+    return 0;
 }
 
 }  // namespace rl

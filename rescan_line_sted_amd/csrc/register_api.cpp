@@ -1,6 +1,6 @@
-// register_api.cpp -- C ABI of the registration primitives (include/rlsted.h: rl_register_sums, rl_shift_images): validation, the
-// shift's taps (formed on the host in long double, register_kernels.hpp shift_taps), the chunking under the workspace caps and the
-// launches of register_kernels.hip.  Only offsets and taps go up and the sums and statistics come down.  No kernel is launched on
+// register_api.cpp -- C ABI of the registration primitives (include/rlsted.h: rl_register_sums, rl_shift_images,
+// rl_register_xcorr): validation, the shift's taps (formed on the host in long double, register_kernels.hpp shift_taps), the
+// chunking under the workspace caps and the launches of register_kernels.hip and xcorr_kernels.hip.  Only offsets and taps go up and the sums and statistics come down.  No kernel is launched on
 // bad arguments.
 #include <algorithm>
 #include <cmath>
@@ -8,13 +8,27 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "kernel_variants.hpp"
 #include "register_kernels.hpp"
+#include "xcorr_kernels.hpp"
 
 using namespace rl;
 
 namespace {
 constexpr size_t kRegSumWorkBytes = (size_t)256 << 20;     // the partials of the pairs in flight; a larger single pair runs alone
 constexpr size_t kShiftWorkBytes = (size_t)512 << 20;      // the float64 intermediates of the images in flight
+constexpr size_t kXcorrWorkBytes = (size_t)32 << 20;       // the spectra and kept rows of the pairs in flight; a larger single pair runs alone
+
+const KernelTable* xcorr_table(int L) {
+    switch (L) {
+        case 64: return table_64();
+        case 192: return table_192();
+        case 256: return table_256();
+        case 576: return table_576();
+        case 1152: return table_1152();
+    }
+    return nullptr;
+}
 
 size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 bool float_dtype_ok(int d) { return d == RL_F32 || d == RL_F64; }
@@ -124,5 +138,59 @@ extern "C" int rl_shift_images(rl_ctx* ctx, const void* src_dev, int src_dtype, 
     }
     if (stats_out) HIP_TRY(hipMemcpyAsync(stats_out, stats, (size_t)n * kShiftFields * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));   // (the taps' table is the call's own)
+    return RL_OK;
+}
+
+extern "C" int rl_register_xcorr(rl_ctx* ctx, const void* ref_dev, int ref_dtype, const int64_t* ref_offsets, const void* mov_dev,
+                                 int mov_dtype, const int64_t* mov_offsets, int n_pairs, int ny, int nx, int R, double* peaks_out,
+                                 float* surface_out) {
+    if (!ctx || !ref_dev || !ref_offsets || !mov_dev || !mov_offsets || !peaks_out) return fail(RL_ERR_INVALID, "NULL argument");
+    if (!float_dtype_ok(ref_dtype) || !float_dtype_ok(mov_dtype)) return fail(RL_ERR_INVALID, "dtypes must be RL_F32 or RL_F64");
+    if (n_pairs < 1) return fail(RL_ERR_INVALID, "n_pairs must be at least 1");
+    if (ny < 1 || nx < 1) return fail(RL_ERR_INVALID, "ny and nx must be at least 1");
+    if (R < 1 || R > std::min(ny, nx) / 2) return fail(RL_ERR_INVALID, "the search radius must lie in 1 .. min(ny, nx) / 2");
+    const int Ly = select_xcorr((long long)ny + R), Lx = select_xcorr((long long)nx + R);
+    if (!Ly || !Lx)
+        return fail(RL_ERR_INVALID, "ny + R and nx + R must not exceed the largest transform length of the coarse stage (" + std::to_string(kXcMaxL) + ")");
+    for (int i = 0; i < n_pairs; ++i)
+        if (ref_offsets[i] < 0 || mov_offsets[i] < 0) return fail(RL_ERR_INVALID, "pair " + std::to_string(i) + ": negative offset");
+    static_assert(kXcFields == RL_XCORR_FIELDS, "the header's field count");
+    HIP_TRY(hipSetDevice(ctx->device));
+    void *tw_y = nullptr, *tw_x = nullptr;
+    RL_TRY(ctx->twiddles(xcorr_table(Ly), RL_F32, &tw_y));
+    RL_TRY(ctx->twiddles(xcorr_table(Lx), RL_F32, &tw_x));
+    const size_t W = 2 * (size_t)R + 1;
+    const size_t spec_b = round_up((size_t)ny * Lx * sizeof(cx<float>), 256), rows_b = round_up(W * Lx * sizeof(cx<float>), 256);
+    const size_t corr_b = round_up(W * W * sizeof(float), 256), surf_b = surface_out ? corr_b : 0;
+    const size_t per = spec_b + rows_b + corr_b + surf_b;
+    const size_t chunk = std::min<size_t>((size_t)n_pairs, std::max<size_t>(1, kXcorrWorkBytes / per));
+    const size_t off_bytes = round_up((size_t)n_pairs * sizeof(long long), 256);
+    const size_t stats_b = round_up(chunk * 4 * sizeof(double), 256), peaks_b = round_up(chunk * kXcFields * sizeof(double), 256);
+    char* w = nullptr;
+    RL_TRY(reg_workspace(ctx, 2 * off_bytes + stats_b + peaks_b + chunk * per, &w));
+    long long* a_off = (long long*)w;
+    long long* b_off = (long long*)(w + off_bytes);
+    XcArgs a;
+    a.a = ref_dev; a.b = mov_dev; a.a_f64 = ref_dtype == RL_F64; a.b_f64 = mov_dtype == RL_F64;
+    a.ny = ny; a.nx = nx; a.R = R; a.Ly = Ly; a.Lx = Lx;
+    char* q = w + 2 * off_bytes;
+    a.stats = (double*)q; q += stats_b;
+    a.peaks = (double*)q; q += peaks_b;
+    a.spec = (cx<float>*)q; q += chunk * spec_b;
+    a.rows = (cx<float>*)q; q += chunk * rows_b;
+    a.corr = (float*)q; q += chunk * corr_b;
+    a.surf = surface_out ? (float*)q : nullptr;
+    a.tw_y = (const cx<float>*)tw_y; a.tw_x = (const cx<float>*)tw_x;
+    HIP_TRY(hipMemcpyAsync(a_off, ref_offsets, (size_t)n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(b_off, mov_offsets, (size_t)n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    for (size_t first = 0; first < (size_t)n_pairs; first += chunk) {
+        const size_t n = std::min(chunk, (size_t)n_pairs - first);
+        a.a_off = a_off + first; a.b_off = b_off + first; a.pairs = (int)n;
+        HIP_TRY(xcorr_pairs(a, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(peaks_out + first * kXcFields, a.peaks, n * kXcFields * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        if (surface_out)
+            HIP_TRY(hipMemcpyAsync(surface_out + first * W * W, a.surf, n * W * W * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
     return RL_OK;
 }

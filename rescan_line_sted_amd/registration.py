@@ -21,6 +21,8 @@ from ._lib import DTYPES, check, lib
 from .stack import INGEST_FIELDS, ORDERS, CameraModel, _stack_shape, raw_code
 
 MAX_RADIUS = 32                       # rl_register_sums
+XCORR_FIELDS = 7                      # rl_register_xcorr
+XCORR_MAX_LENGTH = 1152               # the largest transform length of the coarse stage: image side + radius
 _NP = {'f32': np.float32, 'f64': np.float64}
 _I64P = ctypes.POINTER(ctypes.c_int64)
 
@@ -68,9 +70,12 @@ def _check_search(ny, nx, max_shift, refine, margin):
     return max_shift, refine, margin
 
 
-def _estimate(dev, ref, ref_offsets, mov, mov_offsets, ny, nx, max_shift, refine, margin, scratch, surfaces=False):
+def _estimate(dev, ref, ref_offsets, mov, mov_offsets, ny, nx, max_shift, refine, margin, scratch, surfaces=False, coarse=None):
     """Stages 1 - 5 for the pairs (ref at ref_offsets[i], mov at mov_offsets[i]) through dev.sums / dev.shift; scratch: a float64
-    buffer of len(pairs) images (refine > 0).  Returns (shifts (N, 2), info)."""
+    buffer of len(pairs) images (refine > 0, or coarse).  coarse: None, or the radius of the coarse stage in front
+    (_estimate_coarse).  Returns (shifts (N, 2), info)."""
+    if coarse is not None:
+        return _estimate_coarse(dev, ref, ref_offsets, mov, mov_offsets, ny, nx, max_shift, refine, coarse, scratch, surfaces)
     N = len(mov_offsets)
     n = (ny - 2 * margin) * (nx - 2 * margin)
     shifts, value = np.zeros((N, 2)), np.zeros(N)
@@ -96,6 +101,84 @@ def _estimate(dev, ref, ref_offsets, mov, mov_offsets, ny, nx, max_shift, refine
                 d, value[i], _ = surface_peak(c)
                 shifts[i] += d
     info = {'ncc': value, 'at_limit': at_limit, 'flat': flat}
+    if surfaces:
+        info['surfaces'] = np.stack(kept)
+    return shifts, info
+
+
+# ---- host logic: the coarse stage ----------------------------------------------------------------------------------------------------
+def coarse_fields(peaks, radius):
+    """(c (N, 2) int64, value, snr, flat) from the fields of rl_register_xcorr [N][7]: snr = (peak - window mean) / window standard
+    deviation (0 where the window has no variance); flat: an energy that is not positive."""
+    peaks = np.asarray(peaks, dtype=np.float64).reshape(-1, XCORR_FIELDS)
+    n = float((2 * radius + 1) ** 2)
+    mean = peaks[:, 5] / n
+    var = peaks[:, 6] / n - mean * mean
+    ok = var > 0.0
+    snr = np.zeros(len(peaks))
+    snr[ok] = (peaks[ok, 2] - mean[ok]) / np.sqrt(var[ok])
+    flat = ~(peaks[:, 3] > 0.0) | ~(peaks[:, 4] > 0.0)
+    return np.rint(peaks[:, :2]).astype(np.int64), peaks[:, 2].copy(), snr, flat
+
+
+def coarse_margin(c, max_shift):
+    """The margin of the pairs with coarse displacements c (N, 2): 8 ceil(|c|_inf / 8) + max_shift + 2 -- the band the order-1 copy
+    fills by mirroring stays outside the sums; a function of the pair alone, so a pair's result does not depend on its call."""
+    c = np.asarray(c).reshape(-1, 2)
+    return 8 * ((np.abs(c).max(axis=1) + 7) // 8) + max_shift + 2
+
+
+def _check_coarse(ny, nx, coarse, max_shift, margin):
+    if coarse is None:
+        return None
+    if int(coarse) != coarse or int(coarse) < 1:
+        raise ValueError('coarse must be None or a radius of at least 1 pixel; got %r' % (coarse,))
+    coarse = int(coarse)
+    if margin is not None:
+        raise ValueError('margin cannot be given together with coarse: every pair gets 8 ceil(|c| / 8) + max_shift + 2')
+    worst = coarse + max_shift + 2
+    if ny - 2 * worst < 8 or nx - 2 * worst < 8:
+        raise ValueError('a %d x %d image leaves no 8 x 8 interior inside coarse + max_shift + 2 = %d pixels' % (ny, nx, worst))
+    if ny + coarse > XCORR_MAX_LENGTH or nx + coarse > XCORR_MAX_LENGTH:
+        raise ValueError('the coarse stage serves image side + coarse <= %d; got %d x %d with coarse = %d' % (XCORR_MAX_LENGTH, ny, nx, coarse))
+    return coarse
+
+
+def _estimate_coarse(dev, ref, ref_offsets, mov, mov_offsets, ny, nx, max_shift, refine, coarse, scratch, surfaces=False):
+    """The two-stage estimate: rl_register_xcorr proposes c_i; the moving image displaced by c_i (order 1: a copy of the displaced
+    pixels) goes through the exact window of radius max_shift; shift = c_i + peak + parabola; the refine passes shift the ORIGINAL
+    image by the total.  Pairs of equal margin share the device calls.  scratch: a float64 buffer of len(pairs) images."""
+    N = len(mov_offsets)
+    n_pix = ny * nx
+    peaks = dev.xcorr(ref, ref_offsets, mov, mov_offsets, ny, nx, coarse)
+    c, cvalue, csnr, cflat = coarse_fields(peaks, coarse)
+    margins = coarse_margin(c, max_shift)
+    shifts, value = c.astype(np.float64), np.zeros(N)
+    at_limit, flat = np.zeros(N, dtype=bool), np.zeros(N, dtype=bool)
+    kept = [None] * N
+    for M in sorted(set(int(m) for m in margins)):
+        idx = np.flatnonzero(margins == M)
+        n = (ny - 2 * M) * (nx - 2 * M)
+        dev.gather_shift(mov, [mov_offsets[i] for i in idx], ny, nx, c[idx].astype(np.float64), scratch, order=1)
+        S, A = dev.sums(ref, [ref_offsets[i] for i in idx], scratch, [k * n_pix for k in range(idx.size)], ny, nx, max_shift, M)
+        for k, i in enumerate(idx):
+            s, flat[i] = ncc_surface(S[k], A[k], n)
+            kept[i] = s
+            if not flat[i]:
+                d, value[i], at_limit[i] = surface_peak(s)
+                shifts[i] = np.where(c[i] == 0, d, c[i] + d)
+        for _ in range(refine):
+            live = idx[~flat[idx]]
+            if live.size == 0:
+                break
+            dev.gather_shift(mov, [mov_offsets[i] for i in live], ny, nx, shifts[live], scratch)
+            S, A = dev.sums(ref, [ref_offsets[i] for i in live], scratch, [k * n_pix for k in range(live.size)], ny, nx, 1, M)
+            for k, i in enumerate(live):
+                s, f = ncc_surface(S[k], A[k], n)
+                if not f:
+                    d, value[i], _ = surface_peak(s)
+                    shifts[i] += d
+    info = {'ncc': value, 'at_limit': at_limit, 'flat': flat, 'coarse': c, 'coarse_value': cvalue, 'coarse_snr': csnr, 'coarse_flat': cflat}
     if surfaces:
         info['surfaces'] = np.stack(kept)
     return shifts, info
@@ -170,6 +253,18 @@ class _Device:
                                    mo.ctypes.data_as(_I64P), n, ny, nx, R, M, _lib.ptr(S), _lib.ptr(A)))
         return S, A
 
+    def xcorr(self, ref, ref_offsets, mov, mov_offsets, ny, nx, R, surfaces=False):
+        """rl_register_xcorr: the fields [pairs][7]; with surfaces=True (fields, v [pairs][2R+1][2R+1] float32)."""
+        n = len(mov_offsets)
+        W = 2 * R + 1
+        ro, mo = np.ascontiguousarray(ref_offsets, dtype=np.int64), np.ascontiguousarray(mov_offsets, dtype=np.int64)
+        P = np.empty((n, XCORR_FIELDS))
+        V = np.empty((n, W, W), dtype=np.float32) if surfaces else None
+        check(lib.rl_register_xcorr(self.ctx.handle, ref.ptr, DTYPES[ref.dtype], ro.ctypes.data_as(_I64P), mov.ptr, DTYPES[mov.dtype],
+                                    mo.ctypes.data_as(_I64P), n, ny, nx, R, _lib.ptr(P),
+                                    None if V is None else V.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        return (P, V) if surfaces else P
+
     def shift(self, src, src_element, n, ny, nx, shifts, order, floor, dst, dst_element=0):
         """rl_shift_images on n consecutive images; returns the statistics [n][2] (raised, sum)."""
         sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(n, 2)
@@ -178,15 +273,15 @@ class _Device:
                                   -np.inf if floor is None else float(floor), dst.at(dst_element), DTYPES[dst.dtype], _lib.ptr(stats)))
         return stats
 
-    def gather_shift(self, src, offsets, ny, nx, shifts, dst):
-        """The images at the element offsets of src, each by its shift (order 3, no floor), to consecutive images of dst; runs of
-        consecutive images go through one call."""
+    def gather_shift(self, src, offsets, ny, nx, shifts, dst, order=3):
+        """The images at the element offsets of src, each by its shift (order 3 unless given, no floor), to consecutive images of
+        dst; runs of consecutive images go through one call."""
         offsets, k = list(offsets), 0
         while k < len(offsets):
             m = 1
             while k + m < len(offsets) and offsets[k + m] == offsets[k] + m * ny * nx:
                 m += 1
-            self.shift(src, offsets[k], m, ny, nx, shifts[k:k + m], 3, None, dst, k * ny * nx)
+            self.shift(src, offsets[k], m, ny, nx, shifts[k:k + m], order, None, dst, k * ny * nx)
             k += m
 
     def iterate(self, iterations):
@@ -216,13 +311,7 @@ def _float_images(a, name):
 
 
 # ---- public ----------------------------------------------------------------------------------------------------------------------------
-def estimate_shifts(images, reference, max_shift=8, refine=1, margin=None, device=None, surfaces=False):
-    """The translation of every image relative to its reference.  images: (N, ny, nx) or (ny, nx), float32 or float64; reference:
-    (ny, nx), shared, or (N, ny, nx).  max_shift: the search radius in pixels, 1 .. 32.  refine: passes that shift the image by
-    the current estimate (order 3) and add the parabola offset of a 3 x 3 window.  margin: pixels at every border kept out of the
-    sums (default, and at least with refine > 0, max_shift + 2).  Returns (shifts (N, 2) float64 (dy, dx), info) with info['ncc']
-    (the peak value), 'at_limit' (the integer peak lay on the window's border: no sub-pixel part, the drift may be larger), 'flat' (an
-    image without variance: shift 0) and, with surfaces=True, 'surfaces' (N, W, W)."""
+def _pairs_on_device(images, reference):
     images, dt = _float_images(images, 'images')
     reference, rdt = _float_images(reference, 'reference')
     if images.ndim == 2:
@@ -232,16 +321,67 @@ def estimate_shifts(images, reference, max_shift=8, refine=1, margin=None, devic
     N, ny, nx = images.shape
     if reference.shape not in ((ny, nx), (N, ny, nx)):
         raise ValueError('reference: expected %s or %s; got shape %s' % ((ny, nx), (N, ny, nx), reference.shape))
-    max_shift, refine, margin = _check_search(ny, nx, max_shift, refine, margin)
+    return images, dt, reference, rdt
+
+
+def coarse_shifts(images, reference, radius, device=None, surfaces=False):
+    """The integer displacement of every image relative to its reference from the FFT cross-correlation over [-radius, radius]^2
+    (rl_register_xcorr): a proposal for any drift radius at the cost of a few transforms per pair, to be judged by the exact window
+    (estimate_shifts(coarse=radius) does both).  images, reference: as for estimate_shifts; radius: 1 .. min(ny, nx) / 2 with
+    ny + radius and nx + radius <= 1152.  Returns (c (N, 2) int64 (dy, dx), info) with info['value'] (the overlap-normalised
+    covariance at the peak), 'snr' ((peak - window mean) / window standard deviation: a peak that does not stand out of its window
+    is not to be trusted), 'flat' (an image without variance: c = 0) and, with surfaces=True, 'surfaces' (N, W, W) float32."""
+    images, dt, reference, rdt = _pairs_on_device(images, reference)
+    N, ny, nx = images.shape
+    if int(radius) != radius or not 1 <= int(radius) <= min(ny, nx) // 2:
+        raise ValueError('radius must lie in 1 .. min(ny, nx) / 2 = %d; got %r' % (min(ny, nx) // 2, radius))
+    radius = int(radius)
+    if ny + radius > XCORR_MAX_LENGTH or nx + radius > XCORR_MAX_LENGTH:
+        raise ValueError('the coarse stage serves image side + radius <= %d; got %d x %d with radius %d' % (XCORR_MAX_LENGTH, ny, nx, radius))
     dev = _Device(device=_lib.DEFAULT_DEVICE if device is None else device)
     try:
         mov, ref = dev.alloc(images.size, dt), dev.alloc(reference.size, rdt)
         dev.upload(mov, images)
         dev.upload(ref, reference)
-        scratch = dev.alloc(images.size, 'f64') if refine else None
+        n_pix = ny * nx
+        out = dev.xcorr(ref, [i * n_pix if reference.ndim == 3 else 0 for i in range(N)], mov, [i * n_pix for i in range(N)], ny, nx, radius, surfaces)
+        c, value, snr, flat = coarse_fields(out[0] if surfaces else out, radius)
+        info = {'value': value, 'snr': snr, 'flat': flat}
+        if surfaces:
+            info['surfaces'] = out[1]
+        return c, info
+    finally:
+        dev.close()
+
+
+def estimate_shifts(images, reference, max_shift=8, refine=1, margin=None, device=None, surfaces=False, coarse=None):
+    """The translation of every image relative to its reference.  images: (N, ny, nx) or (ny, nx), float32 or float64; reference:
+    (ny, nx), shared, or (N, ny, nx).  max_shift: the search radius in pixels, 1 .. 32.  refine: passes that shift the image by
+    the current estimate (order 3) and add the parabola offset of a 3 x 3 window.  margin: pixels at every border kept out of the
+    sums (default, and at least with refine > 0, max_shift + 2).  Returns (shifts (N, 2) float64 (dy, dx), info) with info['ncc']
+    (the peak value), 'at_limit' (the integer peak lay on the window's border: no sub-pixel part, the drift may be larger), 'flat' (an
+    image without variance: shift 0) and, with surfaces=True, 'surfaces' (N, W, W).
+    coarse: None -- the window alone, as above -- or a radius Rc: rl_register_xcorr proposes an integer displacement c within Rc
+    pixels (any Rc with ny + Rc, nx + Rc <= 1152), the moving image displaced by c (order 1: a copy of the displaced pixels) goes
+    through the window of radius max_shift, shift = c + peak + parabola, and the refine passes shift the ORIGINAL image by the
+    total, so no image is interpolated twice.  Pair i keeps 8 ceil(|c_i| / 8) + max_shift + 2 pixels out of its sums (the
+    mirror-filled band of the copy), so ny - 2 (Rc + max_shift + 2) >= 8 is required, likewise nx, and margin cannot be given.
+    at_limit then says that the PROPOSAL was wrong (the fine peak lay on the border of the window around c), not that the drift was
+    large.  info gains 'coarse' (N, 2) int64, 'coarse_value', 'coarse_snr', 'coarse_flat' (coarse_shifts)."""
+    images, dt, reference, rdt = _pairs_on_device(images, reference)
+    N, ny, nx = images.shape
+    given_margin = margin
+    max_shift, refine, margin = _check_search(ny, nx, max_shift, refine, None if coarse is not None else margin)
+    coarse = _check_coarse(ny, nx, coarse, max_shift, given_margin)
+    dev = _Device(device=_lib.DEFAULT_DEVICE if device is None else device)
+    try:
+        mov, ref = dev.alloc(images.size, dt), dev.alloc(reference.size, rdt)
+        dev.upload(mov, images)
+        dev.upload(ref, reference)
+        scratch = dev.alloc(images.size, 'f64') if refine or coarse is not None else None
         n_pix = ny * nx
         return _estimate(dev, ref, [i * n_pix if reference.ndim == 3 else 0 for i in range(N)], mov, [i * n_pix for i in range(N)], ny, nx,
-                         max_shift, refine, margin, scratch, surfaces)
+                         max_shift, refine, margin, scratch, surfaces, coarse)
     finally:
         dev.close()
 
@@ -278,13 +418,15 @@ def shift_images(images, shifts, order=3, floor=None, device=None):
 
 def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame-view', roi=None, dtype='f32', batch=None, shifts=None,
                                 register=('views', 'frames'), max_shift=8, refine=1, interp=3, acceleration=None, tv_lambda=None,
-                                tv_epsilon=0.1, device=None):
+                                tv_epsilon=0.1, device=None, coarse=None):
     """deconvolve_stack with every image registered on the device before the iterations.  raw, camera, order, roi, dtype, batch,
     acceleration, tv_lambda, tv_epsilon: exactly those of deconvolve_stack.
     register: 'frames' in it -- image (f, v) is registered to image (0, v), the same PSF: drift over time; 'views' in it -- image
     (0, v) is registered to image (0, 0) (every PSF here is point-symmetric, so the correlation of two different blurs of one object
     still peaks at the true displacement); the shift applied to (f, v) is the sum of the two.  shifts: an (F, V, 2) array skips the
-    estimation.  max_shift, refine: as for estimate_shifts (the margin is max_shift + 2).  interp: 3 (cubic B-spline) or 1
+    estimation.  max_shift, refine, coarse: as for estimate_shifts (the margin is max_shift + 2; with coarse=Rc both the view and the
+    frame estimates take the coarse stage first -- drift of any size up to Rc -- and info gains 'coarse' (F, V, 2), 'coarse_snr'
+    (F, V), 'view_coarse' (V, 2), 'view_coarse_snr' (V,); given shifts=, no coarse call is made).  interp: 3 (cubic B-spline) or 1
     (bilinear); interpolating noisy counts correlates neighbouring pixels -- where the Poisson statistics must be kept exactly, run
     once for info['shifts'] and again with shifts=np.rint(...) and interp=1, which only moves pixels.
     Per chunk of `batch` frames, on the context's stream: upload of the raw bytes, rl_ingest into a staging buffer, the estimate,
@@ -329,6 +471,8 @@ def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame
             raise ValueError('shifts: expected finite values of shape %s; got shape %s' % ((F, V, 2), given.shape))
     elif register:
         max_shift, refine, margin = _check_search(ny, nx, max_shift, refine, None)
+        coarse = _check_coarse(ny, nx, coarse, max_shift, None)
+    estimating = given is None and bool(register)
     frames = raw.reshape((F, V, sy, sx) if order == 'frame-view' else (V, F, sy, sx))
     n_pix, img_bytes = ny * nx, sy * sx * raw.dtype.itemsize
     dev = _Device(psfs, batch, (ny, nx), dtype, _lib.DEFAULT_DEVICE if device is None else device, acceleration, tv_lambda, tv_epsilon)
@@ -336,7 +480,7 @@ def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame
         raw_dev = dev.alloc(batch * V * img_bytes, None)
         staging, refs = dev.alloc(batch * V * n_pix, dtype), dev.alloc(V * n_pix, dtype)
         stats_dev = dev.alloc(batch * V * INGEST_FIELDS, 'f64')
-        scratch = dev.alloc(batch * V * n_pix, 'f64') if given is None and register and refine else None
+        scratch = dev.alloc(batch * V * n_pix, 'f64') if estimating and (refine or coarse is not None) else None
         dark = None
         if camera.dark_map is not None:
             dark = dev.alloc(n_pix, 'f32')
@@ -346,6 +490,9 @@ def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame
         ingest_stats, applied, raised = np.zeros((F, V, INGEST_FIELDS)), np.zeros((F, V, 2)), np.zeros((F, V), dtype=np.int64)
         value, at_limit, flat = np.zeros((F, V)), np.zeros((F, V), dtype=bool), np.zeros((F, V), dtype=bool)
         view_shift, view_info = np.zeros((V, 2)), {'ncc': np.zeros(V), 'at_limit': np.zeros(V, dtype=bool), 'flat': np.zeros(V, dtype=bool)}
+        use_coarse = coarse if estimating else None
+        coarse_c, coarse_snr = np.zeros((F, V, 2), dtype=np.int64), np.zeros((F, V))
+        view_coarse, view_coarse_snr = np.zeros((V, 2), dtype=np.int64), np.zeros(V)
         for first in range(0, F, batch):
             nt = min(batch, F - first)
             if order == 'frame-view':                            # one piece [nt][V]
@@ -365,16 +512,20 @@ def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame
             else:
                 if first == 0 and 'views' in register and V > 1:
                     view_shift[1:], vi = _estimate(dev, refs, [0] * (V - 1), refs, [v * n_pix for v in range(1, V)], ny, nx, max_shift, refine,
-                                                   margin, scratch)
+                                                   margin, scratch, coarse=use_coarse)
                     for k in view_info:
                         view_info[k][1:] = vi[k]
+                    if use_coarse is not None:
+                        view_coarse[1:], view_coarse_snr[1:] = vi['coarse'], vi['coarse_snr']
                 if 'frames' in register:
                     pairs = [(f, v) for f in range(nt) for v in range(V) if first + f > 0]      # (frame 0 is its own reference)
                     if pairs:
                         s, fi = _estimate(dev, refs, [v * n_pix for _, v in pairs], staging, [(f * V + v) * n_pix for f, v in pairs], ny, nx,
-                                          max_shift, refine, margin, scratch)
+                                          max_shift, refine, margin, scratch, coarse=use_coarse)
                         for k, (f, v) in enumerate(pairs):
                             chunk[f, v] = s[k]
+                            if use_coarse is not None:
+                                coarse_c[first + f, v], coarse_snr[first + f, v] = fi['coarse'][k], fi['coarse_snr'][k]
                             value[first + f, v], at_limit[first + f, v], flat[first + f, v] = fi['ncc'][k], fi['at_limit'][k], fi['flat'][k]
                 chunk[:nt] += view_shift
             st = dev.shift(staging, 0, batch * V, ny, nx, chunk.reshape(-1, 2), interp, camera.epsilon, meas)
@@ -386,6 +537,8 @@ def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame
                 'shifts': applied, 'ncc': value, 'at_limit': at_limit, 'flat': flat, 'view_ncc': view_info['ncc'],
                 'view_at_limit': view_info['at_limit'], 'view_flat': view_info['flat'], 'raised': raised,
                 'unresolved': dev.unresolved(), 'strategy': dev.strategy(), 'chunks': -(-F // batch), 'batch': batch}
+        if use_coarse is not None:
+            info.update({'coarse': coarse_c, 'coarse_snr': coarse_snr, 'view_coarse': view_coarse, 'view_coarse_snr': view_coarse_snr})
         return out, info
     finally:
         dev.close()
