@@ -280,6 +280,15 @@ int rl_deconv_simulated_images(const rl_deconv* h, int* images);
  * hardware queue with a lane ("Draws ahead").  0 before the first cycle and whenever the switch is off.   */
 int rl_deconv_draws_ahead(const rl_deconv* h, int* slices);
 
+/* Slices of the last simulate + deconvolve cycle whose Poisson draw ran through the frame-group kernel.  The frames of a slice
+ * that shares its simulation (rl_deconv_object_classes) draw from few rate images; with the Philox generator such a slice is
+ * drawn in groups of 8 frames of one rate image (where the launch has as many) per tile of 256 pixels, and what the sampler
+ * derives from the rate alone -- a square root, divisions, two logarithms -- is evaluated once per pixel and run of frames
+ * with one rate image instead of once per frame.  Every draw keeps its frame's own key and image id: measurements and estimates are the same bits either way.
+ * RLSTED_POISSON_GROUPS=0 in the environment when the plan is created draws every slice through the per-frame kernel.  Slices
+ * that do not share and draws with RL_RNG_NONE take the per-frame kernel always.  0 before the first cycle.                    */
+int rl_deconv_grouped_draws(const rl_deconv* h, int* slices);
+
 /* Predictions the plan could not resolve.  iterate divides the measurement by H(estimate) clamped at 0 (line_sted_tools.py:575,
  * 524); in exact arithmetic that prediction is positive, but a transform resolves a value to eps * the frame's maximum only, so
  * on sparse emitters over a black background the predictions of the dark region are rounding noise of either sign -- below 1e-7

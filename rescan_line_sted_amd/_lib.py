@@ -88,6 +88,7 @@ PROTOTYPES = {
     'rl_deconv_object_classes': (_i, [_vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)]),
     'rl_deconv_simulated_images': (_i, [_vp, _c.POINTER(_i)]),
     'rl_deconv_draws_ahead': (_i, [_vp, _c.POINTER(_i)]),
+    'rl_deconv_grouped_draws': (_i, [_vp, _c.POINTER(_i)]),
     'rl_deconv_unresolved': (_i, [_vp, _c.POINTER(_c.c_uint64), _i]),
     'rl_deconv_dims': (_i, [_vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)]),
     'rl_batch_run': (_i, [_vp, _vp, _i, _i, _i, _dp]),
@@ -313,6 +314,13 @@ class DeconvPlan:
         rl_deconv_draws_ahead); 0 where every slice drew at the head of its lane."""
         a = _i()
         check(lib.rl_deconv_draws_ahead(self.handle, ctypes.byref(a)))
+        return a.value
+
+    def grouped_draws(self):
+        """Slices of the last cycle whose Poisson draw ran through the frame-group kernel (include/rlsted.h
+        rl_deconv_grouped_draws); 0 with RLSTED_POISSON_GROUPS=0 and where no slice shared its simulation."""
+        a = _i()
+        check(lib.rl_deconv_grouped_draws(self.handle, ctypes.byref(a)))
         return a.value
 
     def set_object(self, obj, total_brightness=None):

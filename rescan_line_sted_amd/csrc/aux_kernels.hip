@@ -3,7 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "aux_kernels.hpp"
+#include "dev_sync.hpp"
 #include "philox_poisson.hpp"
+#include "poisson_kernels.hpp"
 
 namespace rl {
 
@@ -54,34 +56,6 @@ __global__ void k_psf_dft_cols(const double2* __restrict__ s1, const double2* __
         out[((size_t)v * ly + ky) * pitch + k] = mk<T>((T)(re * scale), (T)(im * scale));
     }
 }
-
-// Philox key / counter of an image of the launch: one seed and consecutive image indices from
-// image0, or -- frame_seeds != nullptr -- a seed and an image id per frame (V views each), so that
-// a frame's draws do not depend on which batch it was put in.
-struct PoissonKeys {
-    unsigned long long seed0;
-    unsigned image0, V;
-    const unsigned long long* frame_seeds;   // [frames] or nullptr
-    const unsigned* frame_ids;               // [frames] (with frame_seeds)
-    // [frames] or nullptr: frame f of the launch takes its rates from images rate_frame[f] * V + view of `noiseless` (frames that
-    // carry the same object share one simulated image, object_classes.hpp); the counters above stay the frame's own
-    const unsigned* rate_frame;
-    __device__ __forceinline__ unsigned long long seed(unsigned img) const { return frame_seeds ? frame_seeds[img / V] : seed0; }
-    __device__ __forceinline__ unsigned image(unsigned img) const {
-        return frame_seeds ? frame_ids[img / V] * V + img % V : image0 + img;
-    }
-    template <typename T>
-    __device__ __forceinline__ T rate(const T* __restrict__ noiseless, unsigned i, unsigned n_pix) const {
-        if (!rate_frame) return noiseless[i];   // (uniform)
-        const unsigned img = i / n_pix, pix = i - img * n_pix;
-        return noiseless[((size_t)rate_frame[img / V] * V + img % V) * n_pix + pix];
-    }
-    // the rates of image `img` of the launch, for a tile that lies inside it (img is workgroup uniform: scalar loads)
-    template <typename T>
-    __device__ __forceinline__ const T* image_rates(const T* __restrict__ noiseless, unsigned img, unsigned n_pix) const {
-        return noiseless + (rate_frame ? (size_t)rate_frame[img / V] * V + img % V : (size_t)img) * n_pix;
-    }
-};
 
 // noisy = Poisson(noiseless) + 1e-9   (line_sted_tools.py:510).  ONE launch since round 4: a workgroup takes tiles of 2048
 // pixels; every pixel gets the first PTRS attempt (philox_poisson_fast: ~87 % are squeeze-accepted and written at once), the
@@ -181,6 +155,20 @@ __global__ void __launch_bounds__(256) k_poisson(const T* __restrict__ noiseless
         }
         __syncthreads();                      // the lists are free for the next tile
     }
+}
+
+// Frames that share rate images (keys.rate_frame), Philox: groups of kPoissonGroup frames per 256-pixel tile, the PTRS set-up once
+// per pixel and run of equal rate images instead of once per frame (poisson_kernels.hpp).  29.0 KB of LDS against k_poisson's 32.8.
+struct PoissonSync : DevSync {
+    __device__ __forceinline__ unsigned lds_add(unsigned* p, unsigned v) const { return atomicAdd(p, v); }
+};
+template <typename T>
+// amdgpu_waves_per_eu(5): 96 vector registers instead of 98, so that the fifth workgroup per CU that the LDS allows fits the register
+// file too; 2 registers go to 12 B of scratch per lane for it (tests/test_poisson_groups_cpu.py holds the kernel to that).  Kernel
+// median 6.5 % lower with it, and the headline's rounds all below the parent's only with it (profiles/poisson_groups).
+__global__ void __launch_bounds__(kPoissonGroupPix) __attribute__((amdgpu_waves_per_eu(5))) k_poisson_groups(PoissonGroupParams<T> p) {
+    __shared__ __attribute__((aligned(8))) unsigned char lds[kPoissonGroupLds];
+    poisson_groups_body<T>(p, threadIdx.x, blockIdx.x, gridDim.x, lds, PoissonSync{});
 }
 
 // ---- host <-> plan staging: float64 host arrays are converted on the device -----------
@@ -306,7 +294,7 @@ hipError_t aux_box_norm(int dtype, const double* integral_dev, void* out, int V,
 hipError_t aux_poisson(int dtype, const void* noiseless, void* noisy, unsigned n_pix, unsigned n_img, unsigned image0,
                        unsigned long long seed, int rng_kind, void* list_ws, hipStream_t s,
                        const unsigned long long* frame_seeds, const unsigned* frame_ids, unsigned V, const unsigned* rate_frame,
-                       unsigned grid_cap) {
+                       unsigned grid_cap, bool groups) {
     (void)list_ws;   // (rounds 1-3: the global work list between the two launches)
     const PoissonKeys keys{seed, image0, V ? V : 1u, frame_seeds, frame_ids, rate_frame};
     const size_t total = (size_t)n_pix * n_img;
@@ -315,6 +303,13 @@ hipError_t aux_poisson(int dtype, const void* noiseless, void* noisy, unsigned n
     const size_t tiles = (total + kPoissonTile - 1) / kPoissonTile;
     const size_t cap = grid_cap < 1 ? 1 : grid_cap > kPoissonGrid ? kPoissonGrid : grid_cap;
     const unsigned g = (unsigned)(tiles > cap ? cap : tiles);
+    if (aux_poisson_groups(groups, rng_kind, rate_frame != nullptr)) {   // a sharing slice
+        const unsigned items = poisson_group_items(n_pix, n_img / keys.V, keys.V);
+        const unsigned gg = (unsigned)(items > cap ? cap : items);
+        if (dtype == DT_F32) k_poisson_groups<float><<<gg, kPoissonGroupPix, 0, s>>>(PoissonGroupParams<float>{(const float*)noiseless, (float*)noisy, n_pix, n_img / keys.V, keys});
+        else k_poisson_groups<double><<<gg, kPoissonGroupPix, 0, s>>>(PoissonGroupParams<double>{(const double*)noiseless, (double*)noisy, n_pix, n_img / keys.V, keys});
+        return hipGetLastError();
+    }
     const bool tile_img = n_pix % (unsigned)kPoissonTile == 0;
     auto launch = [&](auto zero, auto in_image) {
         using T = decltype(zero);

@@ -54,11 +54,15 @@ size_t aux_poisson_workspace_bytes(size_t total_pixels);
 // counters stay those of the frame itself, so every draw is the one it would be from a copy of the rates.
 // grid_cap: at most so many workgroups (1 .. kPoissonGrid).  The tiles are walked with a grid stride and a value is a function of
 // (seed, image, pixel) alone: a launch of any width writes the same bits -- a narrow one leaves the chip to the kernels beside it.
+// groups: a launch with rate_frame and the Philox generator (aux_poisson_groups) draws through k_poisson_groups -- frame groups
+// per pixel tile, the sampler's rate-only set-up once per pixel and run of frames with one rate image (poisson_kernels.hpp) --,
+// the same bits; every other launch, and every launch with groups == false, through k_poisson.
 constexpr unsigned kPoissonGrid = 4096;
+inline bool aux_poisson_groups(bool groups, int rng_kind, bool rate_frame) { return groups && rate_frame && rng_kind == 1; }
 hipError_t aux_poisson(int dtype, const void* noiseless, void* noisy, unsigned n_pix, unsigned n_img, unsigned image0,
                        unsigned long long seed, int rng_kind, void* list_ws, hipStream_t s,
                        const unsigned long long* frame_seeds = nullptr, const unsigned* frame_ids = nullptr, unsigned V = 1,
-                       const unsigned* rate_frame = nullptr, unsigned grid_cap = kPoissonGrid);
+                       const unsigned* rate_frame = nullptr, unsigned grid_cap = kPoissonGrid, bool groups = true);
 // float64 stack [frames][n] (device) -> plan dtype, each frame scaled to sum target[f]
 // Every `sums` argument below is device memory of aux_sums_elems(frames) doubles: the frames' sums, then scratch for the partial
 // sums of large frames (aux_kernels.hip frame_sums).

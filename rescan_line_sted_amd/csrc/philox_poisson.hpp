@@ -133,6 +133,68 @@ RL_HD double det_logfact(double k) {
     return ((x - 0.5) * det_log(x) - x) + 0.9189385332046727 + c * xi;
 }
 
+// ---- PTRS (lam >= 10) in pieces: what depends on the rate alone, one candidate from one Philox block, the acceptance test.
+// philox_poisson_fast(), philox_ptrs_attempt() and philox_poisson() below are these pieces in a row; a kernel that draws many
+// frames from one rate image (poisson_kernels.hpp) evaluates the rate-only pieces once per pixel and the others per frame.  Every
+// piece is a deterministic function of its arguments: where it is evaluated, and how often, changes no bit.
+struct PtrsRate {   // the set-up of every attempt
+    double lam, b, a, vr;
+};
+RL_HD PtrsRate ptrs_rate(double lam) {
+    RL_FP_STRICT
+    PtrsRate r;
+    const double slam = __builtin_sqrt(lam);
+    r.lam = lam;
+    r.b = 0.931 + 2.53 * slam;
+    r.a = -0.059 + 0.02483 * r.b;
+    r.vr = 0.9277 - 3.6224 / (r.b - 2.0);
+    return r;
+}
+struct PtrsSlow {   // the rate-only values of the logarithm test: log(lam), log(invalpha)
+    double loglam, log_invalpha;
+};
+RL_HD PtrsSlow ptrs_slow(const PtrsRate& r) {
+    RL_FP_STRICT
+    PtrsSlow s;
+    const double invalpha = 1.1239 + 1.1328 / (r.b - 3.4);
+    s.loglam = det_log(r.lam);
+    s.log_invalpha = det_log(invalpha);
+    return s;
+}
+struct PtrsCandidate {
+    double U, V, us, k;
+};
+RL_HD Philox4 ptrs_block(uint32_t k0, uint32_t k1, uint32_t image, uint32_t pixel, uint32_t blk) {
+    return philox4x32_10(pixel, image, blk, 0x504F4953u, k0, k1);
+}
+RL_HD PtrsCandidate ptrs_candidate(const PtrsRate& r, const Philox4& o) {
+    RL_FP_STRICT
+    PtrsCandidate c;
+    c.U = u53(o.x[0], o.x[1]) - 0.5;
+    c.V = u53(o.x[2], o.x[3]);
+    c.us = 0.5 - (c.U < 0.0 ? -c.U : c.U);
+    c.k = __builtin_floor((2.0 * r.a / c.us + r.b) * c.U + r.lam + 0.43);
+    return c;
+}
+// the squeeze: ~87 % of candidates are accepted here, without a logarithm
+RL_HD bool ptrs_squeeze(const PtrsRate& r, const PtrsCandidate& c) {
+    RL_FP_STRICT
+    return c.us >= 0.07 && c.V <= r.vr;
+}
+// The whole acceptance test of a candidate.  slow() yields the PtrsSlow of r and is called only where the logarithm test is
+// reached: computed on the spot (philox_ptrs_attempt) or read from a table, the values are the same.
+template <class Slow>
+RL_HD bool ptrs_accept(const PtrsRate& r, const PtrsCandidate& c, Slow slow) {
+    RL_FP_STRICT
+    if (ptrs_squeeze(r, c)) return true;                                  // ~87 % of attempts leave here
+    if (c.k < 0.0 || (c.us < 0.013 && c.V > c.us)) return false;
+    if (!(c.V > 0.0)) return true;
+    const PtrsSlow s = slow();
+    const double lhs = (det_log(c.V) + s.log_invalpha) - det_log(r.a / (c.us * c.us) + r.b);
+    const double rhs = (c.k * s.loglam - r.lam) - det_logfact(c.k);
+    return lhs <= rhs;
+}
+
 // First attempt only (block 0) for lam >= 10: returns true and the variate when the
 // PTRS squeeze accepts it (~87 % of pixels), false when the pixel needs the full
 // sampler.  Exactly the first loop trip of philox_poisson(), so a pixel finished
@@ -144,18 +206,10 @@ RL_HD bool philox_poisson_fast(double lam, uint64_t seed, uint32_t image, uint32
         return true;
     }
     if (lam < 10.0) return false;
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    const double slam = __builtin_sqrt(lam);
-    const double b = 0.931 + 2.53 * slam;
-    const double a = -0.059 + 0.02483 * b;
-    const double vr = 0.9277 - 3.6224 / (b - 2.0);
-    const Philox4 o = philox4x32_10(pixel, image, 0u, 0x504F4953u, k0, k1);
-    const double U = u53(o.x[0], o.x[1]) - 0.5;
-    const double V = u53(o.x[2], o.x[3]);
-    const double us = 0.5 - (U < 0.0 ? -U : U);
-    const double k = __builtin_floor((2.0 * a / us + b) * U + lam + 0.43);
-    *out = k;
-    return us >= 0.07 && V <= vr;
+    const PtrsRate r = ptrs_rate(lam);
+    const PtrsCandidate c = ptrs_candidate(r, ptrs_block((uint32_t)seed, (uint32_t)(seed >> 32), image, pixel, 0u));
+    *out = c.k;
+    return ptrs_squeeze(r, c);
 }
 
 // One PTRS attempt (lam >= 10) with Philox block `blk`: returns true when the candidate *kout is accepted.
@@ -163,25 +217,11 @@ RL_HD bool philox_poisson_fast(double lam, uint64_t seed, uint32_t image, uint32
 // that the pixels still undecided can be repacked densely between attempts.
 RL_HD bool philox_ptrs_attempt(double lam, uint32_t k0, uint32_t k1, uint32_t image, uint32_t pixel, uint32_t blk, double* kout) {
     RL_FP_STRICT
-    const double slam = __builtin_sqrt(lam);
-    const double b = 0.931 + 2.53 * slam;
-    const double a = -0.059 + 0.02483 * b;
-    const double vr = 0.9277 - 3.6224 / (b - 2.0);
-    const Philox4 o = philox4x32_10(pixel, image, blk, 0x504F4953u, k0, k1);
-    const double U = u53(o.x[0], o.x[1]) - 0.5;
-    const double V = u53(o.x[2], o.x[3]);
-    const double us = 0.5 - (U < 0.0 ? -U : U);
-    const double k = __builtin_floor((2.0 * a / us + b) * U + lam + 0.43);
-    *kout = k;
-    if (us >= 0.07 && V <= vr) return true;                      // ~87 % of attempts leave here
-    if (k < 0.0 || (us < 0.013 && V > us)) return false;
-    if (!(V > 0.0)) return true;
-    // slow path: the logarithms are evaluated only here (same values as if hoisted)
-    const double invalpha = 1.1239 + 1.1328 / (b - 3.4);
-    const double loglam = det_log(lam);
-    const double lhs = (det_log(V) + det_log(invalpha)) - det_log(a / (us * us) + b);
-    const double rhs = (k * loglam - lam) - det_logfact(k);
-    return lhs <= rhs;
+    const PtrsRate r = ptrs_rate(lam);
+    const PtrsCandidate c = ptrs_candidate(r, ptrs_block(k0, k1, image, pixel, blk));
+    *kout = c.k;
+    // slow path: the logarithms are evaluated only there (same values as if hoisted)
+    return ptrs_accept(r, c, [&r]() { return ptrs_slow(r); });
 }
 
 constexpr uint32_t kPoissonMaxBlocks = 64;   // attempts per pixel, then the last candidate is taken

@@ -85,6 +85,10 @@ struct PlanOptions {
     // 52 - 59 ms (DESIGN.md section 4 "Draws ahead", profiles/draw_ahead).  Grid, same tables: 64 .. 512 within 0.2 ms of each other.
     bool draw_ahead = false;
     int draw_grid = 128;
+    // RLSTED_POISSON_GROUPS=0: k_poisson for every draw; unset: a sharing slice's Philox draw runs k_poisson_groups, which evaluates
+    // the sampler's rate-only set-up once per pixel and group of 8 frames instead of once per frame (poisson_kernels.hpp; the same
+    // bits; DESIGN.md section 4 "Frame groups", profiles/poisson_groups)
+    bool poisson_groups = true;
     bool inplace = true;         // RLSTED_INPLACE=0: single-view RL iterations spec_a -> spec_b -> spec_a instead of entirely in spec_a
     // RLSTED_COL_ORDER: column kernel work order, images per block of the tile order (fft_kernels.hip k_colconv):
     // 1 image-major ... >= images per launch: tile-major.  Measured at 512^2, 32-frame
@@ -127,6 +131,7 @@ PlanOptions plan_options(int dtype, int n_psf) {
     o.lanes = std::min(std::max(number("RLSTED_LANES", o.lanes), 1), kMaxLanes);
     o.draw_ahead = flag("RLSTED_DRAW_AHEAD", o.draw_ahead);
     o.draw_grid = std::min(std::max(number("RLSTED_DRAW_GRID", o.draw_grid), 1), (int)kPoissonGrid);
+    o.poisson_groups = flag("RLSTED_POISSON_GROUPS", o.poisson_groups);
     o.inplace = flag("RLSTED_INPLACE", o.inplace);
     o.col_order = std::max(number("RLSTED_COL_ORDER", o.col_order), 1);
     o.pair = flag("RLSTED_PAIR", dtype == RL_F32 && n_psf == 1);
@@ -981,6 +986,7 @@ struct rl_deconv {
     int last_sim_images = 0;               // images H was computed for in the last cycle (rl_deconv_simulated_images)
     bool noiseless_sparse = false;         // the last simulation left (some) slices' rates in noiseless_c only
     int last_shared_slices = 0, last_slices = 0;
+    int grouped_draws = 0, last_grouped_draws = 0;   // slices of this / the last cycle that drew through k_poisson_groups (rl_deconv_grouped_draws)
     int last_draws_ahead = 0;              // slices of the last cycle whose draw went to the context's stream (rl_deconv_draws_ahead)
     bool share_possible() const { return opt.share_objects && !sep && (int)obj_class.size() == B && n_classes < B; }
     // The layout for slices of cf frames from obj_class, on the host: share_slices and the two lists.  Returns the compact images.
@@ -1121,7 +1127,9 @@ struct rl_deconv {
         const hipError_t e = aux_poisson(dtype, shared ? noiseless_c : off(noiseless, (size_t)f0 * V * n_img()), off(meas, (size_t)f0 * V * n_img()),
                                          (unsigned)n_img(), (unsigned)(nf * V), (unsigned)(f0 * V), d.seed, d.rng_kind, ws, cur(),
                                          d.key_seeds ? d.key_seeds + f0 : nullptr, d.key_ids ? d.key_ids + f0 : nullptr, (unsigned)V,
-                                         shared ? share_lists.rate_of + f0 : nullptr, ahead ? (unsigned)opt.draw_grid : (unsigned)kPoissonGrid);
+                                         shared ? share_lists.rate_of + f0 : nullptr, ahead ? (unsigned)opt.draw_grid : (unsigned)kPoissonGrid,
+                                         opt.poisson_groups);
+        if (aux_poisson_groups(opt.poisson_groups, d.rng_kind, shared)) ++grouped_draws;
         return e == hipSuccess ? RL_OK : fail(RL_ERR_HIP, std::string("Poisson kernels: ") + hipGetErrorString(e));
     }
     // (start the estimate of a slice and) its k iterations, with their checkpoints
@@ -1197,6 +1205,7 @@ struct rl_deconv {
             ~ActiveGuard() { a = nullptr; }
         } active_guard{active};
         const Run run{k, restart, draw, cp, cf};
+        grouped_draws = 0;
         int rc = RL_OK;   // the first failure: no further work is enqueued behind it, the join is
         for (const StreamOp& op : schedule.ops) {
             if (rc != RL_OK && !op.join) continue;
@@ -1214,6 +1223,7 @@ struct rl_deconv {
         cycle_state = schedule.after;
         if (draw) {
             last_draws_ahead = schedule.draws_ahead;
+            last_grouped_draws = grouped_draws;
             noiseless_sparse = schedule.shared_slices > 0;
             last_shared_slices = schedule.shared_slices;
             last_slices = schedule.slices;
@@ -1923,6 +1933,12 @@ int rl_deconv_object_classes(const rl_deconv* h, int* classes, int* shared_slice
 int rl_deconv_draws_ahead(const rl_deconv* h, int* slices) {
     if (!h || !slices) return fail(RL_ERR_INVALID, "NULL argument");
     *slices = h->last_draws_ahead;
+    return RL_OK;
+}
+
+int rl_deconv_grouped_draws(const rl_deconv* h, int* slices) {
+    if (!h || !slices) return fail(RL_ERR_INVALID, "NULL argument");
+    *slices = h->last_grouped_draws;
     return RL_OK;
 }
 
