@@ -71,6 +71,15 @@ int rl_fft_length_for(int n);
  * (:589-592), which is computed here once.                                   */
 int rl_deconv_create(rl_ctx* ctx, const double* psfs, int n_psf, int py, int px,
                      int batch, int ny, int nx, int dtype, rl_deconv** out);
+/* rl_deconv_create with the plan's switches as an argument.  options: NULL, or a NUL-terminated text of NAME=value entries
+ * separated by whitespace; the names are the RLSTED_* environment variables' own, e.g.
+ * "RLSTED_PAIR=0 RLSTED_LANES=1".  A switch is taken from options; one that options does not name from the environment; one that
+ * neither names has its default.  rl_deconv_create(...) is rl_deconv_create_with(..., NULL, out).
+ * RL_ERR_INVALID, with the offender named in rl_last_error and no plan created: an entry without '=', with an empty name or an
+ * empty value, a name given twice, and a name that is no switch of a plan (a misspelt one, or the process-wide
+ * RLSTED_DEBUG_SYNC).  Variables of the environment that are no switch stay ignored.                                          */
+int rl_deconv_create_with(rl_ctx* ctx, const double* psfs, int n_psf, int py, int px,
+                          int batch, int ny, int nx, int dtype, const char* options, rl_deconv** out);
 int rl_deconv_destroy(rl_deconv* h);
 
 /* Geometry chosen by the plan: ly, lx transform lengths, pitch of spectra. */

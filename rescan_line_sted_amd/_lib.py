@@ -55,6 +55,7 @@ PROTOTYPES = {
     'rl_ctx_synchronize': (_i, [_vp]),
     'rl_fft_length_for': (_i, [_i]),
     'rl_deconv_create': (_i, [_vp, _dp, _i, _i, _i, _i, _i, _i, _i, _c.POINTER(_vp)]),
+    'rl_deconv_create_with': (_i, [_vp, _dp, _i, _i, _i, _i, _i, _i, _i, _c.c_char_p, _c.POINTER(_vp)]),
     'rl_deconv_destroy': (_i, [_vp]),
     'rl_deconv_info': (_i, [_vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_c.c_size_t)]),
     'rl_deconv_set_object': (_i, [_vp, _dp, _dp]),
@@ -253,9 +254,13 @@ def common_psf_shape(psfs):
 class DeconvPlan:
     """rl_deconv: `batch` frames sharing one PSF set and one image shape."""
 
-    def __init__(self, psfs, batch, ny, nx, dtype='f32', device=0, stream=0, acceleration=None, tv_lambda=None, tv_epsilon=0.1):
+    def __init__(self, psfs, batch, ny, nx, dtype='f32', device=0, stream=0, acceleration=None, tv_lambda=None, tv_epsilon=0.1,
+                 options=None):
         """acceleration: None (plain Richardson-Lucy, the reference's iteration) or 'biggs-andrews' (set_acceleration).
-        tv_lambda: None (no regulariser) or the weight of the total-variation step, tv_epsilon its relative smoothing (set_tv)."""
+        tv_lambda: None (no regulariser) or the weight of the total-variation step, tv_epsilon its relative smoothing (set_tv).
+        options: the plan's switches, {name: value} under the RLSTED_* environment variables' own names (values go through str());
+        a switch that is not named is read from the environment (include/rlsted.h rl_deconv_create_with, whose text form -- a
+        str of NAME=value entries -- is accepted as well)."""
         mode = accel_mode(acceleration)
         tv = tv_params(tv_lambda, tv_epsilon)
         psfs = [as_f64(p) for p in psfs]
@@ -269,8 +274,10 @@ class DeconvPlan:
         self.B, self.ny, self.nx = int(batch), int(ny), int(nx)
         self.dtype = dtype
         self.handle = _vp()
-        check(lib.rl_deconv_create(self.ctx.handle, ptr(self.psf_stack), self.V, self.py, self.px,
-                                   self.B, self.ny, self.nx, DTYPES[dtype], ctypes.byref(self.handle)))
+        self.options = options if isinstance(options, str) else dict(options or {})
+        text = self.options if isinstance(options, str) else ' '.join('%s=%s' % (k, v) for k, v in self.options.items())
+        check(lib.rl_deconv_create_with(self.ctx.handle, ptr(self.psf_stack), self.V, self.py, self.px,
+                                        self.B, self.ny, self.nx, DTYPES[dtype], text.encode() or None, ctypes.byref(self.handle)))
         self.acceleration = None
         if mode:
             self.set_acceleration(acceleration)

@@ -147,7 +147,7 @@ inline void cycle_schedule(const CycleInputs& in, CycleSchedule& out) {
     const bool share = in.draws && in.share;
     auto shares = [&](int sl) { return share && in.share_slices[sl].nrep > 0; };
     auto lane_stream = [&](int sl) { return nl > 1 ? sl % nl : kCtxStream; };
-    // Draws ahead (RLSTED_DRAW_AHEAD=1; what it measured and why it is off by default: rlsted.cpp PlanOptions).  The sampler is
+    // Draws ahead (RLSTED_DRAW_AHEAD=1; what it measured and why it is off by default: plan_options.hpp PlanOptions).  The sampler is
     // bound by vector issue, the RL kernels by the memory system, yet a slice's full-width draw at the head of its lane floods
     // every SIMD and the other lane's loop all but stops beside it.  So the draw of a SHARING slice sl -- it reads the class rates
     // only -- goes to the context's stream, a capped number of workgroups wide, behind the "begun" event of the slice IN FRONT of

@@ -22,6 +22,7 @@
 #include "cycle_schedule.hpp"
 #include "kernel_table.hpp"
 #include "object_classes.hpp"
+#include "plan_options.hpp"
 #include "ctx.hpp"
 #include "sep_kernels.hpp"
 #include "sep_taps.hpp"
@@ -66,89 +67,6 @@ const KernelTable* table_for(int L) {
 const int kLengths[] = {64, 192, 256, 576, 1152, 2304, 4608};
 
 size_t esize(int dtype) { return dtype == RL_F32 ? 4 : 8; }
-
-// Every RLSTED_* switch of a plan (RLSTED_DEBUG_SYNC is process wide: rl::debug_sync; RLSTED_SEP_TH: sep_kernels.hip).  Read once,
-// when the plan is created; nothing after plan_options() looks at the environment.  The defaults are the measured optimum.
-struct PlanOptions {
-    // ---- schedule
-    bool chunk_mb_set = false;   // RLSTED_CHUNK_MB: working set of one batch slice in MB; unset: 108 (one lane: 288) and the
-    double chunk_mb = 0;         //   rules of chunk_frames() that only apply when no budget was given
-    // Slices of the batch are independent: they are iterated on `lanes` HIP streams at once so that
-    // the tail of one slice's kernel (the last, partly filled round of workgroups) overlaps another
-    // slice's kernels.  RLSTED_LANES=1: one slice after the other on the context's stream (at most kMaxLanes).
-    int lanes = 2;
-    // RLSTED_DRAW_AHEAD=1: a sharing slice's Poisson draw goes to the context's stream -- idle while the lanes run --, one slice
-    // per lane ahead of the loops and RLSTED_DRAW_GRID workgroups wide (at most aux_kernels.hpp kPoissonGrid), beside the loop of
-    // the slice in front (cycle_schedule.hpp); unset: every slice draws at the head of its lane.  OFF by default: bench.py's
-    // lone plan gains nothing (46.44 ms off, 46.59 ms on, four alternating runs each), plans in a crowded process 0.4 - 0.7 ms --
-    // unless the context's stream shares a hardware queue with a lane (8 plans on 4 queues), where the same cycle takes
-    // 52 - 59 ms (DESIGN.md section 4 "Draws ahead", profiles/draw_ahead).  Grid, same tables: 64 .. 512 within 0.2 ms of each other.
-    bool draw_ahead = false;
-    int draw_grid = 128;
-    // RLSTED_POISSON_GROUPS=0: k_poisson for every draw; unset: a sharing slice's Philox draw runs k_poisson_groups, which evaluates
-    // the sampler's rate-only set-up once per pixel and group of 8 frames instead of once per frame (poisson_kernels.hpp; the same
-    // bits; DESIGN.md section 4 "Frame groups", profiles/poisson_groups)
-    bool poisson_groups = true;
-    bool inplace = true;         // RLSTED_INPLACE=0: single-view RL iterations spec_a -> spec_b -> spec_a instead of entirely in spec_a
-    // RLSTED_COL_ORDER: column kernel work order, images per block of the tile order (fft_kernels.hip k_colconv):
-    // 1 image-major ... >= images per launch: tile-major.  Measured at 512^2, 32-frame
-    // slices: 1: 16.80 k, 2: 16.88 k, 4: 16.98 k, 8: 16.81 k, 32: 16.56 k frames/s.
-    int col_order = 4;
-    bool pair = false;           // RLSTED_PAIR: frame pairs in the RL loop; unset: single-view f32 plans (deconv_build)
-    double pair_max_ratio = 4.0; // RLSTED_PAIR_MAX_RATIO: largest level ratio inside a pair (rl_deconv::levels_ok)
-    // ---- arithmetic (each identical in exact arithmetic)
-    bool sub_one = false;        // RLSTED_SUB_ONE: the second half of every iteration on `ratio - 1`; unset: f32 plans of the product build
-    int fuse_views = -1;         // RLSTED_FUSE_VIEWS: -1 unset (H_t views summed in the Fourier domain on f32 plans, not on f64), 0 / 1 as
-                                 //   given; 0 also asks for the reference's per-view clamp, which `ratio - 1` cannot give (rl_deconv_create)
-    bool col_split = true;       // RLSTED_COL_SPLIT=0: no split column pass (rl_deconv::col_split)
-    bool real_psf = true;        // RLSTED_REAL_PSF=0: keep the complex multiplier for real PSF spectra
-    bool ones_shortcut = true;   // RLSTED_ONES_SHORTCUT=0: the first iteration transforms its frame of ones instead of reading spec_ones
-    bool share_objects = true;   // RLSTED_SHARE_OBJECTS=0: every frame's H(object) is computed, also of frames that carry the same object
-    // ---- strategy (deconv_build)
-    int sep = 1;                 // RLSTED_SEP: separable stencils 0 never, 1 rank-1 PSFs with py + px <= 16, 2 whenever rank 1
-    int sep_one = 1;             // RLSTED_SEP_ONE: 0 two passes, 1 one kernel up to 24 taps a side, 2 one kernel whenever the tile fits LDS
-    int direct = 1;              // RLSTED_DIRECT: direct 2-D stencil 0 never, 1 up to 49 taps, 2 whenever the tile fits LDS
-    // ---- storage-precision study builds (conv_kernels.hpp RL_SPEC_QUANT): log2 of the DC bound of an estimate-type / ratio-type spectrum
-    bool q_exp_est_set = false, q_exp_ratio_set = false;   // RLSTED_Q_EXP_EST, RLSTED_Q_EXP_RATIO
-    int q_exp_est = 14, q_exp_ratio = 14;
-};
-
-PlanOptions plan_options(int dtype, int n_psf) {
-    PlanOptions o;
-    auto flag = [](const char* name, bool unset) {
-        const char* s = getenv(name);
-        return s ? atoi(s) != 0 : unset;
-    };
-    auto number = [](const char* name, int unset, bool* set = nullptr) {
-        const char* s = getenv(name);
-        if (set) *set = s != nullptr;
-        return s ? atoi(s) : unset;
-    };
-    if (const char* s = getenv("RLSTED_CHUNK_MB")) {
-        o.chunk_mb_set = true;
-        o.chunk_mb = atof(s);
-    }
-    o.lanes = std::min(std::max(number("RLSTED_LANES", o.lanes), 1), kMaxLanes);
-    o.draw_ahead = flag("RLSTED_DRAW_AHEAD", o.draw_ahead);
-    o.draw_grid = std::min(std::max(number("RLSTED_DRAW_GRID", o.draw_grid), 1), (int)kPoissonGrid);
-    o.poisson_groups = flag("RLSTED_POISSON_GROUPS", o.poisson_groups);
-    o.inplace = flag("RLSTED_INPLACE", o.inplace);
-    o.col_order = std::max(number("RLSTED_COL_ORDER", o.col_order), 1);
-    o.pair = flag("RLSTED_PAIR", dtype == RL_F32 && n_psf == 1);
-    if (const char* s = getenv("RLSTED_PAIR_MAX_RATIO")) o.pair_max_ratio = atof(s);
-    o.sub_one = flag("RLSTED_SUB_ONE", dtype == RL_F32 && RL_SPEC_QUANT == 0);
-    if (const char* s = getenv("RLSTED_FUSE_VIEWS")) o.fuse_views = atoi(s) != 0 ? 1 : 0;
-    o.col_split = flag("RLSTED_COL_SPLIT", o.col_split);
-    o.real_psf = flag("RLSTED_REAL_PSF", o.real_psf);
-    o.ones_shortcut = flag("RLSTED_ONES_SHORTCUT", o.ones_shortcut);
-    o.share_objects = flag("RLSTED_SHARE_OBJECTS", o.share_objects);
-    o.sep = number("RLSTED_SEP", o.sep);
-    o.sep_one = number("RLSTED_SEP_ONE", o.sep_one);
-    o.direct = number("RLSTED_DIRECT", o.direct);
-    o.q_exp_est = number("RLSTED_Q_EXP_EST", o.q_exp_est, &o.q_exp_est_set);
-    o.q_exp_ratio = number("RLSTED_Q_EXP_RATIO", o.q_exp_ratio, &o.q_exp_ratio_set);
-    return o;
-}
 
 // Device temporaries of the plan set-up: freed when the scope ends, whichever way it ends (hipFree waits for the device).
 struct TempBuffers {
@@ -626,7 +544,7 @@ struct rl_deconv {
         for (int f0 = 0; f0 < frames; f0 += 65535) {
             const int n = std::min(65535, frames - f0);
             const size_t img = n_img() * esize(dtype), in_off = (size_t)f0 * (multi ? V : 1) * img, out_off = (size_t)f0 * (multi ? 1 : V) * img;
-            HIP_TRY(sep2d(dtype, mode, (const char*)in + in_off, sep_uf, sep_vf, aux ? (const char*)aux + out_off : nullptr, nrm,
+            HIP_TRY(sep2d(dtype, opt.sep_th, mode, (const char*)in + in_off, sep_uf, sep_vf, aux ? (const char*)aux + out_off : nullptr, nrm,
                           (char*)dst + out_off, n, ny, nx, py, px, V, cur()));
         }
         return RL_OK;
@@ -1472,7 +1390,7 @@ static int deconv_build(rl_deconv* h, const double* psfs) {
             // RLSTED_SEP_ONE: 0 two passes, 1 (default) one kernel up to 24 taps a side (beyond, the two-pass form is
             // faster: profiles/r02/separable_vs_fft.json), 2 one kernel whenever the tile fits LDS
             const bool want_one = h->opt.sep_one >= 2 || (h->opt.sep_one == 1 && std::max(py, px) <= 24);
-            if (want_one && sep2d_fits(h->dtype, h->py, h->px, (int)V)) {
+            if (want_one && sep2d_fits(h->dtype, h->opt.sep_th, h->py, h->px, (int)V)) {
                 std::vector<double> uf, vf;
                 sep_flipped_taps(u, vv, V, py, px, uf, vf);
                 RL_TRY(h->upload_taps(&h->sep_uf, uf));
@@ -1497,7 +1415,7 @@ static int deconv_build(rl_deconv* h, const double* psfs) {
     {
         const int direct_mode = h->opt.direct;
         if (!h->sep && sep_mode > 0 && direct_mode > 0 && (direct_mode > 1 || h->py * h->px <= 49) && h->py * h->px <= 1024 &&
-            direct2d_fits(h->dtype, h->py, h->px, (int)V)) {
+            direct2d_fits(h->dtype, h->opt.sep_th, h->py, h->px, (int)V)) {
             std::vector<double> f;
             sep_direct_taps(psfs, V, h->py, h->px, f);
             RL_TRY(h->upload_taps(&h->sep_uf, f));
@@ -1547,16 +1465,26 @@ static int deconv_build(rl_deconv* h, const double* psfs) {
 
 int rl_deconv_create(rl_ctx* ctx, const double* psfs, int n_psf, int py, int px, int batch, int ny, int nx, int dtype,
                      rl_deconv** out) {
+    return rl_deconv_create_with(ctx, psfs, n_psf, py, px, batch, ny, nx, dtype, nullptr, out);
+}
+
+int rl_deconv_create_with(rl_ctx* ctx, const double* psfs, int n_psf, int py, int px, int batch, int ny, int nx, int dtype,
+                          const char* options, rl_deconv** out) {
     if (!ctx || !psfs || !out) return fail(RL_ERR_INVALID, "NULL argument");
     *out = nullptr;
     if (n_psf < 1 || py < 1 || px < 1 || batch < 1 || ny < 1 || nx < 1) return fail(RL_ERR_INVALID, "non-positive size");
     if (dtype != RL_F32 && dtype != RL_F64) return fail(RL_ERR_INVALID, "dtype must be RL_F32 or RL_F64");
     if (n_psf > rl_deconv::kMaxGridY) return fail(RL_ERR_UNSUPPORTED, "more than 65535 views");
+    OptionLookup lookup;
+    std::string bad;
+    if (!lookup.parse(options, &bad)) return fail(RL_ERR_INVALID, bad);
+    const PlanOptions opt = plan_options(lookup, dtype, n_psf, (int)kPoissonGrid, RL_SPEC_QUANT);
+    if (const std::string* name = lookup.unasked()) return fail(RL_ERR_INVALID, "option '" + *name + "' is no switch of a plan");
     HIP_TRY(hipSetDevice(ctx->device));
     rl_deconv* h = new rl_deconv;
     h->ctx = ctx;
     h->V = n_psf; h->py = py; h->px = px; h->B = batch; h->ny = ny; h->nx = nx; h->dtype = dtype;
-    h->opt = plan_options(dtype, n_psf);
+    h->opt = opt;
     if (h->opt.q_exp_est_set) h->q_est = std::ldexp(1.0f, 14 - h->opt.q_exp_est);
     if (h->opt.q_exp_ratio_set) h->q_ratio = std::ldexp(1.0f, 14 - h->opt.q_exp_ratio);
     h->fuse_views = h->opt.fuse_views < 0 ? dtype == RL_F32 : h->opt.fuse_views != 0;

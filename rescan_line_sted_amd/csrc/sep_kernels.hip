@@ -17,8 +17,6 @@
 #include <mutex>
 #include <set>
 
-#include <cstdlib>
-
 #include "sep_kernels.hpp"
 
 namespace rl {
@@ -141,29 +139,25 @@ hipError_t sep_cols(int dtype, int mode, const void* tmp, const void* taps_u, co
 }
 
 
-// tile height of the one-kernel form: RLSTED_SEP_TH (32 or 64) for float, 32 for double
-static int sep_th32() {
-    static const int th = getenv("RLSTED_SEP_TH") ? atoi(getenv("RLSTED_SEP_TH")) : 32;
-    return th == 64 ? 64 : 32;
-}
-static int sep_th(int dtype) { return dtype == DT_F32 ? sep_th32() : 32; }
+// th: the tile height of the one-kernel form, the plan's (plan_options.hpp sep_th): 32 or 64 for float, 32 for double
 static size_t sep_esize(int dtype) { return dtype == DT_F32 ? 4 : 8; }
-bool sep2d_fits(int dtype, int py, int px, int V) { return sep2d_fits_tile(sep_esize(dtype), sep_th(dtype), py, px, V); }
-bool direct2d_fits(int dtype, int py, int px, int V) { return direct2d_fits_tile(sep_esize(dtype), sep_th(dtype), py, px, V); }
+bool sep2d_fits(int dtype, int th, int py, int px, int V) { return sep2d_fits_tile(sep_esize(dtype), th, py, px, V); }
+bool direct2d_fits(int dtype, int th, int py, int px, int V) { return direct2d_fits_tile(sep_esize(dtype), th, py, px, V); }
 bool sep_two_pass_fits(int dtype, int py, int px) { return sep_two_pass_fits_esize(sep_esize(dtype), py, px); }
-hipError_t sep2d(int dtype, int mode, const void* in, const void* taps_uf, const void* taps_vf, const void* aux, const void* norm,
+hipError_t sep2d(int dtype, int th, int mode, const void* in, const void* taps_uf, const void* taps_vf, const void* aux, const void* norm,
                  void* dst, int frames, int ny, int nx, int py, int px, int V, hipStream_t s) {
     if (frames < 1) return hipSuccess;
+    if (th != 32 && !(th == 64 && dtype == DT_F32)) return hipErrorInvalidValue;
     if (taps_vf == nullptr) {   // the direct 2-D stencil: taps_uf = [V][px][8 * ceil(py / 8)]
-        if (frames > 65535 || !direct2d_fits(dtype, py, px, V)) return hipErrorInvalidValue;
+        if (frames > 65535 || !direct2d_fits(dtype, th, py, px, V)) return hipErrorInvalidValue;
         if (dtype != DT_F32) return sep2d_t<double, 32, true>(mode, in, taps_uf, nullptr, aux, norm, dst, frames, ny, nx, py, px, V, s);
-        return sep_th32() == 64 ? sep2d_t<float, 64, true>(mode, in, taps_uf, nullptr, aux, norm, dst, frames, ny, nx, py, px, V, s)
-                                : sep2d_t<float, 32, true>(mode, in, taps_uf, nullptr, aux, norm, dst, frames, ny, nx, py, px, V, s);
+        return th == 64 ? sep2d_t<float, 64, true>(mode, in, taps_uf, nullptr, aux, norm, dst, frames, ny, nx, py, px, V, s)
+                        : sep2d_t<float, 32, true>(mode, in, taps_uf, nullptr, aux, norm, dst, frames, ny, nx, py, px, V, s);
     }
-    if (frames > 65535 || !sep2d_fits(dtype, py, px, V)) return hipErrorInvalidValue;
+    if (frames > 65535 || !sep2d_fits(dtype, th, py, px, V)) return hipErrorInvalidValue;
     if (dtype != DT_F32) return sep2d_t<double, 32>(mode, in, taps_uf, taps_vf, aux, norm, dst, frames, ny, nx, py, px, V, s);
-    return sep_th32() == 64 ? sep2d_t<float, 64>(mode, in, taps_uf, taps_vf, aux, norm, dst, frames, ny, nx, py, px, V, s)
-                            : sep2d_t<float, 32>(mode, in, taps_uf, taps_vf, aux, norm, dst, frames, ny, nx, py, px, V, s);
+    return th == 64 ? sep2d_t<float, 64>(mode, in, taps_uf, taps_vf, aux, norm, dst, frames, ny, nx, py, px, V, s)
+                    : sep2d_t<float, 32>(mode, in, taps_uf, taps_vf, aux, norm, dst, frames, ny, nx, py, px, V, s);
 }
 
 }  // namespace rl

@@ -305,14 +305,15 @@ hipError_t sep_cols(int dtype, int mode, const void* tmp, const void* taps_u, co
                     int frames_or_images, int ny, int nx, int py, int V, hipStream_t s);
 // Both passes in one kernel (input tile + halo in LDS).  taps_uf / taps_vf: [V][8*ceil(py/8)] / [V][8*ceil(px/8)],
 // FLIPPED (f[k] = taps[n-1-k]) and zero padded (sep_taps.hpp).  STORE / RATIO: in [frames], dst [frames*V]; SUM / UPDATE: in
-// [frames*V], dst [frames].  sep2d_fits: the tile fits the 160 KB of LDS at this process's tile height (RLSTED_SEP_TH).
-bool sep2d_fits(int dtype, int py, int px, int V);
+// [frames*V], dst [frames].  th: the tile height, the plan's (plan_options.hpp sep_th: 32, or 64 on a float plan; anything else
+// is an error).  sep2d_fits: the tile fits the 160 KB of LDS at height th.
+bool sep2d_fits(int dtype, int th, int py, int px, int V);
 // the direct 2-D stencil for PSFs that are not rank 1 (sep2d with taps_vf == nullptr, taps_uf = [V][px][8*ceil(py/8)]:
 // F[l][k] = p[py-1-k][px-1-l], zero padded along k): the input tile and the taps fit LDS
-bool direct2d_fits(int dtype, int py, int px, int V);
+bool direct2d_fits(int dtype, int th, int py, int px, int V);
 // the two-pass form (sep_rows + sep_cols) fits LDS: py up to 609 taps in f32, 289 in f64 (the plan falls back to the FFT path beyond)
 bool sep_two_pass_fits(int dtype, int py, int px);
-hipError_t sep2d(int dtype, int mode, const void* in, const void* taps_uf, const void* taps_vf, const void* aux, const void* norm,
+hipError_t sep2d(int dtype, int th, int mode, const void* in, const void* taps_uf, const void* taps_vf, const void* aux, const void* norm,
                  void* dst, int frames, int ny, int nx, int py, int px, int V, hipStream_t s);
 #endif
 }  // namespace rl

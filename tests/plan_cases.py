@@ -40,6 +40,17 @@ def _case(name, row, B, ny, nx, psf, seed, env=None, env32=None, want32=None, wa
             'levels': levels, 'written': written, 'twin': twin, 'slices': slices}
 
 
+def plans_per_value(lib, psfs, B, ny, nx, dtype, switch, values=('0', '1'), options=None, fft_only=False):
+    """One plan per value of `switch`, alive side by side, each with `options` besides (DeconvPlan's options; a value of None: the
+    switch is not given, the plan has its default).  fft_only: no stencil may have taken the PSF set."""
+    out = [lib.DeconvPlan(psfs, B, ny, nx, dtype=dtype, options=dict(options or {}, **({} if v is None else {switch: v})))
+           for v in values]
+    for p in out if fft_only else []:
+        s = p.strategy()
+        assert not s['separable'] and not s['direct_stencil']
+    return out
+
+
 _NO_PAIR = {'RLSTED_PAIR': '0'}
 _FFT = {'separable': False, 'direct_stencil': False}
 _PF = dict(_FFT, frame_pairs=False)

@@ -43,8 +43,8 @@ def _noisy(psfs, obj, brightness, seed):
     return [rng.poisson(m) + 1e-9 for m in d.H(obj)]
 
 
-def _plan(psfs, B, ny, nx, dtype='f64', acceleration=BA):
-    return _lib().DeconvPlan(psfs, B, ny, nx, dtype=dtype, acceleration=acceleration)
+def _plan(psfs, B, ny, nx, dtype='f64', acceleration=BA, options=None):
+    return _lib().DeconvPlan(psfs, B, ny, nx, dtype=dtype, acceleration=acceleration, options=options)
 
 
 def _pixel_rel(a, b):
@@ -95,17 +95,15 @@ def _cases():
 
 
 @pytest.mark.parametrize('case', ['pair', 'per_frame', 'views4', 'split', 'separable', 'direct'])
-def test_f32_matches_f64_on_every_loop(case, monkeypatch):
-    psfs, n, B, K, env, want = _cases()[case]
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+def test_f32_matches_f64_on_every_loop(case):
+    psfs, n, B, K, options, want = _cases()[case]
     base = _stack(['astronaut', 'rings'])[:B]
     obj = np.stack([np.kron(o, np.ones((n // 128, n // 128))) for o in base])
-    p64 = _plan(psfs, B, n, n, 'f64')
+    p64 = _plan(psfs, B, n, n, 'f64', options=options)
     p64.set_object(obj, [5e10 * (n / 128) ** 2] * B)
     p64.simulate(seed=11)
     meas = p64.measurement()
-    p32 = _plan(psfs, B, n, n, 'f32')
+    p32 = _plan(psfs, B, n, n, 'f32', options=options)
     p32.set_measurement(meas)
     p32.iterate(K)
     p64.iterate(K)

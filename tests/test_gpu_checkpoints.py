@@ -61,7 +61,7 @@ class Buffer:
         self.res.free()
 
 
-# name: (psfs, dtype, ny, nx, batch, object pattern = the tasks, plan keywords, environment at plan creation, strategy to expect)
+# name: (psfs, dtype, ny, nx, batch, object pattern = the tasks, plan keywords, the plan's options, strategy to expect)
 CASES = {
     'f64_two_chunks_short_last': (random_psfs(1), 'f64', 48, 40, 5, 'ABCABCA', {}, {}, {'frame_pairs': False, 'separable': False}),
     # (no plan of 128 x 128 or less pairs its frames: the pair loop exists on the transforms from L = 256 on, and 200 x 200 is the size
@@ -80,13 +80,9 @@ CASES = {
 }
 
 
-def make_plan(lib, monkeypatch, case, batch=None):
-    psfs, dtype, ny, nx, B, _, kw, env, want = CASES[case]
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    plan = lib.DeconvPlan(psfs, batch or B, ny, nx, dtype=dtype, **kw)
-    for k in env:
-        monkeypatch.delenv(k)
+def make_plan(lib, case, batch=None):
+    psfs, dtype, ny, nx, B, _, kw, options, want = CASES[case]
+    plan = lib.DeconvPlan(psfs, batch or B, ny, nx, dtype=dtype, options=options, **kw)
     s = plan.strategy()
     if batch is None:
         assert {k: s[k] for k in want} == want, (case, s)
@@ -102,11 +98,11 @@ def tasks_of(case, brightness=3e6):
     return objs, brightness, seeds, ids
 
 
-def plain(lib, monkeypatch, case, K, out_dtype, slots=None):
+def plain(lib, case, K, out_dtype, slots=None):
     """rl_batch_submit with K iterations on a fresh plan: the downloaded buffer [slots][ny][nx] (sentinel behind the tasks)."""
     _, _, ny, nx, _, pattern, _, _, _ = CASES[case]
     objs, tb, seeds, ids = tasks_of(case)
-    plan = make_plan(lib, monkeypatch, case)
+    plan = make_plan(lib, case)
     buf = Buffer((slots or len(objs)) * ny * nx, out_dtype)
     plan.batch_submit(objs, tb, seeds, ids, K, buf.address, out_dtype)
     plan.ctx.synchronize()
@@ -115,14 +111,14 @@ def plain(lib, monkeypatch, case, K, out_dtype, slots=None):
     return out, plan
 
 
-def checkpoints(lib, monkeypatch, case, ks, out_dtype, outs=True, traces=True, slots=None, skip=(), plan=None, select=None):
+def checkpoints(lib, case, ks, out_dtype, outs=True, traces=True, slots=None, skip=(), plan=None, select=None):
     """rl_batch_submit_checkpoints on a fresh plan (or `plan`): ([n_k] downloaded buffers or None, [n_k][slots][6] traces or None,
     the plan).  Checkpoints listed in `skip` get NULL entries in both arrays; `select`: the indices of the case's tasks to run."""
     _, _, ny, nx, _, pattern, _, _, _ = CASES[case]
     objs, tb, seeds, ids = tasks_of(case)
     if select is not None:
         objs, seeds, ids = [objs[i] for i in select], [seeds[i] for i in select], [ids[i] for i in select]
-    plan = plan or make_plan(lib, monkeypatch, case)
+    plan = plan or make_plan(lib, case)
     slots = slots or len(objs)
     obufs = [Buffer(slots * ny * nx, out_dtype) for _ in ks] if outs else None
     tbufs = [Buffer(slots * cr.FIELDS, 'f64') for _ in ks] if traces else None
@@ -140,68 +136,68 @@ def checkpoints(lib, monkeypatch, case, ks, out_dtype, outs=True, traces=True, s
 
 # ------------------------------------------------------------------ bit equality with separate runs
 @pytest.mark.parametrize('case', sorted(CASES))
-def test_checkpoints_are_the_separate_runs(lib, monkeypatch, case):
+def test_checkpoints_are_the_separate_runs(lib, case):
     _, dtype, ny, nx, B, pattern, _, _, _ = CASES[case]
     n = len(pattern)
     slots = n + 3
-    est, tr, plan = checkpoints(lib, monkeypatch, case, KS, dtype, slots=slots)
+    est, tr, plan = checkpoints(lib, case, KS, dtype, slots=slots)
     if case == 'slices_on_two_lanes_shared_classes':
         assert plan.object_classes() == {'classes': 6, 'shared_slices': 2, 'slices': 3}
     for j, K in enumerate(KS):
-        want, _ = plain(lib, monkeypatch, case, K, dtype, slots=slots)
+        want, _ = plain(lib, case, K, dtype, slots=slots)
         assert np.all(want[n:] == SENTINEL) and np.all(want[:n] != SENTINEL)
         assert np.array_equal(est[j], want), (case, K)                 # (the untouched slots behind the tasks included)
         assert np.all(tr[j, n:] == SENTINEL) and np.all(np.isfinite(tr[j, :n]))
     # the plan is left as the plain run with the last count leaves it
-    _, plan_k = plain(lib, monkeypatch, case, KS[-1], dtype)
+    _, plan_k = plain(lib, case, KS[-1], dtype)
     assert np.array_equal(plan.estimate(), plan_k.estimate())
     assert np.array_equal(plan.measurement(), plan_k.measurement())
 
 
 @pytest.mark.parametrize('case,out_dtype', [('f64_two_chunks_short_last', 'f32'), ('f32_frame_pairs', 'f64')])
-def test_a_destination_of_the_other_type(lib, monkeypatch, case, out_dtype):
+def test_a_destination_of_the_other_type(lib, case, out_dtype):
     n = len(CASES[case][5])
-    est, _, _ = checkpoints(lib, monkeypatch, case, [2, 5], out_dtype, traces=False, slots=n + 1)
+    est, _, _ = checkpoints(lib, case, [2, 5], out_dtype, traces=False, slots=n + 1)
     for j, K in enumerate([2, 5]):
-        want, _ = plain(lib, monkeypatch, case, K, out_dtype, slots=n + 1)
+        want, _ = plain(lib, case, K, out_dtype, slots=n + 1)
         assert np.array_equal(est[j], want), (case, K)
 
 
 # ------------------------------------------------------------------ calls that must agree
 @pytest.mark.parametrize('case', ['f64_two_chunks_short_last', 'f32_frame_pairs'])
-def test_calls_that_must_agree(lib, monkeypatch, case):
+def test_calls_that_must_agree(lib, case):
     dtype = CASES[case][1]
-    full_e, full_t, _ = checkpoints(lib, monkeypatch, case, KS, dtype)
+    full_e, full_t, _ = checkpoints(lib, case, KS, dtype)
     # one checkpoint at K is the plain run
-    one_e, one_t, _ = checkpoints(lib, monkeypatch, case, [5], dtype)
-    want, plan_k = plain(lib, monkeypatch, case, 5, dtype)
+    one_e, one_t, _ = checkpoints(lib, case, [5], dtype)
+    want, plan_k = plain(lib, case, 5, dtype)
     assert np.array_equal(one_e[0], want) and np.array_equal(one_e[0], full_e[3]) and np.array_equal(one_t[0], full_t[3])
     # NULL entries inside the arrays change nothing else
-    e2, t2, _ = checkpoints(lib, monkeypatch, case, KS, dtype, skip=(1, 4))
+    e2, t2, _ = checkpoints(lib, case, KS, dtype, skip=(1, 4))
     for j in range(len(KS)):
         if j in (1, 4):
             assert np.all(e2[j] == SENTINEL) and np.all(t2[j] == SENTINEL)
         else:
             assert np.array_equal(e2[j], full_e[j]) and np.array_equal(t2[j], full_t[j])
     # estimates only, traces only: the same bits; with trace_dev only the plan's final estimate is the plain run's
-    e3, _, _ = checkpoints(lib, monkeypatch, case, KS, dtype, traces=False)
-    _, t4, plan4 = checkpoints(lib, monkeypatch, case, KS, dtype, outs=False)
+    e3, _, _ = checkpoints(lib, case, KS, dtype, traces=False)
+    _, t4, plan4 = checkpoints(lib, case, KS, dtype, outs=False)
     assert all(np.array_equal(a, b) for a, b in zip(e3, full_e)) and np.array_equal(t4, full_t)
-    _, plan8 = plain(lib, monkeypatch, case, KS[-1], dtype)
+    _, plan8 = plain(lib, case, KS[-1], dtype)
     assert np.array_equal(plan4.estimate(), plan8.estimate())
     # a second call on the same plan: the same bits again
-    _, t5, _ = checkpoints(lib, monkeypatch, case, KS, dtype, outs=False, plan=plan4)
+    _, t5, _ = checkpoints(lib, case, KS, dtype, outs=False, plan=plan4)
     assert np.array_equal(t5, full_t)
 
 
 # ------------------------------------------------------------------ trace parity
 @pytest.mark.parametrize('case', ['f64_two_chunks_short_last', 'f32_frame_pairs', 'slices_on_two_lanes_shared_classes'])
-def test_trace_against_long_double(lib, monkeypatch, case):
+def test_trace_against_long_double(lib, case):
     """A single-chunk run (the plan's batch covers the tasks): every field of every checkpoint of every task within the derived
     bound of the long double sums of the downloaded checkpoint and the plan's object; the same bits from a second run."""
     _, dtype, ny, nx, B, pattern, _, _, _ = CASES[case]
     select = list(range(min(B, len(pattern))))
-    est, tr, plan = checkpoints(lib, monkeypatch, case, KS, dtype, select=select)
+    est, tr, plan = checkpoints(lib, case, KS, dtype, select=select)
     obj = plan.object()
     esize = 4 if dtype == 'f32' else 8
     worst = 0.0
@@ -211,17 +207,17 @@ def test_trace_against_long_double(lib, monkeypatch, case):
     print('%s: worst error / bound %.3g' % (case, worst))
     # semi-convergence is a property of the data; the sums of T are the same at every checkpoint
     assert np.array_equal(tr[0, :, [1, 3]], tr[-1, :, [1, 3]])
-    est2, tr2, _ = checkpoints(lib, monkeypatch, case, KS, dtype, select=select)
+    est2, tr2, _ = checkpoints(lib, case, KS, dtype, select=select)
     assert np.array_equal(tr2, tr) and all(np.array_equal(a, b) for a, b in zip(est, est2))
 
 
-def test_trace_of_a_task_alone_and_in_a_batch(lib, monkeypatch):
+def test_trace_of_a_task_alone_and_in_a_batch(lib):
     """f64: a task's estimate does not depend on its place in the list, and its trace is a function of estimate and object only --
     task 5 of the two-chunk batch (the second chunk's first) gives the bits it gives alone in a plan of one frame."""
     case = 'f64_two_chunks_short_last'
-    est, tr, _ = checkpoints(lib, monkeypatch, case, KS, 'f64')
-    alone = make_plan(lib, monkeypatch, case, batch=1)
-    e1, t1, _ = checkpoints(lib, monkeypatch, case, KS, 'f64', plan=alone, select=[5])
+    est, tr, _ = checkpoints(lib, case, KS, 'f64')
+    alone = make_plan(lib, case, batch=1)
+    e1, t1, _ = checkpoints(lib, case, KS, 'f64', plan=alone, select=[5])
     for j in range(len(KS)):
         assert np.array_equal(e1[j][0], est[j][5]) and np.array_equal(t1[j, 0], tr[j, 5]), KS[j]
 
@@ -298,10 +294,10 @@ def test_best_iterations_at_six_photons_per_pixel(lib, small_sweep):
 
 
 # ------------------------------------------------------------------ error codes
-def test_error_codes(lib, monkeypatch):
+def test_error_codes(lib):
     case = 'f64_two_chunks_short_last'
     _, _, ny, nx, _, _, _, _, _ = CASES[case]
-    plan = make_plan(lib, monkeypatch, case)
+    plan = make_plan(lib, case)
     objs, tb, seeds, ids = tasks_of(case)
     objs = [np.ascontiguousarray(o) for o in objs[:2]]
     T = lib.DeconvPlan._Task

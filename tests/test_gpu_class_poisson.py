@@ -16,9 +16,12 @@ L = 192 (general row body), 200 x 200 at L = 256 (wave-private kernels, frame pa
 107 x 107 STED PSF runs the kernels compiled for 512-pixel rows.
 """
 import ctypes
+import functools
 
 import numpy as np
 import pytest
+
+from plan_cases import plans_per_value
 
 pytestmark = pytest.mark.gpu
 
@@ -43,20 +46,8 @@ def objects(pattern, ny, nx, seed=11):
     return np.stack([kinds[c] for c in pattern])
 
 
-def plans(lib, monkeypatch, psfs, B, ny, nx, dtype, env=None):
-    """(per-frame plan, sharing plan): the switch is read when a plan is created."""
-    out = []
-    for k, v in (env or {}).items():
-        monkeypatch.setenv(k, v)
-    for share in ('0', '1'):
-        monkeypatch.setenv('RLSTED_SHARE_OBJECTS', share)
-        out.append(lib.DeconvPlan(psfs, B, ny, nx, dtype=dtype))
-    for k in ['RLSTED_SHARE_OBJECTS'] + list(env or {}):
-        monkeypatch.delenv(k)
-    for p in out:
-        s = p.strategy()
-        assert not s['separable'] and not s['direct_stencil']
-    return out
+# (per-frame plan, sharing plan) = plans(lib, psfs, B, ny, nx, dtype, options=None)
+plans = functools.partial(plans_per_value, switch='RLSTED_SHARE_OBJECTS', fft_only=True)
 
 
 def twin(plan, dtype, seed):
@@ -80,9 +71,9 @@ def same_cycles(off, on, K, seeds=SEEDS, cycles=1):
 @pytest.mark.parametrize('V', [1, 2])
 @pytest.mark.parametrize('dtype', ['f32', 'f64'])
 @pytest.mark.parametrize('size', [128, 200])
-def test_class_cycle_is_the_per_frame_cycle(lib, monkeypatch, size, dtype, V):
+def test_class_cycle_is_the_per_frame_cycle(lib, size, dtype, V):
     pattern = 'AABABCA'
-    off, on = plans(lib, monkeypatch, small_psfs(V), len(pattern), size, size, dtype)
+    off, on = plans(lib, small_psfs(V), len(pattern), size, size, dtype)
     assert on.info()['lx'] == on.info()['ly'] == {128: 192, 200: 256}[size]
     assert on.strategy()['frame_pairs'] == (size == 200 and dtype == 'f32' and V == 1)
     for p in (off, on):
@@ -94,7 +85,7 @@ def test_class_cycle_is_the_per_frame_cycle(lib, monkeypatch, size, dtype, V):
 
 
 @pytest.mark.parametrize('dtype', ['f32', 'f64'])
-def test_zero_pixels_and_rates_on_both_sides_of_ten(lib, monkeypatch, dtype):
+def test_zero_pixels_and_rates_on_both_sides_of_ten(lib, dtype):
     """One object with a dark block and a ramp whose rates cross 10 inside one image: PTRS, the multiplication method and the
     exact zero all meet in a tile."""
     size, V = 128, 2
@@ -103,7 +94,7 @@ def test_zero_pixels_and_rates_on_both_sides_of_ten(lib, monkeypatch, dtype):
     a[40:90, 10:70] = 0.0
     b = rng.random((size, size)) * 200 + 1
     objs = np.stack([a, a, b, a, a, b, a])
-    off, on = plans(lib, monkeypatch, small_psfs(V), 7, size, size, dtype)
+    off, on = plans(lib, small_psfs(V), 7, size, size, dtype)
     for p in (off, on):
         p.set_object(objs, 7000.0)
     same_cycles(off, on, K=2)
@@ -115,14 +106,14 @@ def test_zero_pixels_and_rates_on_both_sides_of_ten(lib, monkeypatch, dtype):
 
 
 @pytest.mark.parametrize('size,dtype,V,mb', [(200, 'f32', 1, '0.001'), (128, 'f64', 2, '2.2')])
-def test_a_class_is_simulated_once_for_all_slices_and_lanes(lib, monkeypatch, size, dtype, V, mb):
+def test_a_class_is_simulated_once_for_all_slices_and_lanes(lib, size, dtype, V, mb):
     """Slices of two frames on two streams: class A is drawn from in three slices, on both lanes, class B in one; H is computed
     for 2 V images per cycle, not for the 4 V of one representative per slice.  Three cycles follow each other without the
     lanes meeting.  What this can catch of the event order is the first cycle's wait for the class rates on lane 1; the order
     between a cycle's last draws and the NEXT cycle's class simulation holds by construction (run_slices), not by this test: within
     one call the object stays, so an overtaking simulation would write the bytes that are there, and the API joins the lanes
     before the object can change (rl_deconv_set_object, rl_batch_submit)."""
-    off, on = plans(lib, monkeypatch, small_psfs(V), 8, size, size, dtype, env={'RLSTED_CHUNK_MB': mb, 'RLSTED_LANES': '2'})
+    off, on = plans(lib, small_psfs(V), 8, size, size, dtype, options={'RLSTED_CHUNK_MB': mb, 'RLSTED_LANES': '2'})
     for p in (off, on):
         p.set_object(objects('AAAAAABB', size, size), 3e7)
     same_cycles(off, on, K=3, seeds=(5, 900), cycles=3)
@@ -132,10 +123,10 @@ def test_a_class_is_simulated_once_for_all_slices_and_lanes(lib, monkeypatch, si
     assert np.array_equal(on.measurement(), twin(on, dtype, 900 + 2))      # (cycle r of a call draws with seed + r)
 
 
-def test_sharing_and_per_frame_slices_in_one_cycle(lib, monkeypatch):
+def test_sharing_and_per_frame_slices_in_one_cycle(lib):
     """A B C D | A A A A | E E F F in slices of four on two lanes: the first slice simulates its four frames, the others draw from
     three classes simulated once."""
-    off, on = plans(lib, monkeypatch, small_psfs(1), 12, 128, 128, 'f64', env={'RLSTED_CHUNK_MB': '2.0', 'RLSTED_LANES': '2'})
+    off, on = plans(lib, small_psfs(1), 12, 128, 128, 'f64', options={'RLSTED_CHUNK_MB': '2.0', 'RLSTED_LANES': '2'})
     for p in (off, on):
         p.set_object(objects('ABCDAAAAEEFF', 128, 128), 3e7)
     same_cycles(off, on, K=2, seeds=(5, 6), cycles=2)
@@ -143,8 +134,8 @@ def test_sharing_and_per_frame_slices_in_one_cycle(lib, monkeypatch):
     assert on.simulated_images() == 4 + 3
 
 
-def test_a_second_object_between_cycles(lib, monkeypatch):
-    off, on = plans(lib, monkeypatch, small_psfs(1), 6, 200, 200, 'f32')
+def test_a_second_object_between_cycles(lib):
+    off, on = plans(lib, small_psfs(1), 6, 200, 200, 'f32')
     for seed, pattern in ((1, 'AABABC'), (2, 'CCCCAA')):
         for p in (off, on):
             p.set_object(objects(pattern, 200, 200, seed=40 + seed), 7e7)
@@ -153,8 +144,8 @@ def test_a_second_object_between_cycles(lib, monkeypatch):
     assert np.array_equal(on.measurement(), twin(on, 'f32', 2))
 
 
-def test_handing_out_the_object_buffer_returns_to_the_per_frame_path(lib, monkeypatch):
-    off, on = plans(lib, monkeypatch, small_psfs(1), 4, 128, 128, 'f64')
+def test_handing_out_the_object_buffer_returns_to_the_per_frame_path(lib):
+    off, on = plans(lib, small_psfs(1), 4, 128, 128, 'f64')
     for p in (off, on):
         p.set_object(objects('AAAA', 128, 128), 3e7)
     same_cycles(off, on, K=1, seeds=(5,))
@@ -166,12 +157,12 @@ def test_handing_out_the_object_buffer_returns_to_the_per_frame_path(lib, monkey
 
 
 @pytest.mark.parametrize('size,dtype,V', [(200, 'f32', 1), (128, 'f64', 2)])
-def test_batch_run_tasks_share_objects_with_their_own_seeds(lib, monkeypatch, size, dtype, V):
+def test_batch_run_tasks_share_objects_with_their_own_seeds(lib, size, dtype, V):
     """rl_batch_run over chunks of two-frame slices on two lanes; every task has its own seed and image id."""
     from oracle import philox_poisson as pp
     B, n_tasks, K = 6, 10, 2
     mb = {200: '0.001', 128: '2.2'}[size]
-    off, on = plans(lib, monkeypatch, small_psfs(V), B, size, size, dtype, env={'RLSTED_CHUNK_MB': mb, 'RLSTED_LANES': '2'})
+    off, on = plans(lib, small_psfs(V), B, size, size, dtype, options={'RLSTED_CHUNK_MB': mb, 'RLSTED_LANES': '2'})
     kinds = objects('ABC', size, size)
     which = [0, 0, 0, 0, 1, 1, 2, 2, 0, 0]
     tasks = (lib.DeconvPlan._Task * n_tasks)()
@@ -201,9 +192,9 @@ def test_batch_run_tasks_share_objects_with_their_own_seeds(lib, monkeypatch, si
             assert np.array_equal(meas[f, v], want), (f, v)
 
 
-def test_512_specialised_kernels(lib, monkeypatch, golden):
+def test_512_specialised_kernels(lib, golden):
     psf = list(golden('g8_fig2_psfs')['2p0x_lr/point_sted_psf'])
-    off, on = plans(lib, monkeypatch, psf, 4, 512, 512, 'f32')
+    off, on = plans(lib, psf, 4, 512, 512, 'f32')
     assert on.info()['lx'] == 576 and on.strategy()['frame_pairs']
     for p in (off, on):
         p.set_object(objects('AAAB', 512, 512), 8e11)
@@ -211,10 +202,10 @@ def test_512_specialised_kernels(lib, monkeypatch, golden):
     assert on.simulated_images() == 2
 
 
-def test_timing_a_cycle_counts_the_class_simulation(lib, monkeypatch):
+def test_timing_a_cycle_counts_the_class_simulation(lib):
     """rl_deconv_time_cycle on a sharing plan: the simulation's launches are those of one class simulation per cycle, and a kernel
     kind without launches (K = 0: no RL kernels) reports an average of 0."""
-    _, on = plans(lib, monkeypatch, small_psfs(1), 8, 128, 128, 'f64', env={'RLSTED_CHUNK_MB': '2.0', 'RLSTED_LANES': '2'})
+    _, on = plans(lib, small_psfs(1), 8, 128, 128, 'f64', options={'RLSTED_CHUNK_MB': '2.0', 'RLSTED_LANES': '2'})
     on.set_object(objects('AAAAAAAA', 128, 128), 3e7)
     avg = (ctypes.c_double * 8)()
     launches = (ctypes.c_double * 8)()

@@ -132,7 +132,7 @@ def test_multi_view_long_transforms_f32_vs_f64_plan(lib, golden, ny, nx, views):
 
 
 @pytest.mark.parametrize('ny,nx,B', [(2048, 100, 2), (1500, 33, 3), (4096, 40, 2), (1100, 1100, 1), (700, 2048, 2)])
-def test_single_view_long_columns_odd_shapes(lib, golden, ny, nx, B, monkeypatch):
+def test_single_view_long_columns_odd_shapes(lib, golden, ny, nx, B):
     """The whole column pass of the long transforms (16-column tiles at L = 2304, twiddle copies and parked values in LDS, the next
     residue class prefetched) on shapes whose spectra do not fill whole tiles: tall and narrow images, a single frame (no pair),
     an odd batch (half-empty last pair); f32 against the f64 plan, pair loop and per-frame loop."""
@@ -145,19 +145,17 @@ def test_single_view_long_columns_odd_shapes(lib, golden, ny, nx, B, monkeypatch
     p64.iterate(10)
     ref = p64.estimate()
     for flag in ('1', '0'):
-        monkeypatch.setenv('RLSTED_PAIR', flag)
-        p32 = lib.DeconvPlan(psf, B, ny, nx, dtype='f32')
+        p32 = lib.DeconvPlan(psf, B, ny, nx, dtype='f32', options={'RLSTED_PAIR': flag})
         p32.set_object(obj, 5e10 * ny * nx / 128 ** 2)
         p32.set_measurement(noisy)
         p32.iterate(10)
         err = max(max_rel(p32.estimate()[b], ref[b]) for b in range(B))
         assert err < F32_MARGIN, (flag, err)
         del p32
-    monkeypatch.delenv('RLSTED_PAIR', raising=False)
 
 
 @pytest.mark.parametrize('size', [2048, 4096])
-def test_frame_pairs_on_the_long_transforms(lib, golden, size, monkeypatch):
+def test_frame_pairs_on_the_long_transforms(lib, golden, size):
     """L = 2304 / 4608 (one workgroup-synchronous row transform per workgroup): the frame-pair loop (the default for f32
     single-view plans at every size since round 3) against the per-frame loop (RLSTED_PAIR=0) and against the f64 plan,
     two white-noise frames, K = 20.  Rounds 1-2 kept pairs opt-in here because f32 had no margin left (0.87 ... 1.11e-5);
@@ -173,8 +171,7 @@ def test_frame_pairs_on_the_long_transforms(lib, golden, size, monkeypatch):
     del p64
     est = {}
     for flag in ('1', '0'):
-        monkeypatch.setenv('RLSTED_PAIR', flag)
-        p32 = lib.DeconvPlan(psf, 2, size, size, dtype='f32')
+        p32 = lib.DeconvPlan(psf, 2, size, size, dtype='f32', options={'RLSTED_PAIR': flag})
         assert p32.strategy()['frame_pairs'] == (flag == '1')
         p32.set_object(obj, 5e10 * (size // 128) ** 2)
         p32.set_measurement(noisy)
@@ -185,11 +182,10 @@ def test_frame_pairs_on_the_long_transforms(lib, golden, size, monkeypatch):
     print('f32 vs f64 at %d^2, K = 20, pairs / per frame: %s' % (size, errs))
     assert max(errs['1']) < F32_MARGIN and max(errs['0']) < F32_MARGIN, errs
     assert max_rel(est['1'], est['0']) < F32_MARGIN                 # two f32 roundings of the same arithmetic
-    monkeypatch.delenv('RLSTED_PAIR')
     assert lib.DeconvPlan(psf, 2, size, size, dtype='f32').strategy()['frame_pairs']   # default: pairs
 
 
-def test_frame_pairs_need_partners_of_comparable_brightness(lib, golden, astronaut512, monkeypatch):
+def test_frame_pairs_need_partners_of_comparable_brightness(lib, golden, astronaut512):
     """A pair's two frames share one complex transform, so f32 rounding error scales with the BRIGHTER partner:
     the plan pairs frames only while every pair's levels are within a factor of 4 (RLSTED_PAIR_MAX_RATIO) and runs its
     per-frame loop otherwise.  Frame 1 is 1e4 times dimmer than frame 0 here; frames 2 / 3 differ by 2."""
@@ -204,9 +200,8 @@ def test_frame_pairs_need_partners_of_comparable_brightness(lib, golden, astrona
     r = ref.estimate()
     errs = {}
     for force in (False, True):
-        if force:
-            monkeypatch.setenv('RLSTED_PAIR_MAX_RATIO', '1e30')     # pair whatever the levels (what round 2 did)
-        plan = lib.DeconvPlan(psf, 4, 512, 512, dtype='f32')
+        # forced: pair whatever the levels (what round 2 did)
+        plan = lib.DeconvPlan(psf, 4, 512, 512, dtype='f32', options={'RLSTED_PAIR_MAX_RATIO': '1e30'} if force else None)
         assert plan.strategy()['frame_pairs']                       # the plan holds the pair loop ...
         plan.set_object(objs, levels)
         plan.set_measurement(noisy)
@@ -216,7 +211,6 @@ def test_frame_pairs_need_partners_of_comparable_brightness(lib, golden, astrona
     print('guarded / forced pairs, per frame:', errs)
     assert max(errs[False]) < F32_MARGIN, errs
     assert errs[True][1] > 10 * errs[False][1], errs                # the dim partner pays for the bright one when forced
-    monkeypatch.delenv('RLSTED_PAIR_MAX_RATIO')
     ok = lib.DeconvPlan(psf, 4, 512, 512, dtype='f32')              # comparable partners stay paired
     ok.set_object(objs, [8e11, 4e11, 2e11, 6e11])
     ok.simulate(seed=3)
@@ -251,7 +245,7 @@ def test_measurement_written_through_the_device_pointer_is_not_paired_blindly(li
     assert np.array_equal(plan.measurement(), noisy.astype(np.float32).astype(np.float64))
 
 
-def test_multi_view_measurement_with_negative_pixels_keeps_the_per_view_clamp(lib, golden, monkeypatch):
+def test_multi_view_measurement_with_negative_pixels_keeps_the_per_view_clamp(lib, golden):
     """`ratio - 1` clamps the SUM of the views' back-projections, the reference each view's (ref:587); they agree
     unless a view's term is negative, which takes a negative measurement pixel.  A multi-view f32 plan whose uploaded
     measurement has negative pixels (background-subtracted data) therefore runs the plain arithmetic: bit for bit what
@@ -279,12 +273,8 @@ def test_multi_view_measurement_with_negative_pixels_keeps_the_per_view_clamp(li
     assert np.isfinite(d.estimate).all() and d.estimate.min() > 0
     assert max_rel(ref.estimate(), d.estimate) < 1e-10
     out = {}
-    for name, env in (('default', {}), ('plain', {'RLSTED_SUB_ONE': '0'}), ('per_view', {'RLSTED_FUSE_VIEWS': '0'})):
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        plan = lib.DeconvPlan(psfs, 2, 128, 128, dtype='f32')
-        for k in env:
-            monkeypatch.delenv(k)
+    for name, options in (('default', {}), ('plain', {'RLSTED_SUB_ONE': '0'}), ('per_view', {'RLSTED_FUSE_VIEWS': '0'})):
+        plan = lib.DeconvPlan(psfs, 2, 128, 128, dtype='f32', options=options)
         plan.set_measurement(noisy)
         plan.iterate(6)
         out[name] = plan.estimate()
@@ -293,9 +283,7 @@ def test_multi_view_measurement_with_negative_pixels_keeps_the_per_view_clamp(li
     clean = lib.DeconvPlan(psfs, 2, 128, 128, dtype='f32')      # without negative pixels the residual form runs (a different rounding path)
     clean.set_measurement(np.abs(noisy) + 1e-9)
     clean.iterate(6)
-    monkeypatch.setenv('RLSTED_SUB_ONE', '0')
-    plain = lib.DeconvPlan(psfs, 2, 128, 128, dtype='f32')
-    monkeypatch.delenv('RLSTED_SUB_ONE')
+    plain = lib.DeconvPlan(psfs, 2, 128, 128, dtype='f32', options={'RLSTED_SUB_ONE': '0'})
     plain.set_measurement(np.abs(noisy) + 1e-9)
     plain.iterate(6)
     assert not np.array_equal(clean.estimate(), plain.estimate()) and max_rel(clean.estimate(), plain.estimate()) < 2e-5

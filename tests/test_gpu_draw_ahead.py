@@ -19,6 +19,8 @@ import ctypes
 import numpy as np
 import pytest
 
+from plan_cases import plans_per_value
+
 pytestmark = pytest.mark.gpu
 
 
@@ -40,22 +42,11 @@ def objects(pattern, ny, nx, seed=11):
     return np.stack([kinds[c] for c in pattern])
 
 
-def plans(lib, monkeypatch, psfs, B, ny, nx, dtype, mb, lanes=2, switches=('0', '1'), grid=None):
-    """One plan per value of RLSTED_DRAW_AHEAD: the switches are read when a plan is created.  grid: RLSTED_DRAW_GRID -- a
-    two-frame slice of 128^2 has 16 tiles, so only a cap below that makes a workgroup of the background launch walk several."""
-    out = []
-    monkeypatch.setenv('RLSTED_CHUNK_MB', mb)
-    monkeypatch.setenv('RLSTED_LANES', str(lanes))
-    monkeypatch.setenv('RLSTED_DRAW_GRID', str(grid or 256))
-    for ahead in switches:
-        monkeypatch.setenv('RLSTED_DRAW_AHEAD', ahead)
-        out.append(lib.DeconvPlan(psfs, B, ny, nx, dtype=dtype))
-    for k in ('RLSTED_CHUNK_MB', 'RLSTED_LANES', 'RLSTED_DRAW_AHEAD', 'RLSTED_DRAW_GRID'):
-        monkeypatch.delenv(k)
-    for p in out:
-        s = p.strategy()
-        assert not s['separable'] and not s['direct_stencil']
-    return out
+def plans(lib, psfs, B, ny, nx, dtype, mb, lanes=2, switches=('0', '1'), grid=None):
+    """One plan per value of RLSTED_DRAW_AHEAD.  grid: RLSTED_DRAW_GRID -- a two-frame slice of 128^2 has 16 tiles, so only a cap
+    below that makes a workgroup of the background launch walk several."""
+    return plans_per_value(lib, psfs, B, ny, nx, dtype, 'RLSTED_DRAW_AHEAD', switches, fft_only=True,
+                           options={'RLSTED_CHUNK_MB': mb, 'RLSTED_LANES': lanes, 'RLSTED_DRAW_GRID': grid or 256})
 
 
 def twin(plan, dtype, seed):
@@ -89,9 +80,9 @@ SHAPES = {
 }
 
 
-def shape_plans(lib, monkeypatch, name, pattern, lanes=2, **kw):
+def shape_plans(lib, name, pattern, lanes=2, **kw):
     dtype, size, side, V, mb, pairs = SHAPES[name]
-    off, on = plans(lib, monkeypatch, psfs_of(V, side), len(pattern), size, size, dtype, mb, lanes, **kw)
+    off, on = plans(lib, psfs_of(V, side), len(pattern), size, size, dtype, mb, lanes, **kw)
     assert on.strategy()['frame_pairs'] == pairs
     for p in (off, on):
         p.set_object(objects(pattern, size, size), 3e7 * (size / 128) ** 2)
@@ -99,10 +90,10 @@ def shape_plans(lib, monkeypatch, name, pattern, lanes=2, **kw):
 
 
 @pytest.mark.parametrize('name', ['f32-128', 'f32-pairs-200', 'f64-128'])
-def test_two_lanes_three_slices_each(lib, monkeypatch, name):
+def test_two_lanes_three_slices_each(lib, name):
     """Cases 1: a lone cycle draws its first slice per lane in the lane and the other four ahead; in a cycle behind another all
     six.  The last cycle's measurement is the numpy twin's."""
-    off, on, dtype = shape_plans(lib, monkeypatch, name, 'AABBAAAABBAA')
+    off, on, dtype = shape_plans(lib, name, 'AABBAAAABBAA')
     cycles(off, on, 3, 1, 5, slices=6, ahead=4)
     cycles(off, on, 3, 2, (1 << 40) + 3, slices=6, ahead=6)
     assert on.object_classes()['shared_slices'] == 6 and on.simulated_images() == 2
@@ -110,33 +101,33 @@ def test_two_lanes_three_slices_each(lib, monkeypatch, name):
 
 
 @pytest.mark.parametrize('frames,slices,lone,chained', [(14, 7, 4, 7), (8, 4, 1, 2)])
-def test_three_lanes_and_a_slice_count_that_is_no_multiple(lib, monkeypatch, frames, slices, lone, chained):
+def test_three_lanes_and_a_slice_count_that_is_no_multiple(lib, frames, slices, lone, chained):
     """Case 2.  Seven slices: lanes of 3, 2 and 2.  Four slices: lanes 1 and 2 hold ONE slice each -- its draw in a chained cycle
     would overwrite the measurement that very slice of the cycle before still iterates on, so they keep the in-lane draw while
     lane 0 draws both of its slices ahead."""
-    off, on, _ = shape_plans(lib, monkeypatch, 'f64-128', ('AABB' * 4)[:frames], lanes=3)
+    off, on, _ = shape_plans(lib, 'f64-128', ('AABB' * 4)[:frames], lanes=3)
     cycles(off, on, 2, 1, 5, slices=slices, ahead=lone)
     cycles(off, on, 2, 3, 6, slices=slices, ahead=chained)
 
 
-def test_one_slice_per_lane_falls_back(lib, monkeypatch):
+def test_one_slice_per_lane_falls_back(lib):
     """Case 3: the slice a draw would run beside is the slice whose measurement it writes."""
-    off, on, _ = shape_plans(lib, monkeypatch, 'f64-128', 'AABB')
+    off, on, _ = shape_plans(lib, 'f64-128', 'AABB')
     cycles(off, on, 2, 1, 5, slices=2, ahead=0)
     cycles(off, on, 2, 3, 6, slices=2, ahead=0)
 
 
-def test_one_lane_has_no_draw_stream(lib, monkeypatch):
+def test_one_lane_has_no_draw_stream(lib):
     """Case 4."""
-    off, on, _ = shape_plans(lib, monkeypatch, 'f64-128', 'AABBAAAABBAA', lanes=1)
+    off, on, _ = shape_plans(lib, 'f64-128', 'AABBAAAABBAA', lanes=1)
     cycles(off, on, 2, 2, 5, slices=6, ahead=0)
 
 
-def test_sharing_and_per_frame_slices_alternate(lib, monkeypatch):
+def test_sharing_and_per_frame_slices_alternate(lib):
     """Case 5: slices of four frames, A A A A | A B C D | A A A A | B B B B | A B C D | A A A A.  Slices 1 and 4 hold four classes
     in four frames: they simulate every frame in their lane's spectrum space and draw there."""
     pattern = 'AAAAABCDAAAABBBBABCDAAAA'
-    off, on = plans(lib, monkeypatch, psfs_of(1), len(pattern), 128, 128, 'f64', '2.0')
+    off, on = plans(lib, psfs_of(1), len(pattern), 128, 128, 'f64', '2.0')
     for p in (off, on):
         p.set_object(objects(pattern, 128, 128), 3e7)
     cycles(off, on, 2, 1, 5, slices=6, ahead=3)     # slices 2, 3 and 5
@@ -145,37 +136,37 @@ def test_sharing_and_per_frame_slices_alternate(lib, monkeypatch):
     assert np.array_equal(off.noiseless(), on.noiseless())
 
 
-def test_two_views(lib, monkeypatch):
+def test_two_views(lib):
     """Case 6."""
-    off, on, _ = shape_plans(lib, monkeypatch, 'f64-128-V2', 'AABBAAAABBAA', grid=5)
+    off, on, _ = shape_plans(lib, 'f64-128-V2', 'AABBAAAABBAA', grid=5)
     cycles(off, on, 2, 1, 5, slices=6, ahead=4)
     cycles(off, on, 2, 2, 6, slices=6, ahead=6)
 
 
-def test_tiles_that_straddle_images(lib, monkeypatch):
+def test_tiles_that_straddle_images(lib):
     """Case 7: 200^2 = 40000 pixels is no multiple of the 2048-pixel tile -- the sampler's per-pixel image lookup."""
-    off, on, dtype = shape_plans(lib, monkeypatch, 'f32-pairs-200', 'AABBAAAABBAA', grid=7)
+    off, on, dtype = shape_plans(lib, 'f32-pairs-200', 'AABBAAAABBAA', grid=7)
     cycles(off, on, 2, 1, 5, slices=6, ahead=4)
     cycles(off, on, 2, 2, 77, slices=6, ahead=6)
     assert np.array_equal(on.measurement(), twin(on, dtype, 78))
 
 
 @pytest.mark.parametrize('K', [1, 20])
-def test_chained_cycles(lib, monkeypatch, K):
+def test_chained_cycles(lib, K):
     """Case 8: four cycles whose lanes never meet.  K = 1: a draw is long against the loop it runs beside, so the draw stream
     runs into its throttle, and every cycle's draws overwrite the measurements of the cycle before."""
-    off, on, dtype = shape_plans(lib, monkeypatch, 'f32-pairs-200', 'AABBAAAABBAA', grid=3)
+    off, on, dtype = shape_plans(lib, 'f32-pairs-200', 'AABBAAAABBAA', grid=3)
     cycles(off, on, K, 4, 900, slices=6, ahead=6)
     assert np.array_equal(on.measurement(), twin(on, dtype, 903))
     cycles(off, on, K, 4, 17, slices=6, ahead=6)
 
 
-def test_a_new_object_with_another_class_layout(lib, monkeypatch):
+def test_a_new_object_with_another_class_layout(lib):
     """Case 9: the compact buffers are rebuilt for the second object after the first cycle's draws; a plan that only ever saw
     the second object computes the same."""
     first, second = 'AABBAAAABBAA', 'CCCCCCDDEEEE'
     dtype, size, side, V, mb, _ = SHAPES['f32-pairs-200']
-    off, on, fresh = plans(lib, monkeypatch, psfs_of(V, side), 12, size, size, dtype, mb, switches=('0', '1', '1'))
+    off, on, fresh = plans(lib, psfs_of(V, side), 12, size, size, dtype, mb, switches=('0', '1', '1'))
     for p in (off, on):
         p.set_object(objects(first, size, size), 3e7)
     cycles(off, on, 2, 2, 5, slices=6, ahead=6)
@@ -187,12 +178,12 @@ def test_a_new_object_with_another_class_layout(lib, monkeypatch):
     assert on.object_classes() == {'classes': 3, 'shared_slices': 6, 'slices': 6}
 
 
-def test_batch_run_with_per_frame_keys(lib, monkeypatch):
+def test_batch_run_with_per_frame_keys(lib):
     """Case 10: rl_batch_run over two chunks of six two-frame slices; every task has its own seed and image id."""
     from oracle import philox_poisson as pp
     dtype, size, side, V, mb, _ = SHAPES['f64-128-V2']
     B, n_tasks, K = 12, 20, 2
-    off, on = plans(lib, monkeypatch, psfs_of(V, side), B, size, size, dtype, mb)
+    off, on = plans(lib, psfs_of(V, side), B, size, size, dtype, mb)
     kinds = objects('ABC', size, size)
     which = [0, 0, 1, 1, 0, 0, 2, 2, 0, 0, 1, 1] + [2, 2, 0, 0, 0, 0, 1, 1]
     tasks = (lib.DeconvPlan._Task * n_tasks)()
@@ -219,10 +210,10 @@ def test_batch_run_with_per_frame_keys(lib, monkeypatch):
 
 
 @pytest.mark.parametrize('K', [0, 2])
-def test_timing_a_cycle_that_draws_ahead(lib, monkeypatch, K):
+def test_timing_a_cycle_that_draws_ahead(lib, K):
     """Case 11: rl_deconv_time_cycle runs the draws as production does -- the sampler's events bracket its launch on the draw
     stream -- and counts what test_gpu_class_poisson.py::test_timing_a_cycle_counts_the_class_simulation counts."""
-    off, on = plans(lib, monkeypatch, psfs_of(1), 24, 128, 128, 'f64', '2.0')
+    off, on = plans(lib, psfs_of(1), 24, 128, 128, 'f64', '2.0')
     res = []
     for p in (off, on):
         p.set_object(objects('A' * 24, 128, 128), 3e7)

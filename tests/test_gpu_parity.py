@@ -208,8 +208,8 @@ def test_many_frames_persistent_column_kernel_orders(lib, golden):
 
 
 @pytest.mark.parametrize('dtype,tol', [('f32', F32_TOL), ('f64', F64_TOL)])
-def test_kernel_flavours_agree(lib, golden, astronaut512, dtype, tol, monkeypatch):
-    """The RL loop has switchable schedules (read from the environment when a plan is made): in place = single-view
+def test_kernel_flavours_agree(lib, golden, astronaut512, dtype, tol):
+    """The RL loop has switchable schedules (options of a plan, read when it is made): in place = single-view
     iterations entirely in spec_a (RLSTED_INPLACE; 0 also means the per-frame loop instead of frame pairs), the batch
     cut into slices (RLSTED_CHUNK_MB) that are iterated on RLSTED_LANES concurrent streams, the column kernel's tile
     order (RLSTED_COL_ORDER), frame pairs on / off.  Every combination must give the default's result (same arithmetic,
@@ -231,13 +231,10 @@ def test_kernel_flavours_agree(lib, golden, astronaut512, dtype, tol, monkeypatc
                                        ('1', '1', '4', '10'), ('0', '0', '3', '20'), ('1', '1', '1', '100000'),
                                        ('0', '1', '1', '100000')):
         # (the complex PSF-spectrum multiplier throughout: the real one is a separate compilation with its own fma contraction)
-        monkeypatch.setenv('RLSTED_REAL_PSF', '0')
-        monkeypatch.setenv('RLSTED_COL_ORDER', {'10': '3', '100000': '64'}.get(mb, '1'))   # image blocks of the tile order
-        monkeypatch.setenv('RLSTED_PAIR', stream)
-        monkeypatch.setenv('RLSTED_INPLACE', inplace)
-        monkeypatch.setenv('RLSTED_LANES', lanes)
-        monkeypatch.setenv('RLSTED_CHUNK_MB', mb)
-        plan = lib.DeconvPlan(psf, B, 512, 512, dtype=dtype)
+        options = {'RLSTED_REAL_PSF': '0',
+                   'RLSTED_COL_ORDER': {'10': '3', '100000': '64'}.get(mb, '1'),   # image blocks of the tile order
+                   'RLSTED_PAIR': stream, 'RLSTED_INPLACE': inplace, 'RLSTED_LANES': lanes, 'RLSTED_CHUNK_MB': mb}
+        plan = lib.DeconvPlan(psf, B, 512, 512, dtype=dtype, options=options)
         plan.set_object(objs, 8e11)
         if noisy is None:
             plan.simulate(seed=9)
@@ -252,8 +249,6 @@ def test_kernel_flavours_agree(lib, golden, astronaut512, dtype, tol, monkeypatc
     for key, est in results.items():
         assert max_rel(est, ref) < (2e-6 if dtype == 'f32' else 1e-13), key
     # default plans: real multiplier for the (point-symmetric) PSF spectrum, first iteration from the shared H(1)
-    for k in ('RLSTED_REAL_PSF', 'RLSTED_PAIR', 'RLSTED_INPLACE', 'RLSTED_LANES', 'RLSTED_CHUNK_MB', 'RLSTED_COL_ORDER'):
-        monkeypatch.delenv(k, raising=False)
     plan = lib.DeconvPlan(psf, B, 512, 512, dtype=dtype)
     plan.set_object(objs, 8e11)
     plan.set_measurement(noisy)
@@ -264,21 +259,20 @@ def test_kernel_flavours_agree(lib, golden, astronaut512, dtype, tol, monkeypatc
 
 @pytest.mark.parametrize('B,K', [(11, 4), (12, 5)])
 @pytest.mark.parametrize('lanes,mb', [('1', '100000'), ('2', '10'), ('3', '7')])
-def test_bench_cycle_equals_simulate_then_iterate(lib, golden, astronaut512, lanes, mb, B, K, monkeypatch):
+def test_bench_cycle_equals_simulate_then_iterate(lib, golden, astronaut512, lanes, mb, B, K):
     """bench.py's timed call (rl_deconv_bench_cycles: forward model, Poisson, est = 1 and K
     iterations per slice of the batch, slices on concurrent streams) leaves exactly what
     rl_deconv_simulate + rl_deconv_iterate over the whole batch leave.  Frame pairs (B = 11: the last pair half empty),
     the last iteration's spectrum dropped (K = 5), lane joins deferred between the cycles -- the path bench.py times."""
-    monkeypatch.setenv('RLSTED_LANES', lanes)
-    monkeypatch.setenv('RLSTED_CHUNK_MB', mb)
+    options = {'RLSTED_LANES': lanes, 'RLSTED_CHUNK_MB': mb}
     psf = list(golden('g8_fig2_psfs')['2p0x_lr/point_sted_psf'])
     rng = np.random.default_rng(17)
     objs = np.concatenate([astronaut512, rng.random((B - 1, 512, 512)) * 200])
-    a = lib.DeconvPlan(psf, B, 512, 512, dtype='f32')
+    a = lib.DeconvPlan(psf, B, 512, 512, dtype='f32', options=options)
     assert a.strategy()['frame_pairs']               # (an odd batch leaves its last pair half empty)
     a.set_object(objs, 8e11)
     a.bench_cycles(K, 3, seed=39)                      # three cycles back to back (no lane join in between): seeds 39, 40, 41; the last one stays
-    b = lib.DeconvPlan(psf, B, 512, 512, dtype='f32')
+    b = lib.DeconvPlan(psf, B, 512, 512, dtype='f32', options=options)
     b.set_object(objs, 8e11)
     b.simulate(seed=41)
     b.iterate(K)
@@ -288,7 +282,7 @@ def test_bench_cycle_equals_simulate_then_iterate(lib, golden, astronaut512, lan
 
 
 @pytest.mark.parametrize('seed', fuzz_seeds(6))
-def test_random_schedules_bench_cycle_equals_stepwise_calls(lib, seed, monkeypatch):
+def test_random_schedules_bench_cycle_equals_stepwise_calls(lib, seed):
     """Soak test of the schedule (RLSTED_FUZZ_SEEDS): random batch sizes, iteration counts, slice sizes (RLSTED_CHUNK_MB down to
     one frame per slice), 1-4 slices in flight, 1-3 views, f32 / f64, pair loop or per-frame loop, dense or sparse objects -- the
     cycle bench.py times leaves bit for bit what simulate + iterate over the whole batch leave, back to back cycles included."""
@@ -302,15 +296,15 @@ def test_random_schedules_bench_cycle_equals_stepwise_calls(lib, seed, monkeypat
         objs *= rng.random((B, ny, nx)) < 0.05
         objs[:, 0, 0] += 1.0
     frame_mb = ny * nx * 4 * 8 / 1e6
-    monkeypatch.setenv('RLSTED_LANES', str(int(rng.integers(1, 5))))
-    monkeypatch.setenv('RLSTED_CHUNK_MB', '%g' % max(frame_mb * float(rng.choice([0.5, 2, 5, 1000])), 1e-3))
-    monkeypatch.setenv('RLSTED_PAIR', str(int(rng.integers(0, 2))))
+    options = {'RLSTED_LANES': str(int(rng.integers(1, 5))),
+               'RLSTED_CHUNK_MB': '%g' % max(frame_mb * float(rng.choice([0.5, 2, 5, 1000])), 1e-3),
+               'RLSTED_PAIR': str(int(rng.integers(0, 2)))}
     brightness = float(rng.choice([50.0, 1e4, 1e8])) * ny * nx
     cycles = int(rng.integers(1, 4))
-    a = lib.DeconvPlan(psfs, B, ny, nx, dtype=dtype)
+    a = lib.DeconvPlan(psfs, B, ny, nx, dtype=dtype, options=options)
     a.set_object(objs, brightness)
     a.bench_cycles(K, cycles, seed=100 + seed)
-    b = lib.DeconvPlan(psfs, B, ny, nx, dtype=dtype)
+    b = lib.DeconvPlan(psfs, B, ny, nx, dtype=dtype, options=options)
     b.set_object(objs, brightness)
     b.simulate(seed=100 + seed + cycles - 1)
     if K > 0:
@@ -349,7 +343,7 @@ def test_2048_line_rescan_batch_vs_oracle(lib, golden):
 
 
 @pytest.mark.parametrize('ny,nx,B', [(2048, 2048, 2), (1801, 300, 3), (1302, 2011, 1), (4000, 600, 1)])
-def test_split_column_pass_against_whole_pass(lib, golden, ny, nx, B, monkeypatch):
+def test_split_column_pass_against_whole_pass(lib, golden, ny, nx, B):
     """Multi-view f32 plans whose column length is 2304 / 4608 run the split column pass (COL_SPLIT_FWD parks the column
     spectra in register-slot order; COL_SPLIT_INV per view for H, COL_SPLIT_INV_SUM for H_t): against the route through
     the whole per-image kernel and the pre-summed update (RLSTED_COL_SPLIT=0).  H_t sums the views' products before the
@@ -359,8 +353,7 @@ def test_split_column_pass_against_whole_pass(lib, golden, ny, nx, B, monkeypatc
     obj = np.random.default_rng(ny + nx).random((B, ny, nx)) * 255
     est, sim = {}, {}
     for flag in ('0', '1'):
-        monkeypatch.setenv('RLSTED_COL_SPLIT', flag)
-        plan = lib.DeconvPlan(psfs, B, ny, nx, dtype='f32')
+        plan = lib.DeconvPlan(psfs, B, ny, nx, dtype='f32', options={'RLSTED_COL_SPLIT': flag})
         assert plan.info()['ly'] == (4608 if ny > 2048 else 2304)
         assert plan.strategy()['split_column_pass'] == (flag == '1')
         plan.set_object(obj, 5e10 * ny * nx / 128 ** 2)
@@ -369,7 +362,6 @@ def test_split_column_pass_against_whole_pass(lib, golden, ny, nx, B, monkeypatc
         plan.iterate(3)
         est[flag] = plan.estimate()
         del plan
-    monkeypatch.delenv('RLSTED_COL_SPLIT', raising=False)
     assert np.array_equal(sim['0'], sim['1'])
     assert np.isfinite(est['1']).all() and max_rel(est['1'], est['0']) < 2e-6
 
@@ -491,11 +483,7 @@ def test_dark_background_narrow_psf_stays_finite(lib):
     print('f64 plan vs oracle: %.2e; smallest prediction / largest: %.1e' % (max_rel(e64, d.estimate), d.H(d.estimate)[0].min() / d.H(d.estimate)[0].max()))
     assert max_rel(e64, d.estimate) < 1e-8
     for pair in ('1', '0'):
-        os.environ['RLSTED_PAIR'] = pair
-        try:
-            p32 = lib.DeconvPlan(psf, 2, ny, nx, dtype='f32')
-        finally:
-            del os.environ['RLSTED_PAIR']
+        p32 = lib.DeconvPlan(psf, 2, ny, nx, dtype='f32', options={'RLSTED_PAIR': pair})
         assert not p32.strategy()['separable']            # (a rank-1 PSF would run direct stencils: no cancellation there)
         p32.set_measurement(meas)
         p32.iterate(K)
@@ -614,7 +602,7 @@ def test_random_shapes_vs_oracle(lib, seed):
 
 
 @pytest.mark.parametrize('seed', fuzz_seeds(8))
-def test_random_hard_cases_vs_oracle(lib, seed, monkeypatch):
+def test_random_hard_cases_vs_oracle(lib, seed):
     """The soak test's second half (RLSTED_FUZZ_SEEDS): what test_random_shapes_vs_oracle does not draw -- the long transforms
     (L = 1152 / 2304 / 4608 along one axis, the other kept narrow for the oracle), SPARSE objects at a low dose (most pixels count
     zero photons: the neutral-pixel rule of conv_kernels.hpp rl_ratio in every row body), the frame-pair loop against the
@@ -657,9 +645,7 @@ def test_random_hard_cases_vs_oracle(lib, seed, monkeypatch):
     results = {}
     for dtype, tol in (('f64', 1e-10), ('f32', 3e-5)):
         for pair in ('0', '1'):
-            monkeypatch.setenv('RLSTED_PAIR', pair)
-            plan = lib.DeconvPlan(psfs, B, ny, nx, dtype=dtype)
-            monkeypatch.delenv('RLSTED_PAIR')
+            plan = lib.DeconvPlan(psfs, B, ny, nx, dtype=dtype, options={'RLSTED_PAIR': pair})
             plan.set_measurement(meas)
             plan.iterate(K)
             est = plan.estimate()
@@ -707,7 +693,7 @@ def test_edge_cases(lib):
 
 # ------------------------------------- frame pairs (two frames in one complex image) in the RL loop
 @pytest.mark.parametrize('ny,nx,B', [(30, 41, 2), (128, 128, 4), (190, 203, 6), (245, 140, 2), (511, 300, 2), (200, 500, 4), (190, 203, 17), (190, 203, 3)])
-def test_frame_pair_loop_equals_per_frame_loop(lib, ny, nx, B, monkeypatch):
+def test_frame_pair_loop_equals_per_frame_loop(lib, ny, nx, B):
     """RLSTED_PAIR=1 (default for single-view plans with an even batch on the wave-private lengths 64 ... 576): the RL
     loop transforms frames 2p and 2p+1 as the real and imaginary part of one complex image.  Same estimates as the
     per-frame loop (f64: rounding level), also across set_estimate / forward calls that invalidate the spectra."""
@@ -716,8 +702,7 @@ def test_frame_pair_loop_equals_per_frame_loop(lib, ny, nx, B, monkeypatch):
     x = rng.random((B, ny, nx)) * 40
     out = {}
     for flag in ('1', '0'):
-        monkeypatch.setenv('RLSTED_PAIR', flag)
-        plan = lib.DeconvPlan(psf, B, ny, nx, dtype='f64')
+        plan = lib.DeconvPlan(psf, B, ny, nx, dtype='f64', options={'RLSTED_PAIR': flag})
         info = plan.info()                   # pairs exist where both transforms are one-per-wave: L = 256, 576
         assert plan.strategy()['frame_pairs'] == (flag == '1' and info['ly'] in (256, 576) and info['lx'] in (256, 576))
         plan.set_object(x, 1e7)
@@ -741,22 +726,20 @@ def test_frame_pair_loop_equals_per_frame_loop(lib, ny, nx, B, monkeypatch):
     assert max_rel(out['1'][0][0], d.estimate[0]) < 1e-11
 
 
-def test_frame_pair_loop_f32_within_contract(lib, golden, astronaut512, monkeypatch):
+def test_frame_pair_loop_f32_within_contract(lib, golden, astronaut512):
     """f32: the pair loop is as accurate as the per-frame loop (same transforms, the packing / splitting arithmetic
     gone), BASELINE object and white noise alike, a factor of three inside the contract after 20 iterations."""
     psf = list(golden('g8_fig2_psfs')['2p0x_lr/point_sted_psf'])
     noise = np.random.default_rng(5).random((2, 512, 512)) * 200
     objs = np.concatenate([astronaut512, astronaut512.transpose(0, 2, 1), noise])
-    monkeypatch.setenv('RLSTED_PAIR', '0')
-    ref = lib.DeconvPlan(psf, 4, 512, 512, dtype='f64')
+    ref = lib.DeconvPlan(psf, 4, 512, 512, dtype='f64', options={'RLSTED_PAIR': '0'})
     ref.set_object(objs, 8e11)
     ref.simulate(seed=11)
     noisy = ref.measurement()
     ref.iterate(20)
     err = {}
     for flag in ('1', '0'):
-        monkeypatch.setenv('RLSTED_PAIR', flag)
-        plan = lib.DeconvPlan(psf, 4, 512, 512, dtype='f32')
+        plan = lib.DeconvPlan(psf, 4, 512, 512, dtype='f32', options={'RLSTED_PAIR': flag})
         plan.set_object(objs, 8e11)
         plan.set_measurement(noisy)
         plan.iterate(20)
@@ -926,7 +909,7 @@ def test_long_rows_per_pixel_against_long_double(lib, L):
             print(line)
 
 
-def test_float64_multi_view_ratio_minus_one_on_the_longest_rows(lib, monkeypatch):
+def test_float64_multi_view_ratio_minus_one_on_the_longest_rows(lib):
     """A float64 row transform of 4608 needs more than the default 64 KB of dynamic LDS.  The multi-view `ratio - 1` update
     (rowpass_body PRESUM; float64 plans run it with RLSTED_SUB_ONE=1) was missing from the kernels prepare() raises the limit of
     (tests/test_long_rows_cpu.py::test_every_launchable_row_kernel_may_use_its_lds): the launch must succeed and agree with the
@@ -937,8 +920,7 @@ def test_float64_multi_view_ratio_minus_one_on_the_longest_rows(lib, monkeypatch
     meas = rng.random((B, 2, ny, nx)) * 5 + 0.5
     est = []
     for sub in ('0', '1'):
-        monkeypatch.setenv('RLSTED_SUB_ONE', sub)
-        plan = lib.DeconvPlan(psfs, B, ny, nx, dtype='f64')
+        plan = lib.DeconvPlan(psfs, B, ny, nx, dtype='f64', options={'RLSTED_SUB_ONE': sub})
         assert plan.info()['lx'] == 4608 and not plan.strategy()['separable'] and not plan.strategy()['direct_stencil']
         plan.set_measurement(meas)
         plan.iterate(3)

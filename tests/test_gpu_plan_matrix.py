@@ -35,25 +35,22 @@ def _frame_rel(a, b):
     return max(max_rel(a[f], b[f]) for f in range(b.shape[0]))
 
 
-def _create(monkeypatch, env, psfs, B, ny, nx, dtype, mode):
-    """A plan created under the options `env` (read at creation), in the mode `mode`."""
-    with monkeypatch.context() as mp:
-        for k, v in env.items():
-            mp.setenv(k, v)
-        acceleration, lam = pc.MODES[mode]
-        return _lib().DeconvPlan(psfs, B, ny, nx, dtype=dtype, acceleration=acceleration, tv_lambda=lam, tv_epsilon=pc.TV_EPSILON)
+def _create(env, psfs, B, ny, nx, dtype, mode):
+    """A plan created with the options `env`, in the mode `mode`."""
+    acceleration, lam = pc.MODES[mode]
+    return _lib().DeconvPlan(psfs, B, ny, nx, dtype=dtype, acceleration=acceleration, tv_lambda=lam, tv_epsilon=pc.TV_EPSILON, options=env)
 
 
 _CHUNK_MB = {}
 
 
-def _sliced(monkeypatch, case, d, env, dtype, mode):
+def _sliced(case, d, env, dtype, mode):
     """The slices row: the plan under the smallest RLSTED_CHUNK_MB that cuts its five frames into three slices (2, 2, 1), found once
     per element type and mode by asking the plan after a cycle (rl_deconv_object_classes)."""
     key = (dtype, mode)
     budgets = [_CHUNK_MB[key]] if key in _CHUNK_MB else list(0.03 * 1.15 ** np.arange(40))
     for mb in budgets:
-        plan = _create(monkeypatch, dict(env, RLSTED_CHUNK_MB='%.5f' % mb), d['psfs'], case['B'], case['ny'], case['nx'], dtype, mode)
+        plan = _create(dict(env, RLSTED_CHUNK_MB='%.5f' % mb), d['psfs'], case['B'], case['ny'], case['nx'], dtype, mode)
         plan.set_object(d['obj'])
         plan.bench_cycles(1, 1)
         if plan.object_classes()['slices'] == 3:
@@ -114,7 +111,7 @@ def _check_divergence(D, model, dtype, tag):
 
 @pytest.mark.parametrize('mode', list(pc.MODES))
 @pytest.mark.parametrize('name', [c['name'] for c in pc.CASES])
-def test_sequence_follows_the_model(name, mode, monkeypatch):
+def test_sequence_follows_the_model(name, mode):
     case, d = pc.BY_NAME[name], pc.data(name)
     B, ny, nx = case['B'], case['ny'], case['nx']
     model = PlanModel(d['psfs'], B, ny, nx)
@@ -122,10 +119,10 @@ def test_sequence_follows_the_model(name, mode, monkeypatch):
     plans = {}
     for dtype in ('f64', 'f32'):
         env = dict(case['env'], **(case['env32'] if dtype == 'f32' else {}))
-        make = _sliced if case['slices'] else (lambda mp, c, dd, e, t, md: _create(mp, e, dd['psfs'], B, ny, nx, t, md))
-        plans[dtype] = make(monkeypatch, case, d, env, dtype, mode)
+        make = _sliced if case['slices'] else (lambda c, dd, e, t, md: _create(e, dd['psfs'], B, ny, nx, t, md))
+        plans[dtype] = make(case, d, env, dtype, mode)
     if case['twin'] is not None:                             # the same f64 case on another strategy
-        plans['twin'] = _create(monkeypatch, dict(case['env'], **case['twin']), d['psfs'], B, ny, nx, 'f64', mode)
+        plans['twin'] = _create(dict(case['env'], **case['twin']), d['psfs'], B, ny, nx, 'f64', mode)
 
     def check_strategy(expect_pairs=None):
         for key, plan in plans.items():
@@ -217,7 +214,7 @@ def _download(plan, dev, n, dtype):
 @pytest.mark.parametrize('last', ['simulate', 'set_measurement', 'batch_submit', 'bench_cycles'])
 @pytest.mark.parametrize('views', [1, 3])
 @pytest.mark.parametrize('dtype', ['f32', 'f64'])
-def test_plan_with_a_history_equals_a_fresh_plan(dtype, views, last, monkeypatch):
+def test_plan_with_a_history_equals_a_fresh_plan(dtype, views, last):
     """After any prefix of calls -- a mode set and unset, a measurement with negative pixels (a multi-view f32 plan then leaves its
     `ratio - 1` arithmetic), the pair choice flipped, D, a set estimate -- the last two calls give the bits a fresh plan gives."""
     name = 'switch_b4' if views == 1 else 'views3'
@@ -242,7 +239,7 @@ def test_plan_with_a_history_equals_a_fresh_plan(dtype, views, last, monkeypatch
             return _download(plan, dev, n, dtype).reshape(B, ny, nx), plan.strategy()
         return plan.estimate(), plan.strategy()
 
-    used = _create(monkeypatch, case['env'], d['psfs'], B, ny, nx, dtype, 'batv')
+    used = _create(case['env'], d['psfs'], B, ny, nx, dtype, 'batv')
     pc.set_mode(used, 'plain')
     used.set_measurement(_negative(d['meas'][0]))
     used.iterate(2)
@@ -254,7 +251,7 @@ def test_plan_with_a_history_equals_a_fresh_plan(dtype, views, last, monkeypatch
     used.set_estimate(d['x'])
     used.iterate(1)
     got, strat = finish(used)
-    fresh = _create(monkeypatch, case['env'], d['psfs'], B, ny, nx, dtype, 'plain')
+    fresh = _create(case['env'], d['psfs'], B, ny, nx, dtype, 'plain')
     want, strat_fresh = finish(fresh)
     assert strat == strat_fresh
     assert np.all(np.isfinite(want))

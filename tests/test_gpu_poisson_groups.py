@@ -11,8 +11,12 @@ the rates the plan reports.
 Shapes as in test_gpu_class_poisson.py: a 9 x 9 PSF that is not rank 1 keeps the plans on the FFT path; 128 x 128 is a multiple
 of the 256-pixel tile, 200 x 200 leaves a ragged last tile (40000 = 156 * 256 + 64).
 """
+import functools
+
 import numpy as np
 import pytest
+
+from plan_cases import plans_per_value
 
 pytestmark = pytest.mark.gpu
 
@@ -38,18 +42,8 @@ def objects(pattern, ny, nx, seed=11):
     return np.stack([kinds[c] for c in pattern])
 
 
-def plans(lib, monkeypatch, psfs, B, ny, nx, dtype, env=None):
-    """(k_poisson plan, frame-group plan): the switch is read when a plan is created."""
-    out = []
-    for k, v in (env or {}).items():
-        monkeypatch.setenv(k, v)
-    monkeypatch.setenv('RLSTED_POISSON_GROUPS', '0')
-    out.append(lib.DeconvPlan(psfs, B, ny, nx, dtype=dtype))
-    monkeypatch.delenv('RLSTED_POISSON_GROUPS')
-    out.append(lib.DeconvPlan(psfs, B, ny, nx, dtype=dtype))
-    for k in env or {}:
-        monkeypatch.delenv(k)
-    return out
+# (k_poisson plan, frame-group plan: the default) = plans(lib, psfs, B, ny, nx, dtype, options=None)
+plans = functools.partial(plans_per_value, switch='RLSTED_POISSON_GROUPS', values=('0', None))
 
 
 def twin(plan, dtype, seed):
@@ -77,9 +71,9 @@ def same_cycles(off, on, K, seeds=SEEDS, cycles=1):
 @pytest.mark.parametrize('V', [1, 2])
 @pytest.mark.parametrize('dtype', ['f32', 'f64'])
 @pytest.mark.parametrize('size', [128, 200])
-def test_grouped_draw_is_the_per_frame_draw(lib, monkeypatch, size, dtype, V, pattern):
+def test_grouped_draw_is_the_per_frame_draw(lib, size, dtype, V, pattern):
     """B = 9, 7 and 8: a short second group, a single short group, one full group; one run, runs of 2 + 1 + ..., eight runs."""
-    off, on = plans(lib, monkeypatch, small_psfs(V), len(pattern), size, size, dtype)
+    off, on = plans(lib, small_psfs(V), len(pattern), size, size, dtype)
     for p in (off, on):
         p.set_object(objects(pattern, size, size), 3e7 * (size / 128) ** 2)
     info = same_cycles(off, on, K=2)
@@ -88,7 +82,7 @@ def test_grouped_draw_is_the_per_frame_draw(lib, monkeypatch, size, dtype, V, pa
 
 
 @pytest.mark.parametrize('dtype', ['f32', 'f64'])
-def test_zero_pixels_and_a_ramp_across_ten(lib, monkeypatch, dtype):
+def test_zero_pixels_and_a_ramp_across_ten(lib, dtype):
     """A dark block and a ramp whose rates cross 10 inside one image: PTRS, the multiplication method and the exact zero meet
     in a tile and in a run."""
     size, V = 128, 2
@@ -97,7 +91,7 @@ def test_zero_pixels_and_a_ramp_across_ten(lib, monkeypatch, dtype):
     a[40:90, 10:70] = 0.0
     b = rng.random((size, size)) * 200 + 1
     objs = np.stack([a, a, b, a, a, b, a, a, a, a, a])
-    off, on = plans(lib, monkeypatch, small_psfs(V), len(objs), size, size, dtype)
+    off, on = plans(lib, small_psfs(V), len(objs), size, size, dtype)
     for p in (off, on):
         p.set_object(objs, 7000.0)
     same_cycles(off, on, K=2)
@@ -108,12 +102,12 @@ def test_zero_pixels_and_a_ramp_across_ten(lib, monkeypatch, dtype):
 
 
 @pytest.mark.parametrize('size,dtype', [(200, 'f32'), (128, 'f64')])
-def test_rates_between_ten_and_thirty(lib, monkeypatch, size, dtype):
+def test_rates_between_ten_and_thirty(lib, size, dtype):
     """Where the squeeze rejects most often and every list is long: most draws go to the rounds."""
     B = 10
     rng = np.random.default_rng(23)
     obj = rng.random((size, size)) * 0.8 + 0.6
-    off, on = plans(lib, monkeypatch, small_psfs(1, unit_sum=True), B, size, size, dtype)
+    off, on = plans(lib, small_psfs(1, unit_sum=True), B, size, size, dtype)
     for p in (off, on):
         p.set_object(np.broadcast_to(obj, (B, size, size)), 20.0 * size * size)
     same_cycles(off, on, K=2)
@@ -125,18 +119,18 @@ def test_rates_between_ten_and_thirty(lib, monkeypatch, size, dtype):
     assert np.array_equal(on.measurement(), twin(on, dtype, SEEDS[-1]))
 
 
-def test_slices_on_two_lanes_and_a_per_frame_slice(lib, monkeypatch):
+def test_slices_on_two_lanes_and_a_per_frame_slice(lib):
     """A B C D | A A A A | E E F F in slices of four on two lanes: the first slice does not share and draws through k_poisson,
     the others through the frame groups -- in one cycle."""
-    off, on = plans(lib, monkeypatch, small_psfs(1), 12, 128, 128, 'f64', env={'RLSTED_CHUNK_MB': '2.0', 'RLSTED_LANES': '2'})
+    off, on = plans(lib, small_psfs(1), 12, 128, 128, 'f64', options={'RLSTED_CHUNK_MB': '2.0', 'RLSTED_LANES': '2'})
     for p in (off, on):
         p.set_object(objects('ABCDAAAAEEFF', 128, 128), 3e7)
     info = same_cycles(off, on, K=2, seeds=(5, 6), cycles=2)
     assert info == {'classes': 6, 'shared_slices': 2, 'slices': 3}
 
 
-def test_rng_none_keeps_the_per_frame_kernel(lib, monkeypatch):
-    off, on = plans(lib, monkeypatch, small_psfs(1), 8, 128, 128, 'f32')
+def test_rng_none_keeps_the_per_frame_kernel(lib):
+    off, on = plans(lib, small_psfs(1), 8, 128, 128, 'f32')
     for p in (off, on):
         p.set_object(objects('AAAAAAAA', 128, 128), 3e7)
         p.bench_cycles(2, 1, seed=1, rng=lib.RNG_NONE)
@@ -145,7 +139,7 @@ def test_rng_none_keeps_the_per_frame_kernel(lib, monkeypatch):
 
 
 @pytest.mark.parametrize('size,dtype,V', [(200, 'f32', 1), (128, 'f64', 2)])
-def test_batch_submit_with_per_frame_keys(lib, monkeypatch, size, dtype, V):
+def test_batch_submit_with_per_frame_keys(lib, size, dtype, V):
     """rl_batch_submit: every task has its own seed and image id.  13 tasks in chunks of 9: the last chunk holds tasks 9 .. 12 and
     repeats the last one, C C A B B B B B B -- runs of 2 + 1 + 5 in the first group, a second group of one frame."""
     from oracle import philox_poisson as pp
@@ -154,7 +148,7 @@ def test_batch_submit_with_per_frame_keys(lib, monkeypatch, size, dtype, V):
     which = [0, 1, 2, 2, 0, 0, 0, 0, 0, 2, 2, 0, 1]
     seeds = [1000 + 7 * i + ((i % 3) << 34) for i in range(len(which))]
     ids = [50 - i for i in range(len(which))]
-    off, on = plans(lib, monkeypatch, small_psfs(V), B, size, size, dtype)
+    off, on = plans(lib, small_psfs(V), B, size, size, dtype)
     got = []
     for p in (off, on):
         p.batch_submit([kinds[w] for w in which], 3e7, seeds, ids, K, None)
@@ -174,9 +168,9 @@ def test_batch_submit_with_per_frame_keys(lib, monkeypatch, size, dtype, V):
             assert np.array_equal(meas[f, v], want), (f, v)
 
 
-def test_512_with_the_sted_psf(lib, monkeypatch, golden):
+def test_512_with_the_sted_psf(lib, golden):
     psf = list(golden('g8_fig2_psfs')['2p0x_lr/point_sted_psf'])
-    off, on = plans(lib, monkeypatch, psf, 16, 512, 512, 'f32')
+    off, on = plans(lib, psf, 16, 512, 512, 'f32')
     assert on.info()['lx'] == 576 and on.strategy()['frame_pairs']
     for p in (off, on):
         p.set_object(objects('A' * 13 + 'BBA', 512, 512), 8e11)

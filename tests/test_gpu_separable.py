@@ -1,11 +1,6 @@
 """The separable strategy (sep_kernels.hip): plans whose views are all rank 1 and small run H / H_t as row +
 column stencils.  Checked against the FFT strategy of the same library (RLSTED_SEP=0) and against the oracle;
 the strategy choice itself is checked through rl_deconv_strategy."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
@@ -24,19 +19,9 @@ def lib():
 
 
 def plan_with(lib, sep, *args, one_kernel=True, **kw):
-    """A plan created under RLSTED_SEP=sep (0 FFT, 1 automatic, 2 separable whenever rank 1); one_kernel=False
+    """A plan created with RLSTED_SEP=sep (0 FFT, 1 automatic, 2 separable whenever rank 1); one_kernel=False
     keeps the two-pass form of the stencils (RLSTED_SEP_ONE=0), True asks for the one-kernel form whenever its tile fits LDS (=2)."""
-    knobs = {'RLSTED_SEP': str(sep), 'RLSTED_SEP_ONE': '2' if one_kernel else '0'}
-    old = {k: os.environ.get(k) for k in knobs}
-    os.environ.update(knobs)
-    try:
-        return lib.DeconvPlan(*args, **kw)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
+    return lib.DeconvPlan(*args, options={'RLSTED_SEP': str(sep), 'RLSTED_SEP_ONE': '2' if one_kernel else '0'}, **kw)
 
 
 def gauss(n, s, shift=0.0):
@@ -185,17 +170,13 @@ def test_long_column_stencils_raise_their_lds_limit_or_fall_back(lib, dtype, py,
 
 
 # ------------------------------------------------------------------ the direct 2-D stencil (PSFs that are not rank 1)
-def _direct_plan(lib, mode, psfs, B, ny, nx, dtype, monkeypatch):
-    monkeypatch.setenv('RLSTED_DIRECT', str(mode))
-    try:
-        return lib.DeconvPlan(psfs, B, ny, nx, dtype=dtype)
-    finally:
-        monkeypatch.delenv('RLSTED_DIRECT')
+def _direct_plan(lib, mode, psfs, B, ny, nx, dtype):
+    return lib.DeconvPlan(psfs, B, ny, nx, dtype=dtype, options={'RLSTED_DIRECT': str(mode)})
 
 
 @pytest.mark.parametrize('py,px,V,shape', [(3, 5, 2, (40, 70)), (7, 7, 1, (128, 128)), (11, 9, 3, (61, 300)), (2, 6, 2, (33, 33)),
                                            (15, 13, 1, (200, 90)), (8, 4, 4, (17, 250))])
-def test_direct_stencil_matches_fft_strategy_and_oracle(lib, py, px, V, shape, monkeypatch):
+def test_direct_stencil_matches_fft_strategy_and_oracle(lib, py, px, V, shape):
     """PSFs that are small but not rank 1 run as a direct 2-D stencil (sep_kernels.hip k_sep2d DIRECT; the default up to 49 taps,
     RLSTED_DIRECT=2 beyond): H, H_t with and without the normaliser, the noiseless image, the Poisson draws from it and 25 RL
     iterations against the FFT strategy of the same library and against the oracle -- odd / even / two-row taps, 1-4 views, tiles
@@ -204,8 +185,8 @@ def test_direct_stencil_matches_fft_strategy_and_oracle(lib, py, px, V, shape, m
     psfs = [rng.random((1, py, px)) + 0.05 for _ in range(V)]
     B, (ny, nx) = 2, shape
     obj = rng.random((B, ny, nx)) * 50
-    d = _direct_plan(lib, 2, psfs, B, ny, nx, 'f64', monkeypatch)
-    fft = _direct_plan(lib, 0, psfs, B, ny, nx, 'f64', monkeypatch)
+    d = _direct_plan(lib, 2, psfs, B, ny, nx, 'f64')
+    fft = _direct_plan(lib, 0, psfs, B, ny, nx, 'f64')
     assert d.strategy()['direct_stencil'] and not d.strategy()['separable']
     assert not fft.strategy()['direct_stencil'] and not fft.strategy()['separable']
     if py * px <= 49:
@@ -227,14 +208,14 @@ def test_direct_stencil_matches_fft_strategy_and_oracle(lib, py, px, V, shape, m
     for _ in range(25):
         o.iterate()
     assert max_rel(d.estimate()[0], o.estimate[0]) < 1e-10
-    f32 = _direct_plan(lib, 2, psfs, B, ny, nx, 'f32', monkeypatch)
+    f32 = _direct_plan(lib, 2, psfs, B, ny, nx, 'f32')
     assert f32.strategy()['direct_stencil']
     f32.set_measurement(d.measurement())
     f32.iterate(25)
     assert max_rel(f32.estimate(), d.estimate()) < 1e-5
 
 
-def test_direct_stencil_keeps_f32_plans_accurate_on_dark_backgrounds(lib, monkeypatch):
+def test_direct_stencil_keeps_f32_plans_accurate_on_dark_backgrounds(lib):
     """What the direct stencil is for beyond speed: sparse emitters on a black background under a narrow, non-separable PSF
     (tests/test_gpu_parity.py::test_dark_background_narrow_psf_stays_finite).  The FFT path's f32 predictions of the dark region are
     rounding noise (finite, but 1e-5 ... 4e-5 of the maximum from the float64 plan, and counted by rl_deconv_unresolved); the
@@ -247,7 +228,7 @@ def test_direct_stencil_keeps_f32_plans_accurate_on_dark_backgrounds(lib, monkey
     yy, xx = np.mgrid[-4:5, -4:5]
     u, w = 0.866 * xx + 0.5 * yy, -0.5 * xx + 0.866 * yy
     psf = [np.exp(-0.5 * ((u / 1.6) ** 2 + (w / 0.8) ** 2))[None]]
-    p64 = _direct_plan(lib, 0, psf, 2, ny, nx, 'f64', monkeypatch)
+    p64 = _direct_plan(lib, 0, psf, 2, ny, nx, 'f64')
     p64.set_object(obj, 3e3)
     p64.simulate(seed=9)
     meas = p64.measurement()
@@ -255,7 +236,7 @@ def test_direct_stencil_keeps_f32_plans_accurate_on_dark_backgrounds(lib, monkey
     ref = p64.estimate()
     err = {}
     for mode in (0, 2):
-        p32 = _direct_plan(lib, mode, psf, 2, ny, nx, 'f32', monkeypatch)
+        p32 = _direct_plan(lib, mode, psf, 2, ny, nx, 'f32')
         assert p32.strategy()['direct_stencil'] == (mode == 2)
         p32.set_measurement(meas)
         p32.iterate(12)
@@ -280,19 +261,9 @@ def emu():
         print(line)
 
 
-def forced_plan(lib, form, psfs, B, ny, nx, dtype):
-    """A plan made to run `form` of the stencils: RLSTED_SEP=2 with RLSTED_SEP_ONE=0 / 2, or RLSTED_DIRECT=2."""
-    knobs = FORM_KNOBS[form]
-    old = {k: os.environ.get(k) for k in knobs}
-    os.environ.update(knobs)
-    try:
-        plan = lib.DeconvPlan([p[None] for p in psfs], B, ny, nx, dtype=dtype)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
+def forced_plan(lib, form, psfs, B, ny, nx, dtype, **more):
+    """A plan made to run `form` of the stencils: RLSTED_SEP=2 with RLSTED_SEP_ONE=0 / 2, or RLSTED_DIRECT=2; more: further options."""
+    plan = lib.DeconvPlan([p[None] for p in psfs], B, ny, nx, dtype=dtype, options=dict(FORM_KNOBS[form], **more))
     s = plan.strategy()
     assert (s['direct_stencil'] and not s['separable']) if form == 'direct' else s['separable'], (form, s)
     return plan
@@ -402,23 +373,55 @@ def test_random_forced_stencils_per_pixel_f32(lib, emu, seed):
         assert max_rel(plan.estimate(), p64.estimate()) < 1e-5, c
 
 
-def test_tile_height_64_per_pixel_in_a_fresh_process(lib):
-    """RLSTED_SEP_TH is read once per process: a fresh child (tests/sep_th64_child.py) creates f32 plans under RLSTED_SEP_TH=64, runs the
-    one-kernel and DIRECT forms on cases of the shared generator, compares forward and adjoint with the reference per pixel and
-    prints error / bound per case; asserted here."""
-    env = dict(os.environ, RLSTED_SEP_TH='64')
-    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'sep_th64_child.py')], env=env, capture_output=True,
-                       text=True, timeout=600)
-    print(r.stdout[-4000:], r.stderr[-2000:])
-    assert r.returncode == 0
-    rows = [json.loads(l) for l in r.stdout.splitlines() if l.startswith('{')]
+def _worst(out, ref, bound):
+    """The largest error / bound of a pixel (inf: an error where the bound is 0)."""
+    err = np.abs(np.asarray(out, dtype=sr.LD) - ref)
+    if np.any(err[bound == 0] != 0):
+        return float('inf')
+    return float(np.max(err[bound > 0] / bound[bound > 0])) if np.any(bound > 0) else 0.0
+
+
+def test_tile_height_64_per_pixel_beside_the_default_height(lib, emu):
+    """RLSTED_SEP_TH is a switch of the plan: f32 plans created with RLSTED_SEP_TH=64 run the one-kernel and DIRECT forms on cases of
+    the shared generator -- the first ten that fit LDS at height 64 --, forward and adjoint against the long-double reference per
+    pixel.  A plan of the same case at the default height, alive in the same process and called in between, stays within the same
+    bounds: the two heights coexist."""
+    rows = []
+    for seed in range(40):
+        if seed % 3 == 0:          # the two-pass form has one tile height
+            continue
+        c, psfs, views = plan_case(emu, seed, 'f32')
+        if not emu.fits(c.form, 4, 64, c.V, views.py, views.px):
+            continue
+        tall = forced_plan(lib, c.form, psfs, c.frames, c.ny, c.nx, 'f32', RLSTED_SEP_TH='64')
+        low = forced_plan(lib, c.form, psfs, c.frames, c.ny, c.nx, 'f32', RLSTED_SEP_TH='32')
+        assert tall.options['RLSTED_SEP_TH'] == '64'
+        conv, e, _ = sr.forward_ref(c.x, views, c.dtype)
+        cv, ev, _ = sr.forward_views_ref(c.y, views, c.dtype)
+        S = np.maximum(cv, 0).sum(axis=1)
+        E = sr.sum_bound(S, ev.sum(axis=1), c.V, c.dtype)
+        row = {'seed': seed, 'form': c.form, 'case': c}
+        for name, plan in (('64', tall), ('32', low)):                 # (forward of both, then adjoint of both: the calls alternate)
+            s = plan.strategy()
+            assert s['separable'] or s['direct_stencil'], (name, c)     # every plan reports a stencil strategy
+            row['h' + name] = plan.forward(c.x)
+        for name, plan in (('64', tall), ('32', low)):
+            row['ht' + name] = plan.adjoint(c.y, False)
+        for name in ('64', '32'):
+            h, ht = row.pop('h' + name), row.pop('ht' + name)
+            assert not (np.isnan(h).any() or np.isnan(ht).any()), (name, c)
+            row['forward' + name], row['adjoint' + name] = _worst(h, np.maximum(conv, 0), e), _worst(ht, S, E)
+        print({k: v for k, v in row.items() if k != 'case'})
+        rows.append(row)
+        if len(rows) == 10:
+            break
     assert {row['form'] for row in rows} == {'one', 'direct'} and len(rows) >= 8
     for row in rows:
-        assert row['tile_height_env'] == '64' and row['stencil']
-        assert not row['nan'] and row['forward'] <= 1 and row['adjoint'] <= 1, row
+        assert row['forward64'] <= 1 and row['adjoint64'] <= 1, row
+        assert row['forward32'] <= 1 and row['adjoint32'] <= 1, row
 
 
-def test_direct_stencil_dark_background_per_pixel(lib, monkeypatch):
+def test_direct_stencil_dark_background_per_pixel(lib):
     """test_direct_stencil_keeps_f32_plans_accurate_on_dark_backgrounds per pixel, on `forward`: every pixel the PSF can reach from an
     emitter is within gamma(py * px + 2) RELATIVE of the reference (all terms are non-negative: A equals the value), every other pixel
     is exactly 0 -- which a normwise max_rel cannot see."""
@@ -431,7 +434,7 @@ def test_direct_stencil_dark_background_per_pixel(lib, monkeypatch):
         yy, xx = np.mgrid[-4:5, -4:5]
         u, w = 0.866 * xx + 0.5 * yy, -0.5 * xx + 0.866 * yy
         psf = np.exp(-0.5 * ((u / 1.6) ** 2 + (w / 0.8) ** 2)).astype(T)
-        plan = _direct_plan(lib, 2, [psf[None].astype(np.float64)], 2, ny, nx, dtype, monkeypatch)
+        plan = _direct_plan(lib, 2, [psf[None].astype(np.float64)], 2, ny, nx, dtype)
         assert plan.strategy()['direct_stencil']
         views = sr.Views(True, p=psf[None])
         conv, e, A = sr.forward_ref(obj, views, T)

@@ -13,9 +13,12 @@ row body.  The wave-private kernels of L = 256 with the frame-pair loop on singl
 1153 x 40 with two views: the smallest image whose column transform (L = 2304) takes the split pass.
 """
 import ctypes
+import functools
 
 import numpy as np
 import pytest
+
+from plan_cases import plans_per_value
 
 pytestmark = pytest.mark.gpu
 
@@ -39,20 +42,8 @@ def objects(pattern, ny, nx, seed=11):
     return np.stack([kinds[c] for c in pattern])
 
 
-def plans(lib, monkeypatch, psfs, B, ny, nx, dtype, env=None):
-    """(per-frame plan, sharing plan): the switch is read when a plan is created."""
-    out = []
-    for k, v in (env or {}).items():
-        monkeypatch.setenv(k, v)
-    for share in ('0', '1'):
-        monkeypatch.setenv('RLSTED_SHARE_OBJECTS', share)
-        out.append(lib.DeconvPlan(psfs, B, ny, nx, dtype=dtype))
-    for k in ['RLSTED_SHARE_OBJECTS'] + list(env or {}):
-        monkeypatch.delenv(k)
-    for p in out:
-        s = p.strategy()
-        assert not s['separable'] and not s['direct_stencil']
-    return out
+# (per-frame plan, sharing plan) = plans(lib, psfs, B, ny, nx, dtype, options=None)
+plans = functools.partial(plans_per_value, switch='RLSTED_SHARE_OBJECTS', fft_only=True)
 
 
 def same_cycle(off, on, objs, brightness, K, cycles=2, seed=5, shared=True):
@@ -73,9 +64,9 @@ def same_cycle(off, on, objs, brightness, K, cycles=2, seed=5, shared=True):
 @pytest.mark.parametrize('V', [1, 2])
 @pytest.mark.parametrize('dtype', ['f32', 'f64'])
 @pytest.mark.parametrize('size', [128, 200])
-def test_shared_cycle_is_the_per_frame_cycle(lib, monkeypatch, size, dtype, V, pattern):
+def test_shared_cycle_is_the_per_frame_cycle(lib, size, dtype, V, pattern):
     B = len(pattern)
-    off, on = plans(lib, monkeypatch, small_psfs(V), B, size, size, dtype)
+    off, on = plans(lib, small_psfs(V), B, size, size, dtype)
     assert on.info()['lx'] == on.info()['ly'] == {128: 192, 200: 256}[size]
     assert on.strategy()['frame_pairs'] == (size == 200 and dtype == 'f32' and V == 1)
     info = same_cycle(off, on, objects(pattern, size, size), 3e7 * (size / 128) ** 2, K=3)
@@ -83,17 +74,17 @@ def test_shared_cycle_is_the_per_frame_cycle(lib, monkeypatch, size, dtype, V, p
 
 
 @pytest.mark.parametrize('size,dtype,V,mb', [(200, 'f32', 1, '0.001'), (128, 'f64', 2, '2.2')])
-def test_a_class_spans_slices_and_lanes(lib, monkeypatch, size, dtype, V, mb):
+def test_a_class_spans_slices_and_lanes(lib, size, dtype, V, mb):
     """Slices of two frames on two streams (a pair plan's smallest slice; 2.2 MB hold two float64 frames of two views): class A has
     a representative in three slices, on both lanes, and the cycles follow each other without the lanes meeting."""
-    off, on = plans(lib, monkeypatch, small_psfs(V), 8, size, size, dtype, env={'RLSTED_CHUNK_MB': mb, 'RLSTED_LANES': '2'})
+    off, on = plans(lib, small_psfs(V), 8, size, size, dtype, options={'RLSTED_CHUNK_MB': mb, 'RLSTED_LANES': '2'})
     info = same_cycle(off, on, objects('AAAAAABB', size, size), 3e7, K=3, cycles=3)
     assert info == {'classes': 2, 'shared_slices': 4, 'slices': 4}
 
 
-def test_slices_with_many_classes_keep_the_per_frame_path(lib, monkeypatch):
+def test_slices_with_many_classes_keep_the_per_frame_path(lib):
     """A B C D | A A A A in slices of four: the first simulates its four frames, the second one representative."""
-    off, on = plans(lib, monkeypatch, small_psfs(1), 8, 128, 128, 'f64', env={'RLSTED_CHUNK_MB': '2.0', 'RLSTED_LANES': '2'})
+    off, on = plans(lib, small_psfs(1), 8, 128, 128, 'f64', options={'RLSTED_CHUNK_MB': '2.0', 'RLSTED_LANES': '2'})
     info = same_cycle(off, on, objects('ABCDAAAA', 128, 128), 3e7, K=2)
     assert info == {'classes': 4, 'shared_slices': 1, 'slices': 2}
     # all frames distinct: nothing to share
@@ -104,25 +95,25 @@ def test_slices_with_many_classes_keep_the_per_frame_path(lib, monkeypatch):
     assert on.object_classes()['classes'] == 2
 
 
-def test_512_specialised_kernels(lib, monkeypatch, golden):
+def test_512_specialised_kernels(lib, golden):
     psf = list(golden('g8_fig2_psfs')['2p0x_lr/point_sted_psf'])
-    off, on = plans(lib, monkeypatch, psf, 4, 512, 512, 'f32')
+    off, on = plans(lib, psf, 4, 512, 512, 'f32')
     assert on.info()['lx'] == 576 and on.strategy()['frame_pairs']
     same_cycle(off, on, objects('AAAB', 512, 512), 8e11, K=2, cycles=1)
 
 
-def test_split_column_pass(lib, monkeypatch):
-    off, on = plans(lib, monkeypatch, small_psfs(2), 4, 1153, 40, 'f32')
+def test_split_column_pass(lib):
+    off, on = plans(lib, small_psfs(2), 4, 1153, 40, 'f32')
     assert on.info()['ly'] == 2304 and on.strategy()['split_column_pass']
     same_cycle(off, on, objects('ABAA', 1153, 40), 1e8, K=3)
 
 
 @pytest.mark.parametrize('size,dtype,V', [(200, 'f32', 1), (128, 'f64', 2)])
-def test_batch_run_with_tasks_that_share_objects(lib, monkeypatch, size, dtype, V):
+def test_batch_run_with_tasks_that_share_objects(lib, size, dtype, V):
     """rl_batch_run: tasks that point at the same object, each with its own seed and image id; ten tasks on a plan of six frames
     (the short second chunk repeats its last task)."""
     B, n_tasks, K = 6, 10, 3
-    off, on = plans(lib, monkeypatch, small_psfs(V), B, size, size, dtype)
+    off, on = plans(lib, small_psfs(V), B, size, size, dtype)
     kinds = objects('ABC', size, size)
     which = [0, 0, 1, 0, 1, 2, 0, 0, 0, 1]
     tasks = (lib.DeconvPlan._Task * n_tasks)()
@@ -144,10 +135,10 @@ def test_batch_run_with_tasks_that_share_objects(lib, monkeypatch, size, dtype, 
     assert not np.array_equal(got[1][0][0], got[1][0][1])
 
 
-def test_iterate_continues_after_shared_cycles(lib, monkeypatch):
+def test_iterate_continues_after_shared_cycles(lib):
     """K = 4 on the pair loop drops the last spectrum; the first iteration never read or filled the estimate: rl_deconv_iterate
     afterwards rebuilds the spectrum from an estimate that is all there, and K = 0 / K = 1 leave ones / one update."""
-    off, on = plans(lib, monkeypatch, small_psfs(1), 6, 200, 200, 'f32')
+    off, on = plans(lib, small_psfs(1), 6, 200, 200, 'f32')
     assert on.strategy()['frame_pairs']
     objs = objects('AABABC', 200, 200)
     for p in (off, on):
@@ -173,8 +164,8 @@ def test_iterate_continues_after_shared_cycles(lib, monkeypatch):
     assert np.array_equal(off.measurement(), on.measurement())
 
 
-def test_handing_out_the_object_buffer_ends_the_sharing(lib, monkeypatch):
-    off, on = plans(lib, monkeypatch, small_psfs(1), 4, 128, 128, 'f64')
+def test_handing_out_the_object_buffer_ends_the_sharing(lib):
+    off, on = plans(lib, small_psfs(1), 4, 128, 128, 'f64')
     same_cycle(off, on, objects('AAAA', 128, 128), 3e7, K=1)
     on.device_array('object')               # the caller may write it: the classes are no longer known
     on.bench_cycles(1, 1, seed=5)

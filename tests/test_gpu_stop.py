@@ -22,8 +22,8 @@ def _lib():
     return _lib
 
 
-def _plan(psfs, B, ny, nx, dtype='f64', acceleration=None):
-    return _lib().DeconvPlan(psfs, B, ny, nx, dtype=dtype, acceleration=acceleration)
+def _plan(psfs, B, ny, nx, dtype='f64', acceleration=None, options=None):
+    return _lib().DeconvPlan(psfs, B, ny, nx, dtype=dtype, acceleration=acceleration, options=options)
 
 
 def _objects():
@@ -70,7 +70,7 @@ def _check_divergence(plan, dtype, tag):
 def _strategy_cases():
     sep = [np.outer(_gauss(7, 1.2), _gauss(5, 0.9))[None], np.outer(_gauss(5, 0.8), _gauss(7, 1.5))[None]]
     ring = np.outer(_gauss(7, 1.0), _gauss(7, 1.0)) + 0.3 * np.outer(_gauss(7, 2.5), _gauss(7, 0.6))
-    return {   # PSFs, size, batches to draw from, iterations at most, environment, what an f32 plan's strategy must report
+    return {   # PSFs, size, batches to draw from, iterations at most, options, what an f32 plan's strategy must report
         'pair': (sr.psf_set(sr.POINT), 512, (2, 4), 6, {}, {'frame_pairs': True}),
         'per_frame': (sr.psf_set(sr.POINT), 512, (1, 2, 3), 6, {'RLSTED_PAIR': '0'}, {'frame_pairs': False}),
         'views4': (sr.psf_set(sr.LINE), 512, (1, 2, 3), 6, {}, {'split_column_pass': False}),
@@ -84,10 +84,8 @@ def _strategy_cases():
 @pytest.mark.parametrize('dtype', ['f32', 'f64'])
 @pytest.mark.parametrize('case', ['pair', 'per_frame', 'views4', 'split', 'separable', 'direct'])
 @pytest.mark.parametrize('seed', fuzz_seeds(1))
-def test_random_divergence_matches_numpy_on_every_strategy(seed, case, dtype, acceleration, monkeypatch):
-    psfs, n, batches, kmax, env, want = _strategy_cases()[case]
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+def test_random_divergence_matches_numpy_on_every_strategy(seed, case, dtype, acceleration):
+    psfs, n, batches, kmax, options, want = _strategy_cases()[case]
     rng = np.random.default_rng([seed, len(case), _itemsize(dtype)])
     B = int(rng.choice(batches))
     names = ['astronaut', 'rings', 'lines', 'cat']
@@ -95,7 +93,7 @@ def test_random_divergence_matches_numpy_on_every_strategy(seed, case, dtype, ac
     obj = np.stack([np.kron(o, np.ones((n // 128, n // 128))) for o in base])
     dose = 10 ** rng.uniform(6, 10) * (n / 128) ** 2
     doses = dose * rng.uniform(1.0, 3.0, size=B)             # (partners of comparable level: the pair loop runs)
-    plan = _plan(psfs, B, n, n, dtype, acceleration)
+    plan = _plan(psfs, B, n, n, dtype, acceleration, options)
     plan.set_object(obj, doses)
     plan.simulate(seed=seed + 1)
     if dtype == 'f32':

@@ -142,19 +142,17 @@ def _cases():
 
 
 @pytest.mark.parametrize('case', ['pair', 'per_frame', 'views4', 'split', 'separable', 'direct'])
-def test_f32_matches_f64_on_every_loop(case, monkeypatch):
+def test_f32_matches_f64_on_every_loop(case):
     """The f32 error with the regulariser on may be at most twice the error of the same plans with it off, measured here first,
     and never above the f32 contract 1e-5."""
-    psfs, n, B, K, env, want = _cases()[case]
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    psfs, n, B, K, options, want = _cases()[case]
     base = _stack(['astronaut', 'rings'])[:B]
     obj = np.stack([np.kron(o, np.ones((n // 128, n // 128))) for o in base])
-    p64 = _plan(psfs, B, n, n, 'f64', tv=False)
+    p64 = _plan(psfs, B, n, n, 'f64', tv=False, options=options)
     p64.set_object(obj, [5e10 * (n / 128) ** 2] * B)
     p64.simulate(seed=11)
     meas = p64.measurement()
-    p32 = _plan(psfs, B, n, n, 'f32', tv=False)
+    p32 = _plan(psfs, B, n, n, 'f32', tv=False, options=options)
     err = {}
     for tv in (False, True):
         for p in (p32, p64):

@@ -32,6 +32,11 @@ def bind(path, tag):
     m.__file__ = os.path.join(ROOT, 'rescan_line_sted_amd', '_lib.py')
     sys.modules[m.__name__] = m
     exec(compile(src, m.__file__, 'exec'), m.__dict__)
+    if not hasattr(m.lib, 'rl_deconv_create_with'):      # a library from before the options argument: plans without options
+        def create_with(*a):
+            assert a[9] is None, 'this library takes no plan options'
+            return m.lib.rl_deconv_create(*a[:9], a[10])
+        m.lib.rl_deconv_create_with = create_with
     return m
 
 

@@ -16,6 +16,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bench  # noqa: E402
 import ab_bench  # noqa: E402
 import rescan_line_sted_amd  # noqa: E402,F401
+# (quality and sharding keep the package's own binding: made here, before bind() points RLSTED_LIB at a library that may be older than
+# the binding's prototypes)
+import rescan_line_sted_amd._lib  # noqa: E402,F401
 
 libs = sys.argv[1:3]
 sweeps = []
