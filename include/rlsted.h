@@ -686,6 +686,35 @@ int rl_stack_create(rl_deconv* plan, const rl_stack_params* params, rl_stack** o
 int rl_stack_run(rl_stack* st, const void* raw_host, int n_frames, int k_iters, void* out_host, double* ingest_stats,
                  double* export_stats, double* times_ms);
 int rl_stack_destroy(rl_stack* st);
+/* rl_stack_run_registered: rl_stack_run with every image registered on the device before the iterations (registration.py
+ * deconvolve_stack_registered(pipeline=True)).  Per chunk, on the context's stream: the upload waited
+ * for, rl_ingest into a staging buffer [B][V][ny][nx] of the plan's dtype (its statistics into the slot as rl_stack_run does),
+ * `freed` recorded; chunk 0 only: frame 0's V images copied to the references and, with rp->views and V > 1, views 1 .. V - 1
+ * estimated against view 0 (rl_register_estimate); with rp->frames every (f, v) of the chunk but global frame 0 estimated against
+ * reference v, the view shift added (fillers: shift 0); rl_shift_images staging -> the plan's measurement buffer, all B V images,
+ * order rp->interp, floor = epsilon; the plan's iterations from ones; rl_export into the slot.  Uploads of chunk i + 1 and
+ * downloads of chunk i - 1 run on the copy streams as in rl_stack_run.  The estimates are those of the host's loop in
+ * deconvolve_stack_registered, bit for bit.  rp: the switches, max_shift 1 .. 32 (margin max_shift + 2), refine >= 0, interp 1 or 3
+ * (the search values are checked only when something is estimated).  given_shifts: NULL, or host [n_frames][V][2] applied as they
+ * are (no estimate).  register_out: host arrays, all required -- shifts [n_frames][V][2] as applied, fields [n_frames][V][3] = ncc,
+ * at_limit, flat of the frame estimates (0 where none ran), view_shifts [V][2], view_fields [V][3], raised [n_frames][V] (pixels
+ * raised to epsilon by the shift).  times_ms: NULL or [5] = rl_stack_run's four, then the summed wall time of the estimates.  The
+ * staging buffer, the references and (refine > 0) a float64 scratch of B V images are allocated on first use and freed by
+ * rl_stack_destroy.  On failure the copies in flight are waited for before it returns.
+ * RL_ERR_INVALID (nothing is enqueued): a NULL st / raw_host / rp / out_host / register_out or one of its arrays, n_frames < 1,
+ * k_iters < 0, interp neither 1 nor 3, a given shift that is not finite; estimating: max_shift outside 1 .. 32, refine < 0, an
+ * interior ny - 2 (max_shift + 2) or nx - 2 (max_shift + 2) below 8. */
+typedef struct {
+    int views, frames;       /* nonzero: estimate the views on frame 0 / every frame against frame 0 */
+    int max_shift, refine;
+    int interp;              /* 1 or 3 */
+} rl_stack_register;
+typedef struct {
+    double *shifts, *fields, *view_shifts, *view_fields, *raised;
+} rl_stack_register_out;
+int rl_stack_run_registered(rl_stack* st, const void* raw_host, int n_frames, int k_iters, const rl_stack_register* rp,
+                            const double* given_shifts, void* out_host, double* ingest_stats, double* export_stats,
+                            rl_stack_register_out* register_out, double* times_ms);
 /* `bytes` bytes of any type from a host array to a device address of this GPU, as they are (raw camera data on its way to
  * rl_ingest outside a pipeline: deconvolve_tiled with a camera).  Blocking: the host array may go away when it returns. */
 int rl_device_upload_bytes(rl_ctx* ctx, void* dev, const void* host, size_t bytes);
@@ -768,6 +797,35 @@ int rl_shift_images(rl_ctx* ctx, const void* src_dev, int src_dtype, int n, int 
 #define RL_XCORR_FIELDS 7
 int rl_register_xcorr(rl_ctx* ctx, const void* ref_dev, int ref_dtype, const int64_t* ref_offsets, const void* mov_dev, int mov_dtype,
                       const int64_t* mov_offsets, int n_pairs, int ny, int nx, int R, double* peaks_out, float* surface_out);
+
+/* rl_register_peaks: the host's NCC, first-maximum search and parabola (registration.ncc_surface, surface_peak) on the device, bit
+ * for bit, for n_pairs rows of sums as rl_register_sums forms them.  tot_dev: device [n_pairs][(2 R + 1)^2 * 3 + 2] float64 = per
+ * displacement S_b, S_bb, S_ab, then S_a, S_aa.  n_terms: the number of terms of every sum, (ny - 2 M)(nx - 2 M).  Per displacement,
+ * in float64 with every operation rounded on its own: va = S_aa - S_a S_a / n, vb = S_bb - S_b S_b / n,
+ * c = (S_ab - S_a S_b / n) / sqrt(va vb).  A pair is FLAT when va or any vb is not positive (nan included).  The peak is the first
+ * maximum in row-major order; the parabola per axis is delta = (0.5 (m - p)) / ((m - 2 z) + p), 0 where the denominator is 0, and
+ * 0 with at_limit set where the peak lies on the window's border; shift = (peak index - R) + delta.
+ * peaks_out: host [n_pairs][RL_PEAK_FIELDS] = shift_y, shift_x, value at the peak, at_limit (0 / 1), flat (0 / 1); a flat pair gives
+ * 0, 0, 0, 0, 1.  surface_out: NULL, or host [n_pairs][(2 R + 1)^2] = c (zeros for a flat pair).  One workgroup per pair, no
+ * atomics: bit-identical from run to run.  Synchronises the context's stream.
+ * RL_ERR_INVALID (no kernel is launched): a NULL ctx / tot_dev / peaks_out, n_pairs < 1, R outside 1 .. 32, n_terms not finite or
+ * below 1.
+ *
+ * rl_register_estimate: registration._estimate without the coarse stage, in one call -- the sums of rl_register_sums (addressing,
+ * R, M and their checks as there), the peaks of rl_register_peaks on the device, 5 doubles per pair down, then `refine` passes over
+ * the pairs that are not flat: each moving image shifted by its current estimate (rl_shift_images, order 3, no floor) into
+ * scratch_dev (float64, n_pairs images of ny x nx, not overlapping the images), the sums at R = 1 with the same M, the peaks, and
+ * shift += the new offset; such a pass replaces the value, keeps at_limit of the first stage and leaves a pair it finds flat alone.
+ * shifts_out: host [n_pairs][2]; fields_out: host [n_pairs][3] = ncc, at_limit, flat; surface_out: NULL, or host
+ * [n_pairs][(2 R + 1)^2], the first stage's surfaces.  scratch_dev may be NULL when refine == 0.  Uses the context's workspace and
+ * synchronises its stream.
+ * RL_ERR_INVALID (no kernel is launched): as rl_register_sums, a NULL shifts_out / fields_out, refine < 0, refine > 0 without a
+ * scratch buffer. */
+#define RL_PEAK_FIELDS 5
+int rl_register_peaks(rl_ctx* ctx, const double* tot_dev, int n_pairs, int R, double n_terms, double* peaks_out, double* surface_out);
+int rl_register_estimate(rl_ctx* ctx, const void* ref_dev, int ref_dtype, const int64_t* ref_offsets, const void* mov_dev, int mov_dtype,
+                         const int64_t* mov_offsets, int n_pairs, int ny, int nx, int R, int M, int refine, double* scratch_dev,
+                         double* shifts_out, double* fields_out, double* surface_out);
 
 /* ---- line_sted_figure_3.py: the scan-position-by-scan-position imaging simulator (:76-273) ----
  * rl_rotate_image: `rotate` (:382-391) for one [ny][nx] plane -- scipy.ndimage.rotate(order 3,

@@ -72,6 +72,7 @@ def jobs():
     out.append((os.path.join(OBJ, 'ingest_kernels.o'), os.path.join(CSRC, 'ingest_kernels.hip'), DEVICE))
     out.append((os.path.join(OBJ, 'stack_api.o'), os.path.join(CSRC, 'stack_api.cpp'), ['-x', 'hip'] + DEVICE))
     out.append((os.path.join(OBJ, 'register_kernels.o'), os.path.join(CSRC, 'register_kernels.hip'), DEVICE))
+    out.append((os.path.join(OBJ, 'register_peaks.o'), os.path.join(CSRC, 'register_peaks.hip'), DEVICE))
     out.append((os.path.join(OBJ, 'xcorr_kernels.o'), os.path.join(CSRC, 'xcorr_kernels.hip'), DEVICE + FFT_FLAGS))
     out.append((os.path.join(OBJ, 'register_api.o'), os.path.join(CSRC, 'register_api.cpp'), ['-x', 'hip'] + DEVICE))
     out.append((os.path.join(OBJ, 'gauss_fit.o'), os.path.join(CSRC, 'gauss_fit.cpp'), ['-ffp-contract=off']))

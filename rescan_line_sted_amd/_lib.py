@@ -137,11 +137,15 @@ PROTOTYPES = {
     'rl_stack_create': (_i, [_vp, _vp, _c.POINTER(_vp)]),
     'rl_stack_run': (_i, [_vp, _vp, _i, _i, _vp, _dp, _dp, _dp]),
     'rl_stack_destroy': (_i, [_vp]),
+    'rl_stack_run_registered': (_i, [_vp, _vp, _i, _i, _vp, _dp, _vp, _dp, _dp, _vp, _dp]),
     'rl_device_upload_bytes': (_i, [_vp, _vp, _vp, _c.c_size_t]),
     'rl_register_sums': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _vp, _i, _c.POINTER(_c.c_int64), _i, _i, _i, _i, _i, _dp, _dp]),
     'rl_shift_images': (_i, [_vp, _vp, _i, _i, _i, _i, _dp, _i, _c.c_double, _vp, _i, _dp]),
     'rl_register_xcorr': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _vp, _i, _c.POINTER(_c.c_int64), _i, _i, _i, _i, _dp,
                                 _c.POINTER(_c.c_float)]),
+    'rl_register_peaks': (_i, [_vp, _vp, _i, _i, _c.c_double, _dp, _dp]),
+    'rl_register_estimate': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _vp, _i, _c.POINTER(_c.c_int64), _i, _i, _i, _i, _i, _i, _vp,
+                                  _dp, _dp, _dp]),
     'rl_ensemble_stats': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int32), _i, _vp, _i, _c.POINTER(_c.c_int64), _dp,
                                _c.c_size_t, _vp, _vp, _dp]),
 }

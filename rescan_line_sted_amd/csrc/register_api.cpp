@@ -1,7 +1,8 @@
 // register_api.cpp -- C ABI of the registration primitives (include/rlsted.h: rl_register_sums, rl_shift_images,
-// rl_register_xcorr): validation, the shift's taps (formed on the host in long double, register_kernels.hpp shift_taps), the
-// chunking under the workspace caps and the launches of register_kernels.hip and xcorr_kernels.hip.  Only offsets and taps go up and the sums and statistics come down.  No kernel is launched on
-// bad arguments.
+// rl_register_peaks, rl_register_estimate, rl_register_xcorr): validation, the shift's taps (formed on the host in long double,
+// register_kernels.hpp shift_taps), the chunking under the workspace caps and the launches of register_kernels.hip,
+// register_peaks.hip and xcorr_kernels.hip.  Only offsets and taps go up and the sums, peaks and statistics come down.  No kernel is
+// launched on bad arguments.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -48,6 +49,26 @@ int reg_workspace(rl_ctx* ctx, size_t bytes, char** out) {
     }
     *out = (char*)ctx->reg.work;
     return RL_OK;
+}
+
+// the sums of n pairs (offsets: device arrays) in chunks of `chunk` through tot / part, each chunk followed by its peaks into
+// peaks [n][5] and, when surf is not null, surf [n][nd]; enqueued on the context's stream
+int enqueue_sums_peaks(rl_ctx* ctx, const RegGeom& g, const void* ref, int ref_dtype, const long long* a_off, const void* mov, int mov_dtype,
+                       const long long* b_off, size_t n, size_t chunk, double* tot, double* part, double n_terms, double* peaks, double* surf) {
+    for (size_t first = 0; first < n; first += chunk) {
+        const size_t m = std::min(chunk, n - first);
+        RegSumArgs a;
+        a.a = ref; a.b = mov; a.a_off = a_off + first; a.b_off = b_off + first; a.part = part; a.tot = tot; a.pairs = (int)m; a.g = g;
+        HIP_TRY(register_sums(ref_dtype, mov_dtype, a, ctx->stream));
+        RegPeakArgs p;
+        p.tot = tot; p.peaks = peaks + first * kPeakFields; p.surf = surf ? surf + first * g.nd : nullptr; p.pairs = (int)m; p.R = g.R; p.n = n_terms;
+        HIP_TRY(register_peaks(p, ctx->stream));
+    }
+    return RL_OK;
+}
+
+size_t sum_chunk(const RegGeom& g, size_t n) {
+    return std::min<size_t>(n, std::max<size_t>(1, kRegSumWorkBytes / (reg_part_doubles(g) * sizeof(double))));
 }
 }  // namespace
 
@@ -138,6 +159,120 @@ extern "C" int rl_shift_images(rl_ctx* ctx, const void* src_dev, int src_dtype, 
     }
     if (stats_out) HIP_TRY(hipMemcpyAsync(stats_out, stats, (size_t)n * kShiftFields * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));   // (the taps' table is the call's own)
+    return RL_OK;
+}
+
+extern "C" int rl_register_peaks(rl_ctx* ctx, const double* tot_dev, int n_pairs, int R, double n_terms, double* peaks_out, double* surface_out) {
+    if (!ctx || !tot_dev || !peaks_out) return fail(RL_ERR_INVALID, "NULL argument");
+    if (n_pairs < 1) return fail(RL_ERR_INVALID, "n_pairs must be at least 1");
+    if (R < 1 || R > kRegMaxR) return fail(RL_ERR_INVALID, "the search radius must lie in 1 .. 32");
+    if (!std::isfinite(n_terms) || !(n_terms >= 1.0)) return fail(RL_ERR_INVALID, "n_terms must be finite and at least 1");
+    static_assert(kPeakFields == RL_PEAK_FIELDS, "the header's field count");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t nd = (size_t)(2 * R + 1) * (2 * R + 1);
+    const size_t peaks_b = round_up((size_t)n_pairs * kPeakFields * sizeof(double), 256);
+    const size_t surf_b = surface_out ? (size_t)n_pairs * nd * sizeof(double) : 0;
+    char* w = nullptr;
+    RL_TRY(reg_workspace(ctx, peaks_b + surf_b, &w));
+    RegPeakArgs a;
+    a.tot = tot_dev; a.peaks = (double*)w; a.surf = surface_out ? (double*)(w + peaks_b) : nullptr; a.pairs = n_pairs; a.R = R; a.n = n_terms;
+    HIP_TRY(register_peaks(a, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(peaks_out, a.peaks, (size_t)n_pairs * kPeakFields * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (surface_out) HIP_TRY(hipMemcpyAsync(surface_out, a.surf, surf_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return RL_OK;
+}
+
+extern "C" int rl_register_estimate(rl_ctx* ctx, const void* ref_dev, int ref_dtype, const int64_t* ref_offsets, const void* mov_dev,
+                                    int mov_dtype, const int64_t* mov_offsets, int n_pairs, int ny, int nx, int R, int M, int refine,
+                                    double* scratch_dev, double* shifts_out, double* fields_out, double* surface_out) {
+    if (!ctx || !ref_dev || !ref_offsets || !mov_dev || !mov_offsets || !shifts_out || !fields_out) return fail(RL_ERR_INVALID, "NULL argument");
+    if (!float_dtype_ok(ref_dtype) || !float_dtype_ok(mov_dtype)) return fail(RL_ERR_INVALID, "dtypes must be RL_F32 or RL_F64");
+    if (n_pairs < 1) return fail(RL_ERR_INVALID, "n_pairs must be at least 1");
+    if (R < 1 || R > kRegMaxR) return fail(RL_ERR_INVALID, "the search radius must lie in 1 .. 32");
+    if (M < R) return fail(RL_ERR_INVALID, "the margin must be at least the search radius");
+    if (ny < 1 || nx < 1 || (long long)ny - 2LL * M < 8 || (long long)nx - 2LL * M < 8)
+        return fail(RL_ERR_INVALID, "the interior must be at least 8 x 8 pixels: ny - 2 M >= 8 and nx - 2 M >= 8");
+    if (refine < 0) return fail(RL_ERR_INVALID, "refine must be at least 0");
+    if (refine > 0 && !scratch_dev) return fail(RL_ERR_INVALID, "refine > 0 needs a scratch buffer");
+    for (int i = 0; i < n_pairs; ++i)
+        if (ref_offsets[i] < 0 || mov_offsets[i] < 0) return fail(RL_ERR_INVALID, "pair " + std::to_string(i) + ": negative offset");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t n = (size_t)n_pairs, n_pix = (size_t)ny * nx;
+    const RegGeom g = reg_geom(ny, nx, R, M), g1 = reg_geom(ny, nx, 1, M);
+    const size_t chunk = sum_chunk(g, n), chunk1 = sum_chunk(g1, n);
+    const size_t per_tot = (size_t)g.nd * kRegFields + 2, per_tot1 = (size_t)g1.nd * kRegFields + 2;
+    const size_t schunk = std::min<size_t>(n, std::max<size_t>(1, kShiftWorkBytes / (n_pix * sizeof(double))));
+    const size_t off_b = round_up(n * sizeof(long long), 256), peaks_b = round_up(n * kPeakFields * sizeof(double), 256);
+    const size_t surf_b = surface_out ? round_up(n * g.nd * sizeof(double), 256) : 0;
+    const size_t tot_b = round_up(std::max(chunk * per_tot, chunk1 * per_tot1) * sizeof(double), 256);
+    const size_t part_b = round_up(std::max(chunk * reg_part_doubles(g), chunk1 * reg_part_doubles(g1)) * sizeof(double), 256);
+    const size_t table_b = refine ? round_up(n * sizeof(ShiftImage), 256) : 0, tmp_b = refine ? schunk * n_pix * sizeof(double) : 0;
+    char* w = nullptr;
+    RL_TRY(reg_workspace(ctx, 4 * off_b + peaks_b + surf_b + tot_b + part_b + table_b + tmp_b, &w));
+    long long* a_off = (long long*)w;
+    long long* b_off = (long long*)(w + off_b);
+    long long* la_off = (long long*)(w + 2 * off_b);
+    long long* lb_off = (long long*)(w + 3 * off_b);
+    char* q = w + 4 * off_b;
+    double* peaks = (double*)q; q += peaks_b;
+    double* surf = surface_out ? (double*)q : nullptr; q += surf_b;
+    double* tot = (double*)q; q += tot_b;
+    double* part = (double*)q; q += part_b;
+    ShiftImage* table_dev = (ShiftImage*)q; q += table_b;
+    double* tmp = (double*)q;
+    static_assert(sizeof(long long) == sizeof(int64_t), "offsets are copied as they are");
+    HIP_TRY(hipMemcpyAsync(a_off, ref_offsets, n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(b_off, mov_offsets, n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    const double n_terms = (double)(((long long)ny - 2LL * M) * ((long long)nx - 2LL * M));
+    // stages 1 - 3: sums, peaks, 5 doubles per pair down
+    std::vector<double> pk(n * kPeakFields);
+    RL_TRY(enqueue_sums_peaks(ctx, g, ref_dev, ref_dtype, a_off, mov_dev, mov_dtype, b_off, n, chunk, tot, part, n_terms, peaks, surf));
+    HIP_TRY(hipMemcpyAsync(pk.data(), peaks, n * kPeakFields * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (surface_out) HIP_TRY(hipMemcpyAsync(surface_out, surf, n * g.nd * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n; ++i) reg_estimate_first(&pk[i * kPeakFields], shifts_out + 2 * i, fields_out + 3 * i);
+    // stage 4: per pass, the pairs that are not flat shifted by their estimate into the scratch, a 3 x 3 window, the offset added
+    std::vector<size_t> live;
+    for (size_t i = 0; i < n; ++i)
+        if (fields_out[3 * i + 2] == 0.0) live.push_back(i);
+    std::vector<ShiftImage> table(refine ? live.size() : 0);
+    std::vector<long long> la(live.size()), lb(live.size());
+    for (size_t k = 0; k < live.size(); ++k) {
+        la[k] = ref_offsets[live[k]];
+        lb[k] = (long long)(k * n_pix);
+    }
+    if (refine && !live.empty()) {
+        HIP_TRY(hipMemcpyAsync(la_off, la.data(), live.size() * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(lb_off, lb.data(), live.size() * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    }
+    const size_t mov_size = float_size(mov_dtype);
+    for (int pass = 0; pass < refine && !live.empty(); ++pass) {
+        const size_t L = live.size();
+        for (size_t k = 0; k < L; ++k) {
+            const double* s = shifts_out + 2 * live[k];
+            shift_taps(s[0], 3, ny, table[k].gy, &table[k].oy, &table[k].nty);
+            shift_taps(s[1], 3, nx, table[k].gx, &table[k].ox, &table[k].ntx);
+        }
+        HIP_TRY(hipMemcpyAsync(table_dev, table.data(), L * sizeof(ShiftImage), hipMemcpyHostToDevice, ctx->stream));
+        for (size_t k = 0; k < L;) {            // runs of consecutive moving images, at most schunk at a time
+            size_t m = 1;
+            while (k + m < L && m < schunk && mov_offsets[live[k + m]] == mov_offsets[live[k]] + (int64_t)(m * n_pix)) ++m;
+            ShiftArgs a;
+            a.src = (const char*)mov_dev + (size_t)mov_offsets[live[k]] * mov_size;
+            a.dst = scratch_dev + k * n_pix;
+            a.img = table_dev + k;
+            a.part = nullptr;
+            a.n = (int)m;
+            a.ny = ny; a.nx = nx; a.floor = -HUGE_VAL;
+            HIP_TRY(shift_images(mov_dtype, RL_F64, a, tmp, nullptr, ctx->stream));
+            k += m;
+        }
+        RL_TRY(enqueue_sums_peaks(ctx, g1, ref_dev, ref_dtype, la_off, scratch_dev, RL_F64, lb_off, L, chunk1, tot, part, n_terms, peaks, nullptr));
+        HIP_TRY(hipMemcpyAsync(pk.data(), peaks, L * kPeakFields * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (size_t k = 0; k < L; ++k) reg_estimate_refine(&pk[k * kPeakFields], shifts_out + 2 * live[k], fields_out + 3 * live[k]);
+    }
     return RL_OK;
 }
 

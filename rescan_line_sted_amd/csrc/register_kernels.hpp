@@ -1,6 +1,7 @@
 // register_kernels.hpp -- registration of acquired views and frames on the device (rl_register_sums, rl_shift_images,
-// include/rlsted.h): the thread bodies of register_kernels.hip, written as host-compilable templates so that
-// the CPU tests run the very same code (tests/emu/register_emu.cpp), the host builder of the shift's taps, and the launchers.
+// rl_register_peaks, rl_register_estimate, include/rlsted.h): the thread bodies of register_kernels.hip and
+// register_peaks.hip, written as host-compilable templates so that the CPU tests run the very same code (tests/emu/register_emu.cpp,
+// tests/emu/register_peaks_emu.cpp), the host builder of the shift's taps, the estimate's host rules, and the launchers.
 //
 // SUMS  For a pair (A, B) of ny x nx images, a search radius R and a margin M >= R, with the interior I = [M, ny - M) x [M, nx - M):
 //       S_b(d) = sum_I B[y + dy][x + dx]    S_bb(d) = sum_I B[y + dy][x + dx]^2    S_ab(d) = sum_I A[y][x] B[y + dy][x + dx]
@@ -343,9 +344,127 @@ RL_HD void shift_compute(const ShiftParams<TS, TD>& p, size_t i, int by, int bx,
     sums[0] = raised; sums[1] = sum;
 }
 
-// ---- launchers (register_kernels.hip), on stream s.  dtypes: RL_F32 / RL_F64.  All pointers are device pointers.
+// ---- PEAKS -----------------------------------------------------------------------------------------------------------------------
+// The host's stages 2 - 4 (registration.ncc_surface, surface_peak) on a pair's row of totals [nd * 3 + 2] as k_register_totals
+// leaves it, bit for bit.  Per displacement, in float64, every product and quotient rounded on its own (no contraction):
+//     va = saa - sa sa / n    vb = s1 - s0 s0 / n    c = (s2 - sa s0 / n) / sqrt(va vb)
+// FLAT: !(va > 0) or !(vb > 0) for any d (nan counts): shift 0, value 0, at_limit 0, flat 1, a surface of zeros.
+// PEAK: the first maximum in row-major order.  A workgroup of 256 threads per pair, thread t takes d = t, t + 256, ... in increasing
+//   order and keeps (value, index), replaced only on a strict >; the LDS tree keeps the larger value and, on equal values, the
+//   smaller index.  PARABOLA (thread 0): the five values at the peak recomputed by the same expression (the same bits);
+//   den = (m - 2 z) + p, delta = (0.5 (m - p)) / den, 0 where den == 0; a peak on the window's border: at_limit, delta 0;
+//   shift = (double)(i - R) + delta per axis.  No atomics; nothing outside the pair's rows is read or written.
+constexpr int kPeakFields = 5;       // shift_y, shift_x, value, at_limit, flat (RL_PEAK_FIELDS)
+
+struct RegPeakArgs {
+    const double* tot;          // [pairs][nd * 3 + 2]
+    double* peaks;              // [pairs][kPeakFields]
+    double* surf;               // [pairs][nd], or nullptr
+    int pairs, R;
+    double n;                   // terms of every sum
+};
+
+RL_HD double reg_peak_va(const double* tp, int nd, double n) {
+#pragma clang fp contract(off)
+    const double sa = tp[(size_t)nd * kRegFields], saa = tp[(size_t)nd * kRegFields + 1];
+    return saa - sa * sa / n;
+}
+
+// the NCC of displacement d; vb_ok: S_bb - S_b^2 / n > 0 (false for nan)
+RL_HD double reg_ncc(const double* tp, int nd, int d, double n, bool& vb_ok) {
+#pragma clang fp contract(off)
+    const double sa = tp[(size_t)nd * kRegFields];
+    const double va = reg_peak_va(tp, nd, n);
+    const double s0 = tp[(size_t)d * kRegFields], s1 = tp[(size_t)d * kRegFields + 1], s2 = tp[(size_t)d * kRegFields + 2];
+    const double vb = s1 - s0 * s0 / n;
+    vb_ok = vb > 0.0;
+    return (s2 - sa * s0 / n) / sqrt(va * vb);
+}
+
+// thread t's first maximum over its displacements; flat: 1 when va or one of its vb is not positive
+RL_HD void reg_peak_scan(const double* tp, int nd, double n, int t, double& v, int& i, int& flat) {
+    v = -__builtin_inf();
+    i = nd;
+    flat = reg_peak_va(tp, nd, n) > 0.0 ? 0 : 1;
+    for (int d = t; d < nd; d += kRegThreads) {
+        bool ok;
+        const double c = reg_ncc(tp, nd, d, n, ok);
+        if (!ok) flat = 1;
+        if (c > v) {
+            v = c;
+            i = d;
+        }
+    }
+}
+
+// one step of the LDS tree, t < h: the larger value, on equal values the smaller index; flat is or-ed
+RL_HD void reg_peak_tree_step(double* v, int* i, int* f, int t, int h) {
+    if (t >= h) return;
+    const double ov = v[t + h];
+    const int oi = i[t + h];
+    if (ov > v[t] || (ov == v[t] && oi < i[t])) {
+        v[t] = ov;
+        i[t] = oi;
+    }
+    f[t] = f[t] | f[t + h];
+}
+
+RL_HD double reg_parabola(double m, double z, double p) {
+#pragma clang fp contract(off)
+    const double den = (m - 2.0 * z) + p;
+    return den == 0.0 ? 0.0 : (0.5 * (m - p)) / den;
+}
+
+// thread 0: the pair's fields from the tree's (value, index, flat)
+RL_HD void reg_peak_finish(const double* tp, int R, double n, double v, int i, int flat, double* out) {
+#pragma clang fp contract(off)
+    const int W = 2 * R + 1, nd = W * W;
+    if (flat) {
+        out[0] = 0.0; out[1] = 0.0; out[2] = 0.0; out[3] = 0.0; out[4] = 1.0;
+        return;
+    }
+    const int iy = i / W, ix = i - iy * W;
+    out[2] = v; out[4] = 0.0;
+    if (iy == 0 || iy == W - 1 || ix == 0 || ix == W - 1) {
+        out[0] = (double)(iy - R); out[1] = (double)(ix - R); out[3] = 1.0;
+        return;
+    }
+    bool ok;
+    const double z = reg_ncc(tp, nd, i, n, ok);
+    const double ym = reg_ncc(tp, nd, i - W, n, ok), yp = reg_ncc(tp, nd, i + W, n, ok);
+    const double xm = reg_ncc(tp, nd, i - 1, n, ok), xp = reg_ncc(tp, nd, i + 1, n, ok);
+    out[0] = (double)(iy - R) + reg_parabola(ym, z, yp);
+    out[1] = (double)(ix - R) + reg_parabola(xm, z, xp);
+    out[3] = 0.0;
+}
+
+// thread t's share of the surface [nd]: its displacements' NCC, zeros for a flat pair
+RL_HD void reg_peak_surface(const double* tp, int nd, double n, int t, int flat, double* sp) {
+    for (int d = t; d < nd; d += kRegThreads) {
+        bool ok;
+        sp[d] = flat ? 0.0 : reg_ncc(tp, nd, d, n, ok);
+    }
+}
+
+// The host's rules of an estimate (registration._estimate, coarse = None) on the fields [kPeakFields] of a pair: the first stage
+// sets the shift [2] and fields [3] = ncc, at_limit, flat; a refine pass over a pair that was not flat replaces the value and adds
+// the offset unless the pass finds the pair flat (at_limit keeps the first stage's answer).
+inline void reg_estimate_first(const double* pk, double* shift, double* fields) {
+    shift[0] = pk[0]; shift[1] = pk[1];
+    fields[0] = pk[2]; fields[1] = pk[3]; fields[2] = pk[4];
+}
+inline void reg_estimate_refine(const double* pk, double* shift, double* fields) {
+#pragma clang fp contract(off)
+    if (pk[4] != 0.0) return;
+    shift[0] = shift[0] + pk[0];
+    shift[1] = shift[1] + pk[1];
+    fields[0] = pk[2];
+}
+
+// ---- launchers (register_kernels.hip, register_peaks.hip), on stream s.  dtypes: RL_F32 / RL_F64.  All pointers are device pointers.
 #if defined(__HIPCC__) || defined(__HIP_PLATFORM_AMD__)
 hipError_t register_sums(int a_dtype, int b_dtype, const RegSumArgs& a, hipStream_t s);
+hipError_t register_peaks(const RegPeakArgs& a, hipStream_t s);
 // pass 1 (along x): src of src_dtype -> tmp float64; pass 2 (along y): tmp -> dst of dst_dtype; stats [n][2] or nullptr (then
 // a.part may be nullptr too; otherwise a.part holds n * blocks * 2 values)
 hipError_t shift_images(int src_dtype, int dst_dtype, const ShiftArgs& a, double* tmp, double* stats, hipStream_t s);

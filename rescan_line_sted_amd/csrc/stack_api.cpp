@@ -1,6 +1,7 @@
 // stack_api.cpp -- C ABI of the acquired-stack path (include/rlsted.h: rl_ingest, rl_export, rl_stack_create, rl_stack_run,
-// rl_stack_destroy, rl_device_upload_bytes): validation, the launches of ingest_kernels.hip, and the chunk pipeline that overlaps upload, iterations and
-// download.  The pipeline reaches the plan through the C ABI alone (rl_deconv_dims, rl_deconv_device_ptr,
+// rl_stack_run_registered, rl_stack_destroy, rl_device_upload_bytes): validation, the launches of ingest_kernels.hip, and the chunk
+// pipeline that overlaps upload, iterations and download -- with, in the registered run, the estimates (rl_register_estimate) and
+// the shift (rl_shift_images) between the ingest and the iterations.  The pipeline reaches the plan through the C ABI alone (rl_deconv_dims, rl_deconv_device_ptr,
 // rl_deconv_measurement_written, rl_deconv_reset_estimate, rl_deconv_iterate), as the tiled path does.  No kernel is launched on
 // bad arguments.
 #include <algorithm>
@@ -8,6 +9,7 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "ctx.hpp"
 #include "ingest_kernels.hpp"
@@ -160,6 +162,10 @@ struct rl_stack {
     size_t stats_offset() const { return round_up((size_t)B * image_bytes(), 256); }
     size_t stats_bytes() const { return ((size_t)B * V * kIngestFields + (size_t)B * kExportFields) * sizeof(double); }
     size_t out_bytes() const { return stats_offset() + stats_bytes(); }
+    // rl_stack_run_registered's buffers, allocated on first use: staging [B][V][ny][nx] and refs [V][ny][nx] of the plan's dtype,
+    // scratch B * V float64 images
+    void *staging = nullptr, *refs = nullptr;
+    double* scratch = nullptr;
 };
 
 namespace {
@@ -295,6 +301,8 @@ extern "C" int rl_stack_destroy(rl_stack* st) {
             if (e) (void)hipEventDestroy(e);
     }
     if (st->dark) (void)hipFree(st->dark);
+    for (void* p : {st->staging, st->refs, (void*)st->scratch})
+        if (p) (void)hipFree(p);
     if (st->in) (void)hipStreamDestroy(st->in);
     if (st->out) (void)hipStreamDestroy(st->out);
     delete st;
@@ -331,19 +339,133 @@ extern "C" int rl_stack_create(rl_deconv* plan, const rl_stack_params* params, r
 }
 
 namespace {
-// the chunks of a run, in the order of the header's description
-int stack_chunks(rl_stack* st, const char* raw, bool raw_direct, int n_frames, int k_iters, char* out, bool out_direct, double* ingest_stats,
-                 double* export_stats, double* times) {
+// the chunks of a run, in the order of the header's description; compute(chunk) is the context stream's part of a chunk
+template <typename Compute>
+int stack_chunks(rl_stack* st, const char* raw, bool raw_direct, int n_frames, char* out, bool out_direct, double* ingest_stats,
+                 double* export_stats, double* times, Compute compute) {
     const int chunks = (n_frames + st->B - 1) / st->B;
     auto chunk = [&](int i) { return Chunk{i * st->B, std::min(st->B, n_frames - i * st->B), &st->slot[i % 2]}; };
     RL_TRY(stack_upload(st, chunk(0), raw, raw_direct, n_frames));
     for (int i = 0; i < chunks; ++i) {
         if (i + 1 < chunks) RL_TRY(stack_upload(st, chunk(i + 1), raw, raw_direct, n_frames));   // before chunk i iterates
-        RL_TRY(stack_compute(st, chunk(i), k_iters, times));
+        RL_TRY(compute(chunk(i)));
         RL_TRY(stack_download(st, chunk(i), out, out_direct));                                   // while chunk i + 1 iterates
         if (i > 0) RL_TRY(stack_drain(st, chunk(i - 1), out, out_direct, ingest_stats, export_stats, times));
     }
     return stack_drain(st, chunk(chunks - 1), out, out_direct, ingest_stats, export_stats, times);
+}
+
+// a failed run: copies may still be in flight -- an upload reading the caller's page-locked raw array, a download writing the
+// caller's page-locked out array: they are waited for before the caller hears of the failure and may let go of either (statuses
+// ignored: the first failure is the one reported)
+int stack_failed(rl_stack* st, int rc) {
+    const std::string why = rl::last_error();
+    (void)hipStreamSynchronize(st->in);
+    (void)hipStreamSynchronize(st->ctx->stream);
+    (void)hipStreamSynchronize(st->out);
+    (void)hipGetLastError();
+    return fail(rc, why);
+}
+
+// ---- the registered run --------------------------------------------------------------------------------------------------------
+struct RegRun {
+    const rl_stack_register* rp;
+    const double* given;            // [F][V][2] or nullptr
+    rl_stack_register_out* ro;
+    bool estimating;
+    int M;
+    double est_ms = 0.0;
+    std::vector<double> view_shift; // [V][2]
+};
+
+// the pairs (reference offset, moving offset) estimated in one rl_register_estimate; shifts [n][2] and fields [n][3] come back
+int stack_estimate(rl_stack* st, RegRun& r, const void* ref, const void* mov, const std::vector<int64_t>& ro, const std::vector<int64_t>& mo,
+                   std::vector<double>& shifts, std::vector<double>& fields) {
+    const int n = (int)mo.size();
+    shifts.assign((size_t)n * 2, 0.0);
+    fields.assign((size_t)n * 3, 0.0);
+    return rl_register_estimate(st->ctx, ref, st->dtype, ro.data(), mov, st->dtype, mo.data(), n, st->ny, st->nx, r.rp->max_shift, r.M,
+                                r.rp->refine, r.rp->refine > 0 ? st->scratch : nullptr, shifts.data(), fields.data(), nullptr);
+}
+
+// chunk c on the context's stream: ingest into the staging buffer, the estimates, the shift into the plan's measurement, the
+// iterations from ones, export
+int stack_compute_registered(rl_stack* st, const Chunk& c, int k_iters, RegRun& r, double* times) {
+    rl_stack::Slot& sl = *c.sl;
+    hipStream_t s = st->ctx->stream;
+    const rl_stack_params& p = st->prm;
+    const bool by_view = p.order == RL_ORDER_VIEW_FRAME;
+    const int V = st->V, B = st->B;
+    const size_t n_pix = (size_t)st->ny * st->nx, esz = st->dtype == RL_F32 ? sizeof(float) : sizeof(double);
+    double* stats = (double*)(sl.dev_out + st->stats_offset());
+    HIP_TRY(hipStreamWaitEvent(s, sl.uploaded, 0));
+    if (sl.used) HIP_TRY(hipStreamWaitEvent(s, sl.downloaded, 0));
+    HIP_TRY(hipEventRecord(sl.c0, s));
+    const int rc = rl_ingest(st->ctx, sl.dev_raw, p.raw_dtype, c.nt * V, p.src_ny, p.src_pitch, p.y0, p.x0, by_view ? 1 : V, by_view ? c.nt : 1,
+                             B, c.nt, V, st->ny, st->nx, st->dark, p.offset, p.gain, p.epsilon, p.saturation, st->staging, st->dtype, stats);
+    HIP_TRY(hipEventRecord(sl.freed, s));
+    sl.used = true;
+    RL_TRY(rc);
+    std::vector<double> chunk((size_t)B * V * 2, 0.0);              // (fillers: no shift)
+    if (r.given) {
+        std::copy(r.given + (size_t)c.first * V * 2, r.given + ((size_t)c.first + c.nt) * V * 2, chunk.begin());
+    } else {
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<int64_t> ro, mo;
+        std::vector<double> sh, fl;
+        if (c.first == 0) {
+            HIP_TRY(hipMemcpyAsync(st->refs, st->staging, V * n_pix * esz, hipMemcpyDeviceToDevice, s));
+            if (r.rp->views && V > 1) {
+                for (int v = 1; v < V; ++v) {
+                    ro.push_back(0);
+                    mo.push_back((int64_t)(v * n_pix));
+                }
+                RL_TRY(stack_estimate(st, r, st->refs, st->refs, ro, mo, sh, fl));
+                for (int v = 1; v < V; ++v) {
+                    std::copy(&sh[(v - 1) * 2], &sh[(v - 1) * 2] + 2, &r.view_shift[(size_t)v * 2]);
+                    std::copy(&fl[(v - 1) * 3], &fl[(v - 1) * 3] + 3, r.ro->view_fields + (size_t)v * 3);
+                }
+                std::copy(r.view_shift.begin(), r.view_shift.end(), r.ro->view_shifts);
+            }
+        }
+        if (r.rp->frames) {
+            ro.clear();
+            mo.clear();
+            std::vector<int> idx;                                    // f * V + v of each pair; frame 0 is its own reference
+            for (int f = 0; f < c.nt; ++f)
+                for (int v = 0; v < V; ++v)
+                    if (c.first + f > 0) {
+                        ro.push_back((int64_t)(v * n_pix));
+                        mo.push_back((int64_t)(((size_t)f * V + v) * n_pix));
+                        idx.push_back(f * V + v);
+                    }
+            if (!idx.empty()) {
+                RL_TRY(stack_estimate(st, r, st->refs, st->staging, ro, mo, sh, fl));
+                for (size_t k = 0; k < idx.size(); ++k) {
+                    chunk[(size_t)idx[k] * 2] = sh[k * 2];
+                    chunk[(size_t)idx[k] * 2 + 1] = sh[k * 2 + 1];
+                    std::copy(&fl[k * 3], &fl[k * 3] + 3, r.ro->fields + ((size_t)c.first * V + idx[k]) * 3);
+                }
+            }
+        }
+        for (int f = 0; f < c.nt; ++f)
+            for (size_t k = 0; k < (size_t)V * 2; ++k) chunk[(size_t)f * V * 2 + k] = chunk[(size_t)f * V * 2 + k] + r.view_shift[k];
+        r.est_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    std::vector<double> sst((size_t)B * V * 2);
+    RL_TRY(rl_shift_images(st->ctx, st->staging, st->dtype, B * V, st->ny, st->nx, chunk.data(), r.rp->interp, p.epsilon, st->meas, st->dtype,
+                           sst.data()));
+    std::copy(chunk.begin(), chunk.begin() + (size_t)c.nt * V * 2, r.ro->shifts + (size_t)c.first * V * 2);
+    for (size_t i = 0; i < (size_t)c.nt * V; ++i) r.ro->raised[(size_t)c.first * V + i] = sst[i * 2];
+    RL_TRY(rl_deconv_measurement_written(st->plan));
+    RL_TRY(rl_deconv_reset_estimate(st->plan));
+    RL_TRY(rl_deconv_iterate(st->plan, k_iters));
+    float up_ms = 0;
+    HIP_TRY(hipEventElapsedTime(&up_ms, sl.up0, sl.uploaded));
+    times[1] += up_ms;
+    RL_TRY(rl_export(st->ctx, st->est, st->dtype, B, st->ny, st->nx, p.out_scale, sl.dev_out, p.out_dtype, stats + (size_t)B * V * kIngestFields));
+    HIP_TRY(hipEventRecord(sl.exported, s));
+    return RL_OK;
 }
 }  // namespace
 
@@ -356,21 +478,58 @@ extern "C" int rl_stack_run(rl_stack* st, const void* raw_host, int n_frames, in
     const size_t raw_total = (size_t)n_frames * st->V * st->frame_elems() * raw_size(st->prm.raw_dtype);
     const bool raw_direct = host_is_pinned(raw_host, raw_total), out_direct = host_is_pinned(out_host, (size_t)n_frames * st->image_bytes());
     double times[4] = {0, 0, 0, 0};
-    const int rc = stack_chunks(st, (const char*)raw_host, raw_direct, n_frames, k_iters, (char*)out_host, out_direct, ingest_stats,
-                                export_stats, times);
-    if (rc != RL_OK) {
-        // Copies may still be in flight -- an upload reading the caller's page-locked raw array, a download writing the caller's
-        // page-locked out array: they are waited for before the caller hears of the failure and may let go of either (statuses
-        // ignored: the first failure is the one reported).
-        const std::string why = rl::last_error();
-        (void)hipStreamSynchronize(st->in);
-        (void)hipStreamSynchronize(st->ctx->stream);
-        (void)hipStreamSynchronize(st->out);
-        (void)hipGetLastError();
-        return fail(rc, why);
-    }
+    const int rc = stack_chunks(st, (const char*)raw_host, raw_direct, n_frames, (char*)out_host, out_direct, ingest_stats, export_stats, times,
+                                [&](const Chunk& c) { return stack_compute(st, c, k_iters, times); });
+    if (rc != RL_OK) return stack_failed(st, rc);
     times[0] = ms_since(t0);
     if (times_ms) std::copy(times, times + 4, times_ms);
+    return RL_OK;
+}
+
+extern "C" int rl_stack_run_registered(rl_stack* st, const void* raw_host, int n_frames, int k_iters, const rl_stack_register* rp,
+                                       const double* given_shifts, void* out_host, double* ingest_stats, double* export_stats,
+                                       rl_stack_register_out* register_out, double* times_ms) {
+    if (!st || !raw_host || !rp || !out_host || !register_out) return fail(RL_ERR_INVALID, "NULL argument");
+    rl_stack_register_out& ro = *register_out;
+    if (!ro.shifts || !ro.fields || !ro.view_shifts || !ro.view_fields || !ro.raised) return fail(RL_ERR_INVALID, "NULL array in register_out");
+    if (n_frames < 1 || k_iters < 0) return fail(RL_ERR_INVALID, "n_frames must be at least 1 and k_iters at least 0");
+    if (rp->interp != 1 && rp->interp != 3) return fail(RL_ERR_INVALID, "interp must be 1 or 3");
+    const int V = st->V;
+    if (given_shifts) {
+        for (size_t i = 0; i < (size_t)n_frames * V * 2; ++i)
+            if (!std::isfinite(given_shifts[i])) return fail(RL_ERR_INVALID, "the given shifts must be finite");
+    }
+    RegRun r;
+    r.rp = rp; r.given = given_shifts; r.ro = &ro; r.M = rp->max_shift + 2;
+    r.estimating = !given_shifts && (rp->views || rp->frames);
+    r.view_shift.assign((size_t)V * 2, 0.0);
+    if (r.estimating) {
+        if (rp->max_shift < 1 || rp->max_shift > 32) return fail(RL_ERR_INVALID, "max_shift must lie in 1 .. 32");
+        if (rp->refine < 0) return fail(RL_ERR_INVALID, "refine must be at least 0");
+        if (st->ny - 2 * r.M < 8 || st->nx - 2 * r.M < 8) return fail(RL_ERR_INVALID, "the window leaves no 8 x 8 interior inside a margin of max_shift + 2");
+    }
+    HIP_TRY(hipSetDevice(st->ctx->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t n_pix = (size_t)st->ny * st->nx, esz = st->dtype == RL_F32 ? sizeof(float) : sizeof(double);
+    if (!st->staging) HIP_TRY(hipMalloc(&st->staging, (size_t)st->B * V * n_pix * esz));
+    if (!st->refs) HIP_TRY(hipMalloc(&st->refs, (size_t)V * n_pix * esz));
+    if (r.estimating && rp->refine > 0 && !st->scratch) HIP_TRY(hipMalloc((void**)&st->scratch, (size_t)st->B * V * n_pix * sizeof(double)));
+    std::fill(ro.shifts, ro.shifts + (size_t)n_frames * V * 2, 0.0);
+    std::fill(ro.fields, ro.fields + (size_t)n_frames * V * 3, 0.0);
+    std::fill(ro.view_shifts, ro.view_shifts + (size_t)V * 2, 0.0);
+    std::fill(ro.view_fields, ro.view_fields + (size_t)V * 3, 0.0);
+    std::fill(ro.raised, ro.raised + (size_t)n_frames * V, 0.0);
+    const size_t raw_total = (size_t)n_frames * V * st->frame_elems() * raw_size(st->prm.raw_dtype);
+    const bool raw_direct = host_is_pinned(raw_host, raw_total), out_direct = host_is_pinned(out_host, (size_t)n_frames * st->image_bytes());
+    double times[4] = {0, 0, 0, 0};
+    const int rc = stack_chunks(st, (const char*)raw_host, raw_direct, n_frames, (char*)out_host, out_direct, ingest_stats, export_stats, times,
+                                [&](const Chunk& c) { return stack_compute_registered(st, c, k_iters, r, times); });
+    if (rc != RL_OK) return stack_failed(st, rc);
+    times[0] = ms_since(t0);
+    if (times_ms) {
+        std::copy(times, times + 4, times_ms);
+        times_ms[4] = r.est_ms;
+    }
     return RL_OK;
 }
 

@@ -16,12 +16,13 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _lib, stack
 from ._lib import DTYPES, check, lib
-from .stack import INGEST_FIELDS, ORDERS, CameraModel, _stack_shape, raw_code
+from .stack import EXPORT_FIELDS, INGEST_FIELDS, ORDERS, OUT_DTYPES, CameraModel, _stack_shape, raw_code
 
 MAX_RADIUS = 32                       # rl_register_sums
 XCORR_FIELDS = 7                      # rl_register_xcorr
+PEAK_FIELDS = 5                       # rl_register_peaks
 XCORR_MAX_LENGTH = 1152               # the largest transform length of the coarse stage: image side + radius
 _NP = {'f32': np.float32, 'f64': np.float64}
 _I64P = ctypes.POINTER(ctypes.c_int64)
@@ -103,6 +104,16 @@ def _estimate(dev, ref, ref_offsets, mov, mov_offsets, ny, nx, max_shift, refine
     info = {'ncc': value, 'at_limit': at_limit, 'flat': flat}
     if surfaces:
         info['surfaces'] = np.stack(kept)
+    return shifts, info
+
+
+def _estimate_on_device(dev, ref, ref_offsets, mov, mov_offsets, ny, nx, max_shift, refine, margin, scratch, surfaces=False):
+    """_estimate (coarse=None) in one call through dev.estimate (rl_register_estimate): the NCC, the peaks and the parabolas on the
+    device, the refine passes' offsets added on the host by the same rules; the same bits as _estimate."""
+    shifts, fields, C = dev.estimate(ref, ref_offsets, mov, mov_offsets, ny, nx, max_shift, margin, refine, scratch, surfaces)
+    info = {'ncc': fields[:, 0].copy(), 'at_limit': fields[:, 1] != 0.0, 'flat': fields[:, 2] != 0.0}
+    if surfaces:
+        info['surfaces'] = C.reshape(len(mov_offsets), 2 * max_shift + 1, 2 * max_shift + 1)
     return shifts, info
 
 
@@ -253,6 +264,25 @@ class _Device:
                                    mo.ctypes.data_as(_I64P), n, ny, nx, R, M, _lib.ptr(S), _lib.ptr(A)))
         return S, A
 
+    def peaks(self, tot, n_pairs, R, n_terms, surfaces=False):
+        """rl_register_peaks on a float64 device buffer of sums rows [n_pairs][(2R+1)^2 * 3 + 2]: the fields [n_pairs][5]; with
+        surfaces=True (fields, surfaces [n_pairs][(2R+1)^2])."""
+        P = np.empty((n_pairs, PEAK_FIELDS))
+        C = np.empty((n_pairs, (2 * R + 1) ** 2)) if surfaces else None
+        check(lib.rl_register_peaks(self.ctx.handle, tot.ptr, n_pairs, R, float(n_terms), _lib.ptr(P), None if C is None else _lib.ptr(C)))
+        return (P, C) if surfaces else P
+
+    def estimate(self, ref, ref_offsets, mov, mov_offsets, ny, nx, R, M, refine, scratch, surfaces=False):
+        """rl_register_estimate: (shifts [pairs][2], fields [pairs][3] = ncc, at_limit, flat, surfaces [pairs][(2R+1)^2] or None)."""
+        n = len(mov_offsets)
+        ro, mo = np.ascontiguousarray(ref_offsets, dtype=np.int64), np.ascontiguousarray(mov_offsets, dtype=np.int64)
+        shifts, fields = np.empty((n, 2)), np.empty((n, 3))
+        C = np.empty((n, (2 * R + 1) ** 2)) if surfaces else None
+        check(lib.rl_register_estimate(self.ctx.handle, ref.ptr, DTYPES[ref.dtype], ro.ctypes.data_as(_I64P), mov.ptr, DTYPES[mov.dtype],
+                                       mo.ctypes.data_as(_I64P), n, ny, nx, R, M, refine, None if scratch is None else scratch.ptr,
+                                       _lib.ptr(shifts), _lib.ptr(fields), None if C is None else _lib.ptr(C)))
+        return shifts, fields, C
+
     def xcorr(self, ref, ref_offsets, mov, mov_offsets, ny, nx, R, surfaces=False):
         """rl_register_xcorr: the fields [pairs][7]; with surfaces=True (fields, v [pairs][2R+1][2R+1] float32)."""
         n = len(mov_offsets)
@@ -354,7 +384,7 @@ def coarse_shifts(images, reference, radius, device=None, surfaces=False):
         dev.close()
 
 
-def estimate_shifts(images, reference, max_shift=8, refine=1, margin=None, device=None, surfaces=False, coarse=None):
+def estimate_shifts(images, reference, max_shift=8, refine=1, margin=None, device=None, surfaces=False, coarse=None, device_peaks=False):
     """The translation of every image relative to its reference.  images: (N, ny, nx) or (ny, nx), float32 or float64; reference:
     (ny, nx), shared, or (N, ny, nx).  max_shift: the search radius in pixels, 1 .. 32.  refine: passes that shift the image by
     the current estimate (order 3) and add the parabola offset of a 3 x 3 window.  margin: pixels at every border kept out of the
@@ -367,7 +397,11 @@ def estimate_shifts(images, reference, max_shift=8, refine=1, margin=None, devic
     total, so no image is interpolated twice.  Pair i keeps 8 ceil(|c_i| / 8) + max_shift + 2 pixels out of its sums (the
     mirror-filled band of the copy), so ny - 2 (Rc + max_shift + 2) >= 8 is required, likewise nx, and margin cannot be given.
     at_limit then says that the PROPOSAL was wrong (the fine peak lay on the border of the window around c), not that the drift was
-    large.  info gains 'coarse' (N, 2) int64, 'coarse_value', 'coarse_snr', 'coarse_flat' (coarse_shifts)."""
+    large.  info gains 'coarse' (N, 2) int64, 'coarse_value', 'coarse_snr', 'coarse_flat' (coarse_shifts).
+    device_peaks: True -- the NCC, the first maximum and the parabola on the device (rl_register_estimate: the whole estimate in one
+    call, 5 doubles per pair come down instead of the sums); the same bits as the default.  Not with coarse."""
+    if device_peaks and coarse is not None:
+        raise ValueError('device_peaks serves the window alone: coarse must be None')
     images, dt, reference, rdt = _pairs_on_device(images, reference)
     N, ny, nx = images.shape
     given_margin = margin
@@ -380,8 +414,9 @@ def estimate_shifts(images, reference, max_shift=8, refine=1, margin=None, devic
         dev.upload(ref, reference)
         scratch = dev.alloc(images.size, 'f64') if refine or coarse is not None else None
         n_pix = ny * nx
-        return _estimate(dev, ref, [i * n_pix if reference.ndim == 3 else 0 for i in range(N)], mov, [i * n_pix for i in range(N)], ny, nx,
-                         max_shift, refine, margin, scratch, surfaces, coarse)
+        args = (dev, ref, [i * n_pix if reference.ndim == 3 else 0 for i in range(N)], mov, [i * n_pix for i in range(N)], ny, nx,
+                max_shift, refine, margin, scratch, surfaces)
+        return _estimate_on_device(*args) if device_peaks else _estimate(*args, coarse)
     finally:
         dev.close()
 
@@ -418,7 +453,7 @@ def shift_images(images, shifts, order=3, floor=None, device=None):
 
 def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame-view', roi=None, dtype='f32', batch=None, shifts=None,
                                 register=('views', 'frames'), max_shift=8, refine=1, interp=3, acceleration=None, tv_lambda=None,
-                                tv_epsilon=0.1, device=None, coarse=None):
+                                tv_epsilon=0.1, device=None, coarse=None, pipeline=False, out_dtype=None, out_scale=1.0, out=None):
     """deconvolve_stack with every image registered on the device before the iterations.  raw, camera, order, roi, dtype, batch,
     acceleration, tv_lambda, tv_epsilon: exactly those of deconvolve_stack.
     register: 'frames' in it -- image (f, v) is registered to image (0, v), the same PSF: drift over time; 'views' in it -- image
@@ -431,12 +466,18 @@ def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame
     once for info['shifts'] and again with shifts=np.rint(...) and interp=1, which only moves pixels.
     Per chunk of `batch` frames, on the context's stream: upload of the raw bytes, rl_ingest into a staging buffer, the estimate,
     rl_shift_images (floor = camera.epsilon) into the plan's measurement buffer, the iterations from ones, download.  The ingested
-    images of frame 0 stay on the device as the references for the whole call.  There is NO overlap of transfers with the iterations
-    and no u16 export in this path: the estimates come back as float64.
-    Returns (estimates (F, ny, nx) float64, info); info: the ingest statistics of deconvolve_stack ('level', 'clipped', 'saturated',
-    'invalid', each (F, V)), 'shifts' (F, V, 2) as applied, 'ncc', 'at_limit', 'flat' (F, V) of the frame estimates, 'view_ncc',
-    'view_at_limit', 'view_flat' (V,) of the view estimates, 'raised' (F, V) pixels raised to camera.epsilon by the shift, 'unresolved',
-    'strategy', 'chunks', 'batch'."""
+    images of frame 0 stay on the device as the references for the whole call.  With pipeline=False (the default) there is NO overlap
+    of transfers with the iterations and no u16 export: the estimates come back as float64.
+    pipeline=True: the same steps in the overlapped chunk pipeline of deconvolve_stack (rl_stack_run_registered): uploads and
+    downloads on copy streams beside the estimates and the iterations, the NCC and the peaks on the device (rl_register_estimate), and
+    the narrow export -- out_dtype 'f32' (default), 'f64' or 'u16', out_scale and out exactly as for deconvolve_stack (page-locked
+    raw and out arrays are copied to and from directly).  The shifts, the fields and, with out_dtype='f64', the estimates are the bits
+    of pipeline=False.  Not with coarse; out_dtype, out_scale and out only with pipeline=True.
+    Returns (estimates (F, ny, nx) float64 -- pipeline: of out_dtype --, info); info: the ingest statistics of deconvolve_stack
+    ('level', 'clipped', 'saturated', 'invalid', each (F, V)), 'shifts' (F, V, 2) as applied, 'ncc', 'at_limit', 'flat' (F, V) of the
+    frame estimates, 'view_ncc', 'view_at_limit', 'view_flat' (V,) of the view estimates, 'raised' (F, V) pixels raised to
+    camera.epsilon by the shift, 'unresolved', 'strategy', 'chunks', 'batch'; pipeline: also 'clamped' (F,) as deconvolve_stack and
+    'times_ms' (wall_ms, upload_ms, compute_ms, download_ms, estimate_ms)."""
     _lib.tv_params(tv_lambda, tv_epsilon)
     _lib.accel_mode(acceleration)
     if dtype not in DTYPES:
@@ -448,6 +489,14 @@ def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame
     register = (register,) if isinstance(register, str) else tuple(register)
     if any(r not in ('views', 'frames') for r in register):
         raise ValueError("register: any of 'views', 'frames'; got %r" % (register,))
+    if pipeline:
+        if coarse is not None:
+            raise ValueError('pipeline=True serves the window alone: coarse must be None')
+        out_dtype = 'f32' if out_dtype is None else out_dtype
+        if out_dtype not in OUT_DTYPES:
+            raise ValueError("out_dtype must be 'f32', 'f64' or 'u16'; got %r" % (out_dtype,))
+    elif out_dtype is not None or out_scale != 1.0 or out is not None:
+        raise ValueError('out_dtype, out_scale and out need pipeline=True')
     code = raw_code(raw)
     raw = np.ascontiguousarray(raw)
     if 0 in raw.shape:
@@ -473,6 +522,10 @@ def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame
         max_shift, refine, margin = _check_search(ny, nx, max_shift, refine, None)
         coarse = _check_coarse(ny, nx, coarse, max_shift, None)
     estimating = given is None and bool(register)
+    if pipeline:
+        return _registered_pipeline(raw, code, psfs, int(iterations), camera, order, (sy, sx), (y0, x0, ny, nx), dtype, batch, given, register,
+                                    max_shift, refine, interp, acceleration, tv_lambda, tv_epsilon,
+                                    _lib.DEFAULT_DEVICE if device is None else device, out_dtype, out_scale, out)
     frames = raw.reshape((F, V, sy, sx) if order == 'frame-view' else (V, F, sy, sx))
     n_pix, img_bytes = ny * nx, sy * sx * raw.dtype.itemsize
     dev = _Device(psfs, batch, (ny, nx), dtype, _lib.DEFAULT_DEVICE if device is None else device, acceleration, tv_lambda, tv_epsilon)
@@ -539,6 +592,48 @@ def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame
                 'unresolved': dev.unresolved(), 'strategy': dev.strategy(), 'chunks': -(-F // batch), 'batch': batch}
         if use_coarse is not None:
             info.update({'coarse': coarse_c, 'coarse_snr': coarse_snr, 'view_coarse': view_coarse, 'view_coarse_snr': view_coarse_snr})
+        return out, info
+    finally:
+        dev.close()
+
+
+class _RegisterParams(ctypes.Structure):      # rl_stack_register of include/rlsted.h
+    _fields_ = [('views', ctypes.c_int), ('frames', ctypes.c_int), ('max_shift', ctypes.c_int), ('refine', ctypes.c_int),
+                ('interp', ctypes.c_int)]
+
+
+class _RegisterOut(ctypes.Structure):         # rl_stack_register_out
+    _fields_ = [(k, ctypes.POINTER(ctypes.c_double)) for k in ('shifts', 'fields', 'view_shifts', 'view_fields', 'raised')]
+
+
+def _registered_pipeline(raw, code, psfs, iterations, camera, order, sensor, window, dtype, batch, given, register, max_shift, refine, interp,
+                         acceleration, tv_lambda, tv_epsilon, device, out_dtype, out_scale, out):
+    """deconvolve_stack_registered(pipeline=True) after its checks: one rl_stack_run_registered over the whole stack."""
+    y0, x0, ny, nx = window
+    V = len(psfs)
+    F = _stack_shape(raw, V, order)[0]
+    out_code, out_np = OUT_DTYPES[out_dtype]
+    if out is None:
+        out = np.empty((F, ny, nx), dtype=out_np)
+    elif out.dtype != out_np or not out.flags.c_contiguous or out.shape != (F, ny, nx):
+        raise ValueError('out must be a C-contiguous %s array of shape %s' % (np.dtype(out_np).name, (F, ny, nx)))
+    dev = stack._Device(psfs, batch, (ny, nx), dtype, device, acceleration, tv_lambda, tv_epsilon)
+    try:
+        dev.open(code, ORDERS[order], sensor, (y0, x0), camera, out_code, out_scale)
+        ingest_stats, export_stats, times = np.zeros((F, V, INGEST_FIELDS)), np.zeros((F, EXPORT_FIELDS)), np.zeros(5)
+        shifts, fields, raised = np.zeros((F, V, 2)), np.zeros((F, V, 3)), np.zeros((F, V))
+        view_shifts, view_fields = np.zeros((V, 2)), np.zeros((V, 3))
+        params = _RegisterParams(int('views' in register), int('frames' in register), int(max_shift), int(refine), int(interp))
+        reg_out = _RegisterOut(*[_lib.ptr(a) for a in (shifts, fields, view_shifts, view_fields, raised)])
+        dev.run_registered(raw, F, iterations, params, None if given is None else np.ascontiguousarray(given, dtype=np.float64), out,
+                           ingest_stats, export_stats, reg_out, times)
+        info = {'level': ingest_stats[:, :, 0].copy(), 'clipped': ingest_stats[:, :, 1].astype(np.int64),
+                'saturated': ingest_stats[:, :, 2].astype(np.int64), 'invalid': ingest_stats[:, :, 3].astype(np.int64),
+                'shifts': shifts, 'ncc': fields[:, :, 0].copy(), 'at_limit': fields[:, :, 1] != 0.0, 'flat': fields[:, :, 2] != 0.0,
+                'view_ncc': view_fields[:, 0].copy(), 'view_at_limit': view_fields[:, 1] != 0.0, 'view_flat': view_fields[:, 2] != 0.0,
+                'raised': raised.astype(np.int64), 'unresolved': dev.unresolved(), 'strategy': dev.strategy(), 'chunks': -(-F // batch),
+                'batch': batch, 'clamped': export_stats[:, 1].astype(np.int64),
+                'times_ms': dict(zip(('wall_ms', 'upload_ms', 'compute_ms', 'download_ms', 'estimate_ms'), times.tolist()))}
         return out, info
     finally:
         dev.close()

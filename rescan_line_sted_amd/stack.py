@@ -88,6 +88,13 @@ class _Device:
         check(lib.rl_stack_run(self.stack, raw.ctypes.data_as(ctypes.c_void_p), frames, iterations, out.ctypes.data_as(ctypes.c_void_p),
                                _lib.ptr(ingest_stats), _lib.ptr(export_stats), _lib.ptr(times)))
 
+    def run_registered(self, raw, frames, iterations, params, given, out, ingest_stats, export_stats, register_out, times):
+        """All frames through the plan with the registration in front (rl_stack_run_registered): params an rl_stack_register,
+        given None or (F, V, 2) float64, register_out an rl_stack_register_out; fills out, the statistics and the five times."""
+        check(lib.rl_stack_run_registered(self.stack, raw.ctypes.data_as(ctypes.c_void_p), frames, iterations, ctypes.byref(params),
+                                          None if given is None else _lib.ptr(given), out.ctypes.data_as(ctypes.c_void_p),
+                                          _lib.ptr(ingest_stats), _lib.ptr(export_stats), ctypes.byref(register_out), _lib.ptr(times)))
+
     def unresolved(self):
         return self.plan.unresolved()
 

@@ -15,7 +15,13 @@
 each warmed once, then --repeats samples: the median and the spread (min, max) of a host clock around work that ends in a device
 synchronise.
 
-    python tools/gpu/register_throughput.py [--repeats 5] [--frames 1024] [--out profiles/register/throughput.json]
+With --pipeline, instead (profiles/register_pipeline/throughput.json):
+  estimate      the estimate alone on 256 pairs of 512 x 512 at R = 4 / 8 / 16, refine 1: the host's peak search against
+                device_peaks (rl_register_estimate), alternating
+  pipeline      the end-to-end workload above, 1 and 4 views, max_shift 8, refine 1, page-locked raw and out arrays: the host loop,
+                the pipeline with f64 output, the pipeline with u16 output and deconvolve_stack, in one process in alternating order
+
+    python tools/gpu/register_throughput.py [--repeats 5] [--frames 1024] [--pipeline] [--out profiles/register/throughput.json]
 """
 import argparse
 import json
@@ -129,16 +135,96 @@ def end_to_end(reg, stack, _lib, F, B, repeats):
     return rows
 
 
+def alternating(legs, repeats):
+    """Every leg warmed once, then `repeats` rounds in which each leg runs once, the order rotated from round to round (a drift of
+    the machine over the run falls on every leg alike); wall times of calls that end in a synchronise."""
+    names = list(legs)
+    for name in names:
+        legs[name]()
+    out = {name: [] for name in names}
+    for rep in range(repeats):
+        for name in names[rep % len(names):] + names[:rep % len(names)]:
+            t0 = time.perf_counter()
+            legs[name]()
+            out[name].append((time.perf_counter() - t0) * 1e3)
+    return {name: {'ms': float(np.median(v)), 'min_ms': float(min(v)), 'max_ms': float(max(v)), 'samples': len(v)} for name, v in out.items()}
+
+
+def pipeline_rows(reg, stack, _lib, F, B, repeats):
+    """The README's workload (F uint16 frames of 512 x 512, K = 20, batch B, page-locked, max_shift 8, refine 1), 1 and 4 views:
+    deconvolve_stack_registered's host loop, the pipeline with f64 output, the pipeline with u16 output, and deconvolve_stack, in
+    one process in alternating order."""
+    import bench
+    psf = bench.workload(N)[1]
+    rows = {}
+    for V in (1, 4):
+        psfs = [psf[0]] * V if V > 1 else psf
+        raw = _lib.pinned_empty((F, V, N, N), np.uint16)
+        raw[:] = frames_u16(F, V)
+        out64, out16 = _lib.pinned_empty((F, N, N), np.float64), _lib.pinned_empty((F, N, N), np.uint16)
+        cam = stack.CameraModel(dark=DARK, gain=GAIN, saturation=65535)
+        kw = dict(camera=cam, dtype='f32', batch=B, max_shift=8, refine=1)
+        legs = {'host_loop': lambda: reg.deconvolve_stack_registered(raw, psfs, K, **kw),
+                'pipeline_f64': lambda: reg.deconvolve_stack_registered(raw, psfs, K, pipeline=True, out_dtype='f64', out=out64, **kw),
+                'pipeline_u16': lambda: reg.deconvolve_stack_registered(raw, psfs, K, pipeline=True, out_dtype='u16', out=out16, **kw),
+                'deconvolve_stack': lambda: stack.deconvolve_stack(raw, psfs, K, camera=cam, dtype='f32', out_dtype='u16', batch=B, out=out16)}
+        row = alternating(legs, repeats)
+        _, info = reg.deconvolve_stack_registered(raw, psfs, K, pipeline=True, out_dtype='u16', out=out16, **kw)
+        row.update({'frames': F, 'batch': B, 'views': V, 'pipeline_times_ms': info['times_ms']})
+        for name in legs:
+            row[name]['frames_per_s'] = F / row[name]['ms'] * 1e3
+        row['pipeline_u16_over_host_loop'] = row['host_loop']['ms'] / row['pipeline_u16']['ms']
+        rows['views=%d' % V] = row
+        print(json.dumps({'views=%d' % V: row}), flush=True)
+        del raw, out64, out16
+    return rows
+
+
+def estimate_rows(reg, repeats):
+    """The estimate alone, 256 pairs of 512 x 512 f32 against one reference, R = 4 / 8 / 16, margin R + 2, refine 1: the host's peak
+    search (the sums come down) against device_peaks (5 doubles per pair come down), alternating."""
+    dev = reg._Device(device=0)
+    rng = np.random.default_rng(3)
+    rows = {}
+    try:
+        imgs = dev.alloc((PAIRS + 1) * N * N, 'f32')
+        dev.upload(imgs, (rng.random((PAIRS + 1, N, N)) * 100.0).astype(np.float32))
+        scratch = dev.alloc(PAIRS * N * N, 'f64')
+        ref_off, mov_off = [0] * PAIRS, [(k + 1) * N * N for k in range(PAIRS)]
+        for R in (4, 8, 16):
+            args = (dev, imgs, ref_off, imgs, mov_off, N, N, R, 1, R + 2, scratch)
+            legs = {'host_peaks': lambda: reg._estimate(*args), 'device_peaks': lambda: reg._estimate_on_device(*args)}
+            row = alternating(legs, repeats)
+            row.update({'pairs': PAIRS, 'R': R, 'refine': 1, 'host_over_device': row['host_peaks']['ms'] / row['device_peaks']['ms']})
+            rows['R=%d' % R] = row
+    finally:
+        dev.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--frames', type=int, default=1024)
     ap.add_argument('--batch', type=int, default=64)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'register', 'throughput.json'))
+    ap.add_argument('--pipeline', action='store_true', help='only the pipeline and estimate legs (default output profiles/register_pipeline/)')
+    ap.add_argument('--out', default=None)
     args = ap.parse_args()
     from rescan_line_sted_amd import _lib, registration as reg, stack
     if _lib.device_count() < 1:
         sys.exit('no GPU: the throughput is not measured')
+    if args.pipeline:
+        res = {'image': [N, N], 'iterations': K, 'repeats': args.repeats}
+        res['estimate'] = estimate_rows(reg, args.repeats)
+        print(json.dumps(res['estimate']), flush=True)
+        res['pipeline'] = pipeline_rows(reg, stack, _lib, args.frames, args.batch, args.repeats)
+        out = args.out or os.path.join(ROOT, 'profiles', 'register_pipeline', 'throughput.json')
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, 'w') as f:
+            json.dump(res, f, indent=1)
+            f.write('\n')
+        return
+    args.out = args.out or os.path.join(ROOT, 'profiles', 'register', 'throughput.json')
     res = {'image': [N, N], 'iterations': K, 'repeats': args.repeats}
     res['sums'] = sums_rows(reg, args.repeats)
     print(json.dumps(res['sums']), flush=True)
