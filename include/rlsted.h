@@ -827,6 +827,36 @@ int rl_register_estimate(rl_ctx* ctx, const void* ref_dev, int ref_dtype, const 
                          const int64_t* mov_offsets, int n_pairs, int ny, int nx, int R, int M, int refine, double* scratch_dev,
                          double* shifts_out, double* fields_out, double* surface_out);
 
+/* ---- bead images: the peak finder of the PSF measurement ----
+ * rl_find_peaks: the candidates of n images of ny x nx, src_dtype (RL_F32 / RL_F64) at the ELEMENT offsets offsets[i] of src_dev
+ * (host array [n]; any offset >= 0, no alignment assumed).  taps: host float64 w[0 .. 2 h], 0 <= h <= 16; r: the suppression
+ * radius, 1 .. 16; b: the border, b >= h + r, with ny, nx >= 2 b + 1.  Every value widened to float64, no contraction, sums in the
+ * order written:
+ *     u(y, x) = (...((0.0 + w[0] x(y, x - h)) + w[1] x(y, x - h + 1)) + ...) + w[2h] x(y, x + h)
+ *     s(y, x) = the same sum over u(y - h + k, x), k ascending
+ * D = {b <= y < ny - b, b <= x < nx - b}; lo, hi: the min and max of the non-nan s over D (+inf and -inf when there is none);
+ *     t = v > threshold ? v : threshold,   v = lo + rel (hi - lo)
+ * A pixel p of D is a candidate when s(p) >= t, s(q) < s(p) for every q with |q - p|_inf <= r that comes before p in row-major
+ * order and s(q) <= s(p) for every such q after it -- IEEE comparisons as written: a nan anywhere in the window disqualifies p, and a
+ * plateau yields one candidate, its first pixel.
+ * Outputs, host arrays: per image the candidates in ROW-MAJOR order, the first cap of them: yx_out [n][cap][2] = (y, x), s_out
+ * [n][cap] = s(p), x_out [n][cap] = x(p) widened; count_out [n] the true count (it may exceed cap); levels_out [n][RL_PEAK_LEVELS]
+ * = lo, hi, t.  Entries past min(count, cap) are not written.
+ * Tiles of 16 x 32 pixels of D with a halo of h + r in LDS (at most 64 KB), a mask word per tile row, ranks from an integer prefix
+ * over the mask in row-major order (csrc/bead_kernels.hpp); no atomics: bit-identical from run to run, and an image's result does
+ * not depend on the other images of the call.  Images are processed in chunks whose tile partials, masks and candidate lists stay
+ * under a cap of 256 MB (at least one image per chunk); the workspace is kept in the context and freed with it.  Synchronises the
+ * context's stream.
+ * RL_ERR_INVALID (no kernel is launched): a NULL argument, a dtype that is neither, n < 1, h outside 0 .. 16, r outside 1 .. 16,
+ * b < h + r, an image smaller than 2 b + 1 on an axis, a negative offset, cap < 1. */
+#define RL_PEAK_LEVELS 3
+int rl_find_peaks(rl_ctx* ctx, const void* src_dev, int src_dtype, const int64_t* offsets, int n, int ny, int nx, const double* taps,
+                  int h, int r, int b, double rel, double threshold, int cap, int32_t* yx_out, double* s_out, double* x_out,
+                  int64_t* count_out, double* levels_out);
+/* The cap above for the later calls on this context, in bytes (>= 1; a cap below one image's share gives chunks of one image).  The
+ * results do not depend on it.  RL_ERR_INVALID: a NULL ctx, 0 bytes. */
+int rl_find_peaks_chunk_bytes(rl_ctx* ctx, size_t bytes);
+
 /* ---- line_sted_figure_3.py: the scan-position-by-scan-position imaging simulator (:76-273) ----
  * rl_rotate_image: `rotate` (:382-391) for one [ny][nx] plane -- scipy.ndimage.rotate(order 3,
  * mode 'nearest', reshape=False) about the centre; clip != 0 clips to [0, 1.1 * max(in)].  Host in / out. */

@@ -148,6 +148,9 @@ PROTOTYPES = {
                                   _dp, _dp, _dp]),
     'rl_ensemble_stats': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int32), _i, _vp, _i, _c.POINTER(_c.c_int64), _dp,
                                _c.c_size_t, _vp, _vp, _dp]),
+    'rl_find_peaks': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _i, _i, _i, _dp, _i, _i, _i, _c.c_double, _c.c_double, _i,
+                           _c.POINTER(_c.c_int32), _dp, _dp, _c.POINTER(_c.c_int64), _dp]),
+    'rl_find_peaks_chunk_bytes': (_i, [_vp, _c.c_size_t]),
 }
 
 

@@ -103,6 +103,10 @@ struct rl_ctx {
     // rl_register_sums, rl_shift_images (register_api.cpp): a grow-only workspace for a call's offsets, taps, partials, totals
     // and the shift's float64 intermediate; freed with the context
     EnsembleWork reg;
+    // rl_find_peaks (bead_api.cpp): a grow-only workspace for a call's taps, offsets, tile partials, levels, masks and candidate
+    // lists; freed with the context.  beads_cap: the bytes the images in flight of one chunk may take (rl_find_peaks_chunk_bytes)
+    EnsembleWork beads;
+    size_t beads_cap = (size_t)256 << 20;
 
     int device = 0;
     hipStream_t stream = nullptr;

@@ -4,6 +4,12 @@ rescan_line_sted_amd/_build.py; the sets of kernel symbols must be equal and eve
 are compared by name, not by their place in the file: the order in which templates are instantiated moves them around.
 
     python3 tools/device_code_compare.py TREE_A TREE_B [WORKDIR]        exit status 1 on any difference; no GPU needed
+
+With --all, every source of _build.jobs() that carries device code is compared instead (every .hip file, every FFT length, and the
+.cpp files compiled as HIP), for a change that must leave every existing kernel alone.  A source that only one tree has is listed
+and not counted as a difference.
+
+    python3 tools/device_code_compare.py --all TREE_A TREE_B [WORKDIR]
 """
 import hashlib
 import os
@@ -21,10 +27,13 @@ LLVM = os.path.join(os.path.dirname(os.path.dirname(_build.HIPCC)), 'llvm', 'bin
 
 def kernels(tree, L, work):
     """{symbol: [instruction text]} of one length's device code"""
-    elf = os.path.join(work, 'fft_%d.elf' % L)
-    _build._run([_build.HIPCC, '-O3', '-std=c++17', '-fPIC', '-I' + os.path.join(tree, 'include')] + _build.DEVICE + _build.FFT_FLAGS +
-                ['-DRL_CFG_L=%d' % L, '--cuda-device-only', '--no-gpu-bundle-output', '-c',
-                 os.path.join(tree, 'rescan_line_sted_amd', 'csrc', 'fft_kernels.hip'), '-o', elf])
+    return disassembly(tree, 'fft_kernels.hip', _build.DEVICE + _build.FFT_FLAGS + ['-DRL_CFG_L=%d' % L], os.path.join(work, 'fft_%d.elf' % L))
+
+
+def disassembly(tree, source, flags, elf):
+    """{symbol: [instruction text]} of the device code of csrc/`source` of `tree`, compiled with `flags`"""
+    _build._run([_build.HIPCC, '-O3', '-std=c++17', '-fPIC', '-I' + os.path.join(tree, 'include')] + flags +
+                ['--cuda-device-only', '--no-gpu-bundle-output', '-c', os.path.join(tree, 'rescan_line_sted_amd', 'csrc', source), '-o', elf])
     text = subprocess.check_output([os.path.join(LLVM, 'llvm-objdump'), '-d', elf], text=True)
     out, cur = {}, None
     for line in text.split('\n'):
@@ -41,7 +50,41 @@ def kernels(tree, L, work):
     return out
 
 
+def report(name, ka, kb):
+    digest = [hashlib.sha256('\n'.join(k + '\n' + '\n'.join(d[k]) for k in sorted(d)).encode()).hexdigest()[:16] for d in (ka, kb)]
+    differ = sorted(set(ka) ^ set(kb)) + [k for k in sorted(set(ka) & set(kb)) if ka[k] != kb[k]]
+    print('%-28s kernels %3d / %3d   sha256 of the sorted disassembly %s / %s   %s' % (name, len(ka), len(kb), digest[0], digest[1],
+                                                                                 'identical' if not differ else 'DIFFERENT: %s' % differ[:4]))
+    return bool(differ)
+
+
+def main_all(a, b, work):
+    """Every job of _build.jobs() with device flags, by its object's name; the symbols counted are the functions of the device ELF"""
+    todo, only = [], []
+    for obj, src, flags in _build.jobs():
+        if not any(f.startswith('--offload-arch') for f in flags):
+            continue
+        name, source = os.path.splitext(os.path.basename(obj))[0], os.path.basename(src)
+        have = [os.path.exists(os.path.join(t, 'rescan_line_sted_amd', 'csrc', source)) for t in (a, b)]
+        if all(have):
+            todo.append((name, source, flags))
+        else:
+            only.append((name, 'A' if have[0] else 'B'))
+    for d in ('a', 'b'):
+        os.makedirs(os.path.join(work, d), exist_ok=True)
+    runs = [(t, source, flags, os.path.join(work, d, name + '.elf')) for name, source, flags in todo for t, d in ((a, 'a'), (b, 'b'))]
+    with ThreadPoolExecutor(max_workers=8) as ex:
+        res = list(ex.map(lambda j: disassembly(*j), runs))
+    bad = sum(report(name, res[2 * i], res[2 * i + 1]) for i, (name, _, _) in enumerate(todo))
+    for name, which in only:
+        print('%-28s only in tree %s: not compared' % (name, which))
+    return 1 if bad else 0
+
+
 def main():
+    if sys.argv[1] == '--all':
+        a, b = sys.argv[2:4]
+        return main_all(a, b, sys.argv[4] if len(sys.argv) > 4 else tempfile.mkdtemp(prefix='devcmp_'))
     a, b = sys.argv[1:3]
     work = sys.argv[3] if len(sys.argv) > 3 else tempfile.mkdtemp(prefix='devcmp_')
     jobs = [(t, L, os.path.join(work, n)) for L in _build.FFT_LENGTHS for t, n in ((a, 'a'), (b, 'b'))]
