@@ -857,6 +857,57 @@ int rl_find_peaks(rl_ctx* ctx, const void* src_dev, int src_dtype, const int64_t
  * results do not depend on it.  RL_ERR_INVALID: a NULL ctx, 0 bytes. */
 int rl_find_peaks_chunk_bytes(rl_ctx* ctx, size_t bytes);
 
+/* ---- camera calibration: temporal statistics of raw stacks, repair of known defect pixels (DESIGN.md
+ * section 4m) ----
+ * rl_calib: the per-pixel accumulators of one sensor window (y0, x0) + ny x nx of frames of src_ny x src_pitch elements of
+ * raw_dtype (RL_RAW_*), on a context.  rl_calib_accumulate adds n_frames contiguous sensor frames at raw_dev (device memory, e.g.
+ * filled with rl_device_upload_bytes); the launch is enqueued on the context's stream and nothing outside the window is read.
+ *   Integer raw types (u8, u16, i16): S = sum x is int64, Q = sum x^2 is uint64, both exact.  An accumulator holds at most 65535
+ *   frames in all: F Q and S^2 then stay below 2^64 and N = F Q - S^2 is formed exactly in uint64 (>= 0 by Cauchy-Schwarz).  The
+ *   sums do not depend on how the frames are chunked over calls nor on the launch's work split: a call whose window gives few
+ *   workgroups splits its frames over a second grid axis and combines the parts with 64-bit integer atomics.
+ *       mean = (double)S / (double)F;   var = F > 1 ? (double)N / (double)(F (F - 1)) : 0        (unbiased)
+ *   f32: S and Q are float64, S = S + (double)x, Q = Q + (double)x * (double)x in frame order, calls in sequence, no contraction and
+ *   no frame split (the order is part of the definition).  mean = S / F;  var = F > 1 ? (Q - S mean) / (F - 1) : 0.  A non-finite
+ *   input makes its pixel's sums, and with them its mean and variance, non-finite; the other pixels are not touched by it.
+ * rl_calib_frames: F.  rl_calib_sums: waits for the stream and copies the accumulators as they are to host arrays [ny][nx] of 8-byte
+ * values (int64 and uint64, or float64 for f32 raw); either may be NULL, not both.  rl_calib_finalize: float64 maps [ny][nx] in
+ * device memory, either may be NULL, not both; enqueued.  rl_calib_reset: zero sums, F = 0.  rl_calib_destroy(NULL) is RL_OK.
+ * RL_ERR_INVALID (no kernel is launched): a NULL argument, a raw_dtype that is none of RL_RAW_*, a size below 1, a window that
+ * overhangs the frame, n_frames < 1, an accumulate that would take an integer accumulator past 65535 frames (nothing is enqueued, F
+ * stays), a finalize before the first frame or with overlapping maps. */
+typedef struct rl_calib rl_calib;
+int rl_calib_create(rl_ctx* ctx, int raw_dtype, int src_ny, int src_pitch, int y0, int x0, int ny, int nx, rl_calib** out);
+int rl_calib_accumulate(rl_calib* c, const void* raw_dev, int n_frames);
+int rl_calib_frames(const rl_calib* c, long long* frames);
+int rl_calib_sums(rl_calib* c, void* sum_host, void* sumsq_host);
+int rl_calib_finalize(rl_calib* c, double* mean_dev, double* var_dev);
+int rl_calib_reset(rl_calib* c);
+int rl_calib_destroy(rl_calib* c);
+
+/* rl_repair_pixels: the known defect pixels of n_images images [ny][nx] of dtype (RL_F32 / RL_F64) at img_dev, replaced IN PLACE by
+ * the median of their good neighbours.  mask_host [ny][nx], nonzero = defect; radius 1 .. 3.  Per image and defect pixel (y, x):
+ *   for r = 1 .. radius: the values of the pixels within Chebyshev distance r that are inside the image and not defects, in
+ *   row-major order; stop at the first r that yields at least one value;
+ *   sort the c values (ascending, nan last, equal values keep their order): the replacement is v[(c - 1) / 2] for odd c and
+ *   ((double)v[c / 2 - 1] + (double)v[c / 2]) * 0.5, rounded once to dtype, for even c;
+ *   no good pixel within radius: the pixel is left as it is and counted in unrepaired[image] (host array [n_images], may be NULL;
+ *   the mask is the same for every image, so are the counts).
+ * The kernel reads only pixels that are not defects and writes only pixels that are: in place is free of races by construction, and
+ * the result does not depend on the order in which the defects are visited.  The host builds the list of repairable defects (pixel,
+ * ring radius, a bit per window position that is a good neighbour), stages it in a workspace kept in the context and enqueues ONE
+ * launch over (image, listed defect) on the context's stream; a mask without repairable defects launches nothing.
+ * rl_stack_set_defects: the same rule inside rl_stack_run and rl_stack_run_registered, for the plan's window (mask_host [ny][nx] of
+ * it, NULL: none -- the default, and then both runs enqueue exactly what they did before).  The repair of a chunk's images follows
+ * the chunk's rl_ingest on the context's stream: on the plan's measurement buffer in rl_stack_run, on the staging buffer -- before
+ * references and estimates -- in rl_stack_run_registered; in both before rl_deconv_measurement_written.  The ingest statistics stay
+ * those of the ingest.  The list is built once, here, and kept on the device until the next call or rl_stack_destroy.
+ * RL_ERR_INVALID (no kernel is launched): a NULL argument (but mask_host of rl_stack_set_defects), a dtype that is neither, a size
+ * below 1, an image of more than 2^31 - 1 pixels, a radius outside 1 .. 3. */
+int rl_repair_pixels(rl_ctx* ctx, void* img_dev, int dtype, int n_images, int ny, int nx, const unsigned char* mask_host, int radius,
+                     long long* unrepaired);
+int rl_stack_set_defects(rl_stack* st, const unsigned char* mask_host, int radius);
+
 /* ---- line_sted_figure_3.py: the scan-position-by-scan-position imaging simulator (:76-273) ----
  * rl_rotate_image: `rotate` (:382-391) for one [ny][nx] plane -- scipy.ndimage.rotate(order 3,
  * mode 'nearest', reshape=False) about the centre; clip != 0 clips to [0, 1.1 * max(in)].  Host in / out. */

@@ -77,6 +77,8 @@ def jobs():
     out.append((os.path.join(OBJ, 'register_api.o'), os.path.join(CSRC, 'register_api.cpp'), ['-x', 'hip'] + DEVICE))
     out.append((os.path.join(OBJ, 'bead_kernels.o'), os.path.join(CSRC, 'bead_kernels.hip'), DEVICE))
     out.append((os.path.join(OBJ, 'bead_api.o'), os.path.join(CSRC, 'bead_api.cpp'), ['-x', 'hip'] + DEVICE))
+    out.append((os.path.join(OBJ, 'calib_kernels.o'), os.path.join(CSRC, 'calib_kernels.hip'), DEVICE))
+    out.append((os.path.join(OBJ, 'calib_api.o'), os.path.join(CSRC, 'calib_api.cpp'), ['-x', 'hip'] + DEVICE))
     out.append((os.path.join(OBJ, 'gauss_fit.o'), os.path.join(CSRC, 'gauss_fit.cpp'), ['-ffp-contract=off']))
     return [j for j in out if os.path.exists(j[1])]
 

@@ -151,6 +151,15 @@ PROTOTYPES = {
     'rl_find_peaks': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _i, _i, _i, _dp, _i, _i, _i, _c.c_double, _c.c_double, _i,
                            _c.POINTER(_c.c_int32), _dp, _dp, _c.POINTER(_c.c_int64), _dp]),
     'rl_find_peaks_chunk_bytes': (_i, [_vp, _c.c_size_t]),
+    'rl_calib_create': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _c.POINTER(_vp)]),
+    'rl_calib_accumulate': (_i, [_vp, _vp, _i]),
+    'rl_calib_frames': (_i, [_vp, _c.POINTER(_c.c_longlong)]),
+    'rl_calib_sums': (_i, [_vp, _vp, _vp]),
+    'rl_calib_finalize': (_i, [_vp, _vp, _vp]),
+    'rl_calib_reset': (_i, [_vp]),
+    'rl_calib_destroy': (_i, [_vp]),
+    'rl_repair_pixels': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _c.POINTER(_c.c_longlong)]),
+    'rl_stack_set_defects': (_i, [_vp, _vp, _i]),
 }
 
 

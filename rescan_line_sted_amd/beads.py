@@ -226,6 +226,8 @@ def measure_psfs(raw, size, camera=None, order='frame-view', roi=None, sigma=1.0
             dark = dev.alloc(n_pix, 'f32')
             dev.upload(dark, camera.dark_map)
         dev.ingest(raw_dev, code, F * V, (sy, sx), (y0, x0), fs, vs, F, F, V, (ny, nx), camera, dark, imgs, stats)   # -> [F][V][ny][nx]
+        if camera.defects is not None:
+            dev.repair(imgs, F * V, ny, nx, camera.defects, camera.repair_radius)
         psfs, info = [], {k: [] for k in ('positions', 'flux', 'ncc', 'rejected', 'std')}
         n_beads, width = np.zeros(V, dtype=np.int64), np.zeros((V, 2))
         for v in range(V):
@@ -237,6 +239,7 @@ def measure_psfs(raw, size, camera=None, order='frame-view', roi=None, sigma=1.0
             n_beads[v] = len(vi['ncc'])
             width[v] = [_FWHM * abs(get_width(psf[0, size // 2, :])[0]), _FWHM * abs(get_width(psf[0, :, size // 2])[0])]
         info.update({'n_beads': n_beads, 'width': width, 'margin': m, 'border': b})
+        info.update(camera.defect_info())
         return psfs, info
     finally:
         dev.close()

@@ -107,6 +107,8 @@ struct rl_ctx {
     // lists; freed with the context.  beads_cap: the bytes the images in flight of one chunk may take (rl_find_peaks_chunk_bytes)
     EnsembleWork beads;
     size_t beads_cap = (size_t)256 << 20;
+    // rl_repair_pixels (calib_api.cpp): a grow-only workspace for a call's defect list; freed with the context
+    EnsembleWork calib;
 
     int device = 0;
     hipStream_t stream = nullptr;

@@ -1,5 +1,5 @@
 // stack_api.cpp -- C ABI of the acquired-stack path (include/rlsted.h: rl_ingest, rl_export, rl_stack_create, rl_stack_run,
-// rl_stack_run_registered, rl_stack_destroy, rl_device_upload_bytes): validation, the launches of ingest_kernels.hip, and the chunk
+// rl_stack_run_registered, rl_stack_set_defects, rl_stack_destroy, rl_device_upload_bytes): validation, the launches of ingest_kernels.hip, and the chunk
 // pipeline that overlaps upload, iterations and download -- with, in the registered run, the estimates (rl_register_estimate) and
 // the shift (rl_shift_images) between the ingest and the iterations.  The pipeline reaches the plan through the C ABI alone (rl_deconv_dims, rl_deconv_device_ptr,
 // rl_deconv_measurement_written, rl_deconv_reset_estimate, rl_deconv_iterate), as the tiled path does.  No kernel is launched on
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "calib_kernels.hpp"
 #include "ingest_kernels.hpp"
 
 using namespace rl;
@@ -166,6 +167,15 @@ struct rl_stack {
     // scratch B * V float64 images
     void *staging = nullptr, *refs = nullptr;
     double* scratch = nullptr;
+    // rl_stack_set_defects: the device list of the repairable defects of the plan's window (calib_kernels.hpp), or none
+    RepairEntry* defects = nullptr;
+    int n_defects = 0;
+    // the repair of a chunk's B * V ingested images at `img`, on the context's stream (nothing is enqueued without defects)
+    int repair_chunk(void* img) {
+        if (!n_defects) return RL_OK;
+        HIP_TRY(repair(dtype, img, B * V, (size_t)ny * nx, nx, defects, n_defects, ctx->stream));
+        return RL_OK;
+    }
 };
 
 namespace {
@@ -212,6 +222,7 @@ int stack_compute(rl_stack* st, const Chunk& c, int k_iters, double* times) {
     HIP_TRY(hipEventRecord(sl.freed, s));
     sl.used = true;
     RL_TRY(rc);
+    RL_TRY(st->repair_chunk(st->meas));
     RL_TRY(rl_deconv_measurement_written(st->plan));
     RL_TRY(rl_deconv_reset_estimate(st->plan));
     RL_TRY(rl_deconv_iterate(st->plan, k_iters));
@@ -301,6 +312,7 @@ extern "C" int rl_stack_destroy(rl_stack* st) {
             if (e) (void)hipEventDestroy(e);
     }
     if (st->dark) (void)hipFree(st->dark);
+    if (st->defects) (void)hipFree(st->defects);
     for (void* p : {st->staging, st->refs, (void*)st->scratch})
         if (p) (void)hipFree(p);
     if (st->in) (void)hipStreamDestroy(st->in);
@@ -335,6 +347,25 @@ extern "C" int rl_stack_create(rl_deconv* plan, const rl_stack_params* params, r
         return fail(rc, why);
     }
     *out = st;
+    return RL_OK;
+}
+
+extern "C" int rl_stack_set_defects(rl_stack* st, const unsigned char* mask_host, int radius) {
+    if (!st) return fail(RL_ERR_INVALID, "NULL argument");
+    if (mask_host && (radius < 1 || radius > kRepairMaxRadius)) return fail(RL_ERR_INVALID, "radius must lie in 1 .. 3");
+    if ((size_t)st->ny * (size_t)st->nx > 0x7fffffffull) return fail(RL_ERR_INVALID, "an image of more than 2^31 - 1 pixels");
+    HIP_TRY(hipSetDevice(st->ctx->device));
+    HIP_TRY(hipStreamSynchronize(st->ctx->stream));   // (a run in flight reads the present list)
+    if (st->defects) (void)hipFree(st->defects);
+    st->defects = nullptr;
+    st->n_defects = 0;
+    if (!mask_host) return RL_OK;
+    std::vector<RepairEntry> list;
+    repair_list(mask_host, st->ny, st->nx, radius, list, nullptr, nullptr);
+    if (list.empty()) return RL_OK;
+    HIP_TRY(hipMalloc((void**)&st->defects, list.size() * sizeof(RepairEntry)));
+    HIP_TRY(hipMemcpy(st->defects, list.data(), list.size() * sizeof(RepairEntry), hipMemcpyHostToDevice));
+    st->n_defects = (int)list.size();
     return RL_OK;
 }
 
@@ -406,6 +437,7 @@ int stack_compute_registered(rl_stack* st, const Chunk& c, int k_iters, RegRun& 
     HIP_TRY(hipEventRecord(sl.freed, s));
     sl.used = true;
     RL_TRY(rc);
+    RL_TRY(st->repair_chunk(st->staging));                          // (before references and estimates)
     std::vector<double> chunk((size_t)B * V * 2, 0.0);              // (fillers: no shift)
     if (r.given) {
         std::copy(r.given + (size_t)c.first * V * 2, r.given + ((size_t)c.first + c.nt) * V * 2, chunk.begin());

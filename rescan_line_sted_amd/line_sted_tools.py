@@ -56,6 +56,7 @@ from .tiling import deconvolve_tiled   # noqa: F401  (re-exported)
 from .stack import CameraModel, deconvolve_stack   # noqa: F401  (re-exported)
 from .registration import coarse_shifts, deconvolve_stack_registered, estimate_shifts, shift_images   # noqa: F401  (re-exported)
 from .beads import find_beads, measure_psfs   # noqa: F401  (re-exported)
+from .calibration import calibrate_camera, find_defects, photon_transfer, repair_defects, temporal_stats   # noqa: F401  (re-exported)
 
 _DEFAULT_DTYPE = os.environ.get('RLSTED_DTYPE', 'f64')
 _DEFAULT_DEVICE = _lib.DEFAULT_DEVICE

@@ -254,6 +254,11 @@ class _Device:
                             n_valid, V, shape[0], shape[1], None if dark is None else dark.ptr, camera.dark, camera.gain, camera.epsilon,
                             0.0 if camera.saturation is None else camera.saturation, dst.ptr, DTYPES[dst.dtype], stats.ptr))
 
+    def repair(self, buf, n_images, ny, nx, mask, radius):
+        """rl_repair_pixels on the first n_images images of buf, in place."""
+        check(lib.rl_repair_pixels(self.ctx.handle, buf.ptr, DTYPES[buf.dtype], n_images, ny, nx, mask.ctypes.data_as(ctypes.c_void_p),
+                                   int(radius), None))
+
     def sums(self, ref, ref_offsets, mov, mov_offsets, ny, nx, R, M):
         """rl_register_sums: (S [pairs][(2R+1)^2][3], A [pairs][2])."""
         n = len(mov_offsets)
@@ -556,6 +561,8 @@ def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame
                     dev.upload(raw_dev, frames[v, first:first + nt], v * nt * img_bytes)
                 fs, vs = 1, nt
             dev.ingest(raw_dev, code, nt * V, (sy, sx), (y0, x0), fs, vs, batch, nt, V, (ny, nx), camera, dark, staging, stats_dev)
+            if camera.defects is not None:
+                dev.repair(staging, batch * V, ny, nx, camera.defects, camera.repair_radius)
             ingest_stats[first:first + nt] = dev.download(stats_dev, nt * V * INGEST_FIELDS).reshape(nt, V, INGEST_FIELDS)
             if first == 0:
                 dev.copy(refs, 0, staging, 0, V * n_pix)
@@ -590,6 +597,7 @@ def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame
                 'shifts': applied, 'ncc': value, 'at_limit': at_limit, 'flat': flat, 'view_ncc': view_info['ncc'],
                 'view_at_limit': view_info['at_limit'], 'view_flat': view_info['flat'], 'raised': raised,
                 'unresolved': dev.unresolved(), 'strategy': dev.strategy(), 'chunks': -(-F // batch), 'batch': batch}
+        info.update(camera.defect_info())
         if use_coarse is not None:
             info.update({'coarse': coarse_c, 'coarse_snr': coarse_snr, 'view_coarse': view_coarse, 'view_coarse_snr': view_coarse_snr})
         return out, info
@@ -620,6 +628,8 @@ def _registered_pipeline(raw, code, psfs, iterations, camera, order, sensor, win
     dev = stack._Device(psfs, batch, (ny, nx), dtype, device, acceleration, tv_lambda, tv_epsilon)
     try:
         dev.open(code, ORDERS[order], sensor, (y0, x0), camera, out_code, out_scale)
+        if camera.defects is not None:
+            dev.set_defects(camera.defects, camera.repair_radius)
         ingest_stats, export_stats, times = np.zeros((F, V, INGEST_FIELDS)), np.zeros((F, EXPORT_FIELDS)), np.zeros(5)
         shifts, fields, raised = np.zeros((F, V, 2)), np.zeros((F, V, 3)), np.zeros((F, V))
         view_shifts, view_fields = np.zeros((V, 2)), np.zeros((V, 3))
@@ -634,6 +644,7 @@ def _registered_pipeline(raw, code, psfs, iterations, camera, order, sensor, win
                 'raised': raised.astype(np.int64), 'unresolved': dev.unresolved(), 'strategy': dev.strategy(), 'chunks': -(-F // batch),
                 'batch': batch, 'clamped': export_stats[:, 1].astype(np.int64),
                 'times_ms': dict(zip(('wall_ms', 'upload_ms', 'compute_ms', 'download_ms', 'estimate_ms'), times.tolist()))}
+        info.update(camera.defect_info())
         return out, info
     finally:
         dev.close()

@@ -25,9 +25,11 @@ class CameraModel:
     """What turns a sensor's numbers into photons: measurement = max((raw - dark) * gain, 0) + epsilon, formed in float64 on the
     device.  dark: one level, or a (ny, nx) map in the coordinates of the window that is deconvolved (kept as float32); gain:
     photons per count, positive; saturation: None, or the raw level from which a pixel is counted as saturated; epsilon: what
-    load_data_from_tif adds (1e-9), at least 0."""
+    load_data_from_tif adds (1e-9), at least 0.  defects: None, or a boolean (ny, nx) map in window coordinates of the pixels whose
+    ingested values are replaced by the median of their good neighbours within repair_radius (1 .. 3) before the iterations
+    (include/rlsted.h rl_repair_pixels; calibration.find_defects makes such a map)."""
 
-    def __init__(self, dark=0.0, gain=1.0, saturation=None, epsilon=1e-9):
+    def __init__(self, dark=0.0, gain=1.0, saturation=None, epsilon=1e-9, defects=None, repair_radius=3):
         if np.ndim(dark) == 0:
             self.dark, self.dark_map = float(dark), None
             if not np.isfinite(self.dark):
@@ -44,8 +46,26 @@ class CameraModel:
             raise ValueError('epsilon must be finite and at least 0; got %r' % (epsilon,))
         if self.saturation is not None and not self.saturation > 0.0:
             raise ValueError('saturation must be None or positive; got %r' % (saturation,))
+        self.defects, self.repair_radius = None, int(repair_radius)
+        if defects is not None:
+            defects = np.asarray(defects)
+            if defects.dtype != np.bool_ or defects.ndim != 2 or defects.size == 0:
+                raise ValueError('defects: None or a boolean (ny, nx) map; got %s of shape %s' % (defects.dtype, defects.shape))
+            self.defects = np.ascontiguousarray(defects).view(np.uint8)
+        if self.repair_radius != repair_radius or not 1 <= self.repair_radius <= 3:
+            raise ValueError('repair_radius must be 1, 2 or 3; got %r' % (repair_radius,))
+
+    def defect_info(self):
+        """{'defects', 'unrepaired'} of the window: how many pixels the map names and how many of them have no good pixel within
+        repair_radius (they stay as they are); both 0 without a map."""
+        if self.defects is None:
+            return {'defects': 0, 'unrepaired': 0}
+        from .calibration import unrepairable
+        return {'defects': int(np.count_nonzero(self.defects)), 'unrepaired': int(np.count_nonzero(unrepairable(self.defects, self.repair_radius)))}
 
     def check_window(self, ny, nx):
+        if self.defects is not None and self.defects.shape != (ny, nx):
+            raise ValueError('the defect map is %s, the deconvolved window %s' % (self.defects.shape, (ny, nx)))
         if self.dark_map is not None and self.dark_map.shape != (ny, nx):
             raise ValueError('the dark map is %s, the deconvolved window %s' % (self.dark_map.shape, (ny, nx)))
 
@@ -82,6 +102,10 @@ class _Device:
         h = ctypes.c_void_p()
         check(lib.rl_stack_create(self.plan.handle, ctypes.byref(p), ctypes.byref(h)))
         self.stack = h
+
+    def set_defects(self, mask, radius):
+        """The defect map (uint8, the plan's window) whose pixels every chunk repairs after its ingest (rl_stack_set_defects)."""
+        check(lib.rl_stack_set_defects(self.stack, mask.ctypes.data_as(ctypes.c_void_p), int(radius)))
 
     def run(self, raw, frames, iterations, out, ingest_stats, export_stats, times):
         """All frames through the plan, chunk by chunk (rl_stack_run): fills out, the statistics and the four times."""
@@ -132,7 +156,9 @@ def deconvolve_stack(raw, psfs, iterations, camera=None, order='frame-view', roi
     Returns (estimates (F, ny, nx), info); info: 'saturated', 'clipped', 'invalid' (F, V) pixel counts of the ingest, 'level' (F, V)
     the sums of the measurement, 'clamped' (F,) and 'flux' (F,) the count of clamped pixels and the sum of each estimate,
     'unresolved', 'strategy' (the plan's, on the last chunk), 'chunks', 'batch' and 'times' (wall_ms, upload_ms, compute_ms,
-    download_ms of rl_stack_run)."""
+    download_ms of rl_stack_run), 'defects' and 'unrepaired' (the camera's defect map: pixels named, pixels left as they are).  With
+    camera.defects every chunk's ingested images are repaired on the device before the iterations; the ingest statistics stay those
+    of the ingest."""
     _lib.tv_params(tv_lambda, tv_epsilon)
     _lib.accel_mode(acceleration)
     if dtype not in DTYPES:
@@ -165,6 +191,8 @@ def deconvolve_stack(raw, psfs, iterations, camera=None, order='frame-view', roi
     dev = _Device(psfs, batch, (ny, nx), dtype, _lib.DEFAULT_DEVICE if device is None else device, acceleration, tv_lambda, tv_epsilon)
     try:
         dev.open(code, ORDERS[order], (sy, sx), (y0, x0), camera, out_code, out_scale)
+        if camera.defects is not None:
+            dev.set_defects(camera.defects, camera.repair_radius)
         ingest_stats, export_stats, times = np.zeros((F, V, INGEST_FIELDS)), np.zeros((F, EXPORT_FIELDS)), np.zeros(4)
         dev.run(raw, F, int(iterations), out, ingest_stats, export_stats, times)
         info = {'level': ingest_stats[:, :, 0].copy(), 'clipped': ingest_stats[:, :, 1].astype(np.int64),
@@ -172,6 +200,7 @@ def deconvolve_stack(raw, psfs, iterations, camera=None, order='frame-view', roi
                 'flux': export_stats[:, 0].copy(), 'clamped': export_stats[:, 1].astype(np.int64),
                 'unresolved': dev.unresolved(), 'strategy': dev.strategy(), 'chunks': -(-F // batch), 'batch': batch,
                 'times': dict(zip(('wall_ms', 'upload_ms', 'compute_ms', 'download_ms'), times.tolist()))}
+        info.update(camera.defect_info())
         return out, info
     finally:
         dev.close()

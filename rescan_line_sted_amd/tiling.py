@@ -182,6 +182,11 @@ class _Device:
                 self.owned.remove(p)
                 check(lib.rl_device_free(self.ctx.handle, p))      # (waits for the ingest)
 
+    def repair(self, mask, radius):
+        """The defect pixels of the whole ingested image, in place (include/rlsted.h rl_repair_pixels)."""
+        F, V, NY, NX = self.src_shape
+        check(lib.rl_repair_pixels(self.ctx.handle, self.src, self.code, F * V, NY, NX, mask.ctypes.data_as(ctypes.c_void_p), int(radius), None))
+
     def gather(self, slots):
         F, V, NY, NX = self.src_shape
         check(lib.rl_tile_gather(self.ctx.handle, self.src, self.code, F, V, NY, NX, _ints(slots), len(slots), self.tile_shape[0],
@@ -236,7 +241,8 @@ def deconvolve_tiled(measurement, psfs, iterations, tile=None, overlap=None, mar
     the GPU, a TiledResult (.download(); .dev, .dtype, .offsets, .shape for quality.ring_stats_device).
     camera: None, or a stack.CameraModel -- the measurement is then camera data in its own dtype (uint8, uint16, int16, float32; a
     dark map has the image's shape), uploaded as it is and turned into the measurement on the device, max((raw - dark) * gain, 0)
-    + epsilon in float64 rounded once to the plan's element type."""
+    + epsilon in float64 rounded once to the plan's element type; camera.defects (a map of the image's
+    shape) are repaired on the whole image after the ingest (section 5k), and info gains 'defects' and 'unrepaired'."""
     _lib.tv_params(tv_lambda, tv_epsilon)
     _lib.accel_mode(acceleration)
     if dtype not in DTYPES:
@@ -277,6 +283,8 @@ def deconvolve_tiled(measurement, psfs, iterations, tile=None, overlap=None, mar
             dev.upload(measurement)
         else:
             dev.upload_raw(measurement, camera)
+            if camera.defects is not None:
+                dev.repair(camera.defects, camera.repair_radius)
         store = dev.alloc(tiles * ty * tx)
         counts = np.zeros(tiles, dtype=np.int64)
         chunks = 0
@@ -293,6 +301,8 @@ def deconvolve_tiled(measurement, psfs, iterations, tile=None, overlap=None, mar
         out = dev.alloc(F * NY * NX)
         dev.blend(store, layout, F, out)
         info = {'layout': layout, 'tiles': tiles, 'batch': batch, 'chunks': chunks, 'unresolved': dev.unresolved(), 'strategy': dev.strategy()}
+        if camera is not None:
+            info.update(camera.defect_info())
         if until is not None:
             info['iterations'] = counts.reshape(F, len(layout.origins_y), len(layout.origins_x))
         result = dev.result(out, F, (NY, NX))
