@@ -827,6 +827,67 @@ int rl_register_estimate(rl_ctx* ctx, const void* ref_dev, int ref_dtype, const 
                          const int64_t* mov_offsets, int n_pairs, int ny, int nx, int R, int M, int refine, double* scratch_dev,
                          double* shifts_out, double* fields_out, double* surface_out);
 
+/* ---- rotation, scale and shear between views: affine resampling and the sums of a Gauss-Newton step (INTEGRATION.md section 5l,
+ * DESIGN.md section 4n) ----
+ * rl_warp_images: src_dev [n][sy][sx] of src_dtype -> dst_dev [n][oy][ox] of dst_dtype (RL_F32 / RL_F64 each; no overlap; the output
+ * shape is independent of the source's):
+ *     dst[i] = max(scipy.ndimage.affine_transform(src[i], [[m00, m01], [m10, m11]], offset = (o0, o1), output_shape = (oy, ox),
+ *                                                 order = order, mode = 'mirror'), floor)
+ * with xf: host [n][6] = (m00, m01, m10, m11, o0, o1): dst[i][y][x] samples the spline of image i at
+ *     Y = fma(m00, y, fma(m01, x, o0)),   X = fma(m10, y, fma(m11, x, o1)),
+ * whole-sample mirror boundaries in the prefilter and in the evaluation.  Every entry finite, and the four corners of the output
+ * grid must map to |Y|, |X| <= 1e9 (the map is affine, so every pixel then does; F = floor(.) converts exactly to a 32-bit index,
+ * which folds to i mod 2 (n - 1) and then to 2 (n - 1) - i where that is >= n; an axis of length 1 maps to 0).  order: 1 or 3.
+ * floor: any double but nan (-infinity: none).  Computed in float64 with one rounding to the destination type.
+ * ORDER 3: the spline coefficients are the prefilter alone, along x and then along y: per axis the impulse response
+ * h[k] = sqrt(3) z^|k|, z = sqrt(3) - 2, |k| <= 30, of rl_shift_images without its evaluation weights (61 taps formed on the host in
+ * long double, a coefficient is h_0 v_0, then fma(h_m, v_m, .) for m = 1, 2, ... over the samples mirror(. - 30 + m); the dropped tail
+ * is at most 8.8e-18 max|src| per axis), run by the shift's own passes.  The evaluation per axis, with F = floor(Y), t = Y - F,
+ * u = 1 - t, s = the double nearest 1/6, every operation rounded on its own:
+ *     w_0 = ((u u) u) s    w_1 = (((t t) (t - 2)) 3 + 4) s    w_2 = (((u u) (u - 2)) 3 + 4) s    w_3 = ((t t) t) s
+ * at the offsets -1 .. 2 from F (wy from Y, wx from X); with c_ij the coefficient at (Fy - 1 + i, Fx - 1 + j) through the mirror rule:
+ *     r_i = wx_0 c_i0, then r_i = fma(wx_j, c_ij, r_i) for j = 1, 2, 3;     v = wy_0 r_0, then v = fma(wy_i, r_i, v) for i = 1, 2, 3.
+ * ORDER 1: the weights (1 - t, t) at the offsets 0, 1 on the samples themselves: r_i = (1 - tx) s_i0, then r_i = fma(tx, s_i1, r_i)
+ * only where tx != 0; v = (1 - ty) r_0, then v = fma(ty, r_1, v) only where ty != 0.  A weight that is exactly 0 does not read its
+ * sample: an integer translation is a bit-exact copy of the displaced pixels, as in rl_shift_images, and the matrix diag(2, 2) with
+ * offset (0.5, 0.5) is the 2 x 2 mean ((a + b) + (c + d)) / 4.
+ * stats_out: NULL, or host [n][RL_SHIFT_FIELDS] = the count of pixels raised to `floor`, the float64 sum of the stored image, in the
+ * fixed order of csrc/affine_kernels.hpp (a thread of an output tile of 32 x 32 over its rows t / 32 + 8 k in increasing order,
+ * binary tree over 256 threads, workgroups in increasing order; no atomics).  Writes exactly n * oy * ox values.
+ * A tile's source footprint is staged in LDS when it takes at most 48 KB as float64, and read from global memory otherwise: the same
+ * arithmetic, the same bits (rl_warp_path: 1 reads every tile directly, 0 -- the default -- decides per tile; for tests and
+ * measurements).  Images are processed in chunks whose float64 intermediates (order 3: 16 bytes per source pixel) stay under a cap,
+ * in the context's workspace (rl_warp_chunk_bytes: the cap for the later calls on this context, >= 1 byte, at least one image per
+ * chunk; the results do not depend on it).  Synchronises the context's stream.
+ * RL_ERR_INVALID (no kernel is launched): a NULL ctx / source / xf / destination, a dtype that is neither, n, sy, sx, oy or ox < 1,
+ * an order that is neither, floor nan, an entry of xf that is not finite, a corner beyond 1e9, a destination that overlaps the source.
+ *
+ * rl_affine_sums: the normal equations of one Gauss-Newton step of an intensity-based registration, for every motion model at once.
+ * Addressing as rl_register_sums: pair i is the reference A at ELEMENT offset ref_offsets[i] of ref_dev and the moving image W --
+ * ALREADY WARPED by the current estimate -- at w_offsets[i] of w_dev, both [ny][nx]; shared references allowed.  M: margin, M >= 1,
+ * with ny - 2 M >= 8 and nx - 2 M >= 8; ny * nx < 2^31.  With the interior I = [M, ny - M) x [M, nx - M), every value widened to
+ * float64, yc = y - (ny - 1) / 2, xc = x - (nx - 1) / 2 (exact),
+ *     gy = 0.5 (W[y+1][x] - W[y-1][x])    gx = 0.5 (W[y][x+1] - W[y][x-1])    w = W[y][x]    a = A[y][x]
+ *     phi = (gy, gx, gy yc, gy xc, gx yc, gx xc, w, 1)                    (every product rounded on its own)
+ * sums_out: host [n_pairs][RL_AFFINE_FIELDS]: [0, 36) the upper triangle of sum_I phi phi^T in row-major order ((0,0), (0,1), ...,
+ * (0,7), (1,1), ...), each term through fma(phi_j, phi_k, .); [36, 44) sum_I phi_j a through fma(phi_j, a, .); [44] sum_I a^2 through
+ * fma(a, a, .).  The linearisation a ~ g w + b + phi_{0..5} q, q = g (dt_y, dt_x, dL_00, dL_01, dL_10, dL_11), is linear in (q, g, b):
+ * translation, rigid, similarity and affine steps are projections of this one 8 x 8 system on the host.
+ * FIXED ORDER (csrc/affine_kernels.hpp), no atomics: the interior's n pixels in row-major order are cut into nb = min(4096,
+ * ceil(n / 8192)) runs of ceil(n / nb); thread t of a run's 256 takes its pixels t, t + 256, ... in increasing order from 0.0; the
+ * halving tree s[t] = s[t] + s[t + h], h = 128, ..., 1; (((0.0 + run_0) + run_1) + ...).  Bit-identical from run to run, a pair's
+ * result does not depend on the other pairs of the call, and nothing outside an image is read.  Pairs are processed in chunks whose
+ * partial sums stay under a fixed cap, in the context's workspace.  Synchronises the context's stream.
+ * RL_ERR_INVALID (no kernel is launched): a NULL argument, a dtype that is neither, n_pairs < 1, M < 1, an interior smaller than
+ * 8 x 8, 2^31 pixels or more, a negative offset. */
+#define RL_AFFINE_FIELDS 45
+int rl_warp_images(rl_ctx* ctx, const void* src_dev, int src_dtype, int n, int sy, int sx, const double* xf, int order, double floor,
+                   void* dst_dev, int dst_dtype, int oy, int ox, double* stats_out);
+int rl_warp_chunk_bytes(rl_ctx* ctx, size_t bytes);
+int rl_warp_path(rl_ctx* ctx, int path);
+int rl_affine_sums(rl_ctx* ctx, const void* ref_dev, int ref_dtype, const int64_t* ref_offsets, const void* w_dev, int w_dtype,
+                   const int64_t* w_offsets, int n_pairs, int ny, int nx, int M, double* sums_out);
+
 /* ---- bead images: the peak finder of the PSF measurement ----
  * rl_find_peaks: the candidates of n images of ny x nx, src_dtype (RL_F32 / RL_F64) at the ELEMENT offsets offsets[i] of src_dev
  * (host array [n]; any offset >= 0, no alignment assumed).  taps: host float64 w[0 .. 2 h], 0 <= h <= 16; r: the suppression

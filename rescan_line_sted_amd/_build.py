@@ -74,6 +74,7 @@ def jobs():
     out.append((os.path.join(OBJ, 'register_kernels.o'), os.path.join(CSRC, 'register_kernels.hip'), DEVICE))
     out.append((os.path.join(OBJ, 'register_peaks.o'), os.path.join(CSRC, 'register_peaks.hip'), DEVICE))
     out.append((os.path.join(OBJ, 'xcorr_kernels.o'), os.path.join(CSRC, 'xcorr_kernels.hip'), DEVICE + FFT_FLAGS))
+    out.append((os.path.join(OBJ, 'affine_kernels.o'), os.path.join(CSRC, 'affine_kernels.hip'), DEVICE))
     out.append((os.path.join(OBJ, 'register_api.o'), os.path.join(CSRC, 'register_api.cpp'), ['-x', 'hip'] + DEVICE))
     out.append((os.path.join(OBJ, 'bead_kernels.o'), os.path.join(CSRC, 'bead_kernels.hip'), DEVICE))
     out.append((os.path.join(OBJ, 'bead_api.o'), os.path.join(CSRC, 'bead_api.cpp'), ['-x', 'hip'] + DEVICE))

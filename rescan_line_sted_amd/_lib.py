@@ -146,6 +146,10 @@ PROTOTYPES = {
     'rl_register_peaks': (_i, [_vp, _vp, _i, _i, _c.c_double, _dp, _dp]),
     'rl_register_estimate': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _vp, _i, _c.POINTER(_c.c_int64), _i, _i, _i, _i, _i, _i, _vp,
                                   _dp, _dp, _dp]),
+    'rl_warp_images': (_i, [_vp, _vp, _i, _i, _i, _i, _dp, _i, _c.c_double, _vp, _i, _i, _i, _dp]),
+    'rl_warp_chunk_bytes': (_i, [_vp, _c.c_size_t]),
+    'rl_warp_path': (_i, [_vp, _i]),
+    'rl_affine_sums': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _vp, _i, _c.POINTER(_c.c_int64), _i, _i, _i, _i, _dp]),
     'rl_ensemble_stats': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int32), _i, _vp, _i, _c.POINTER(_c.c_int64), _dp,
                                _c.c_size_t, _vp, _vp, _dp]),
     'rl_find_peaks': (_i, [_vp, _vp, _i, _c.POINTER(_c.c_int64), _i, _i, _i, _dp, _i, _i, _i, _c.c_double, _c.c_double, _i,

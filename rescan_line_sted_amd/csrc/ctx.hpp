@@ -103,6 +103,10 @@ struct rl_ctx {
     // rl_register_sums, rl_shift_images (register_api.cpp): a grow-only workspace for a call's offsets, taps, partials, totals
     // and the shift's float64 intermediate; freed with the context
     EnsembleWork reg;
+    // rl_warp_images (register_api.cpp, in the workspace above): warp_cap, the bytes the float64 intermediates of one chunk's images
+    // may take (rl_warp_chunk_bytes); warp_direct, 1 when no tile is to be staged in LDS (rl_warp_path)
+    size_t warp_cap = (size_t)512 << 20;
+    int warp_direct = 0;
     // rl_find_peaks (bead_api.cpp): a grow-only workspace for a call's taps, offsets, tile partials, levels, masks and candidate
     // lists; freed with the context.  beads_cap: the bytes the images in flight of one chunk may take (rl_find_peaks_chunk_bytes)
     EnsembleWork beads;

@@ -1,7 +1,8 @@
 // register_api.cpp -- C ABI of the registration primitives (include/rlsted.h: rl_register_sums, rl_shift_images,
-// rl_register_peaks, rl_register_estimate, rl_register_xcorr): validation, the shift's taps (formed on the host in long double,
-// register_kernels.hpp shift_taps), the chunking under the workspace caps and the launches of register_kernels.hip,
-// register_peaks.hip and xcorr_kernels.hip.  Only offsets and taps go up and the sums, peaks and statistics come down.  No kernel is
+// rl_register_peaks, rl_register_estimate, rl_register_xcorr, rl_warp_images, rl_affine_sums): validation, the shift's and the
+// prefilter's taps (formed on the host in long double, register_kernels.hpp shift_taps, affine_kernels.hpp warp_prefilter_taps), the
+// chunking under the workspace caps and the launches of register_kernels.hip, register_peaks.hip, xcorr_kernels.hip and
+// affine_kernels.hip.  Only offsets and taps go up and the sums, peaks and statistics come down.  No kernel is
 // launched on bad arguments.
 #include <algorithm>
 #include <cmath>
@@ -10,6 +11,7 @@
 
 #include "ctx.hpp"
 #include "kernel_variants.hpp"
+#include "affine_kernels.hpp"
 #include "register_kernels.hpp"
 #include "xcorr_kernels.hpp"
 
@@ -325,6 +327,123 @@ extern "C" int rl_register_xcorr(rl_ctx* ctx, const void* ref_dev, int ref_dtype
         HIP_TRY(hipMemcpyAsync(peaks_out + first * kXcFields, a.peaks, n * kXcFields * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         if (surface_out)
             HIP_TRY(hipMemcpyAsync(surface_out + first * W * W, a.surf, n * W * W * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    return RL_OK;
+}
+
+extern "C" int rl_warp_chunk_bytes(rl_ctx* ctx, size_t bytes) {
+    if (!ctx || bytes < 1) return fail(RL_ERR_INVALID, "NULL context or a cap of 0 bytes");
+    ctx->warp_cap = bytes;
+    return RL_OK;
+}
+
+extern "C" int rl_warp_path(rl_ctx* ctx, int path) {
+    if (!ctx || (path != 0 && path != 1)) return fail(RL_ERR_INVALID, "NULL context or a path that is neither 0 nor 1");
+    ctx->warp_direct = path;
+    return RL_OK;
+}
+
+extern "C" int rl_warp_images(rl_ctx* ctx, const void* src_dev, int src_dtype, int n, int sy, int sx, const double* xf, int order,
+                              double floor, void* dst_dev, int dst_dtype, int oy, int ox, double* stats_out) {
+    if (!ctx || !src_dev || !xf || !dst_dev) return fail(RL_ERR_INVALID, "NULL argument");
+    if (!float_dtype_ok(src_dtype) || !float_dtype_ok(dst_dtype)) return fail(RL_ERR_INVALID, "dtypes must be RL_F32 or RL_F64");
+    if (n < 1 || sy < 1 || sx < 1 || oy < 1 || ox < 1) return fail(RL_ERR_INVALID, "n, sy, sx, oy and ox must be at least 1");
+    if (order != 1 && order != 3) return fail(RL_ERR_INVALID, "order must be 1 or 3");
+    if (std::isnan(floor)) return fail(RL_ERR_INVALID, "floor is nan");
+    for (size_t i = 0; i < (size_t)n; ++i) {
+        const double* m = xf + i * kWarpXf;
+        for (int k = 0; k < kWarpXf; ++k)
+            if (!std::isfinite(m[k])) return fail(RL_ERR_INVALID, "image " + std::to_string(i) + ": the transform must be finite");
+        for (int c = 0; c < 4; ++c) {
+            double Y, X;
+            warp_coord(m, c & 2 ? oy - 1 : 0, c & 1 ? ox - 1 : 0, Y, X);
+            if (!(std::fabs(Y) <= kWarpMaxCoord) || !(std::fabs(X) <= kWarpMaxCoord))
+                return fail(RL_ERR_INVALID, "image " + std::to_string(i) + ": the output grid must map to coordinates of at most 1e9 pixels");
+        }
+    }
+    const size_t s_pix = (size_t)sy * sx, o_pix = (size_t)oy * ox;
+    if (overlaps(src_dev, (size_t)n * s_pix * float_size(src_dtype), dst_dev, (size_t)n * o_pix * float_size(dst_dtype)))
+        return fail(RL_ERR_INVALID, "the destination overlaps the source");
+    static_assert(kWarpFields == RL_SHIFT_FIELDS, "the header's field count");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int nb = warp_blocks_y(oy) * warp_blocks_x(ox);
+    const size_t per = (order == 3 ? 2 * s_pix * sizeof(double) + sizeof(ShiftImage) : 0) + (size_t)nb * kWarpFields * sizeof(double);
+    const size_t chunk = std::min<size_t>((size_t)n, std::max<size_t>(1, ctx->warp_cap / per));
+    const size_t xf_bytes = round_up((size_t)n * kWarpXf * sizeof(double), 256), stats_bytes = round_up((size_t)n * kWarpFields * sizeof(double), 256);
+    const size_t part_bytes = round_up(chunk * nb * kWarpFields * sizeof(double), 256);
+    const size_t table_bytes = order == 3 ? round_up(chunk * sizeof(ShiftImage), 256) : 0;
+    const size_t img_bytes = order == 3 ? round_up(chunk * s_pix * sizeof(double), 256) : 0;
+    char* w = nullptr;
+    RL_TRY(reg_workspace(ctx, xf_bytes + stats_bytes + part_bytes + table_bytes + 2 * img_bytes, &w));
+    double* xf_dev = (double*)w;
+    double* stats = (double*)(w + xf_bytes);
+    double* part = (double*)(w + xf_bytes + stats_bytes);
+    ShiftImage* table_dev = (ShiftImage*)(w + xf_bytes + stats_bytes + part_bytes);
+    double* tmp = (double*)(w + xf_bytes + stats_bytes + part_bytes + table_bytes);
+    double* coef = (double*)(w + xf_bytes + stats_bytes + part_bytes + table_bytes + img_bytes);
+    HIP_TRY(hipMemcpyAsync(xf_dev, xf, (size_t)n * kWarpXf * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    std::vector<ShiftImage> table;
+    if (order == 3) {           // the same taps for every image of a chunk
+        table.resize(chunk);
+        warp_prefilter_taps(sy, table[0].gy, &table[0].oy, &table[0].nty);
+        warp_prefilter_taps(sx, table[0].gx, &table[0].ox, &table[0].ntx);
+        for (size_t k = 1; k < chunk; ++k) table[k] = table[0];
+        HIP_TRY(hipMemcpyAsync(table_dev, table.data(), chunk * sizeof(ShiftImage), hipMemcpyHostToDevice, ctx->stream));
+    }
+    for (size_t first = 0; first < (size_t)n; first += chunk) {
+        const size_t m = std::min(chunk, (size_t)n - first);
+        const char* src = (const char*)src_dev + first * s_pix * float_size(src_dtype);
+        if (order == 3) {       // the prefilter alone: along x into tmp, along y into coef
+            ShiftArgs f;
+            f.src = src; f.dst = coef; f.img = table_dev; f.part = nullptr; f.n = (int)m; f.ny = sy; f.nx = sx; f.floor = -HUGE_VAL;
+            HIP_TRY(shift_images(src_dtype, RL_F64, f, tmp, nullptr, ctx->stream));
+        }
+        WarpArgs a;
+        a.src = order == 3 ? (const void*)coef : (const void*)src;
+        a.dst = (char*)dst_dev + first * o_pix * float_size(dst_dtype);
+        a.xf = xf_dev + first * kWarpXf;
+        a.part = stats_out ? part : nullptr;
+        a.n = (int)m; a.sy = sy; a.sx = sx; a.oy = oy; a.ox = ox; a.order = order; a.direct = ctx->warp_direct; a.floor = floor;
+        HIP_TRY(warp_images(order == 3 ? RL_F64 : src_dtype, dst_dtype, a, stats_out ? stats + first * kWarpFields : nullptr, ctx->stream));
+    }
+    if (stats_out) HIP_TRY(hipMemcpyAsync(stats_out, stats, (size_t)n * kWarpFields * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));   // (the tables are the call's own)
+    return RL_OK;
+}
+
+extern "C" int rl_affine_sums(rl_ctx* ctx, const void* ref_dev, int ref_dtype, const int64_t* ref_offsets, const void* w_dev, int w_dtype,
+                              const int64_t* w_offsets, int n_pairs, int ny, int nx, int M, double* sums_out) {
+    if (!ctx || !ref_dev || !ref_offsets || !w_dev || !w_offsets || !sums_out) return fail(RL_ERR_INVALID, "NULL argument");
+    if (!float_dtype_ok(ref_dtype) || !float_dtype_ok(w_dtype)) return fail(RL_ERR_INVALID, "dtypes must be RL_F32 or RL_F64");
+    if (n_pairs < 1) return fail(RL_ERR_INVALID, "n_pairs must be at least 1");
+    if (M < 1) return fail(RL_ERR_INVALID, "the margin must be at least 1");
+    if (ny < 1 || nx < 1 || (long long)ny - 2LL * M < 8 || (long long)nx - 2LL * M < 8)
+        return fail(RL_ERR_INVALID, "the interior must be at least 8 x 8 pixels: ny - 2 M >= 8 and nx - 2 M >= 8");
+    if ((long long)ny * nx > 0x7fffffffLL) return fail(RL_ERR_INVALID, "an image must have fewer than 2^31 pixels");
+    for (int i = 0; i < n_pairs; ++i)
+        if (ref_offsets[i] < 0 || w_offsets[i] < 0) return fail(RL_ERR_INVALID, "pair " + std::to_string(i) + ": negative offset");
+    static_assert(kAffFields == RL_AFFINE_FIELDS, "the header's field count");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const AffGeom g = aff_geom(ny, nx, M);
+    const size_t per_part = (size_t)g.nb * kAffFields;
+    const size_t chunk = std::min<size_t>((size_t)n_pairs, std::max<size_t>(1, kRegSumWorkBytes / (per_part * sizeof(double))));
+    const size_t off_bytes = round_up((size_t)n_pairs * sizeof(long long), 256);
+    const size_t tot_bytes = round_up(chunk * kAffFields * sizeof(double), 256);
+    char* w = nullptr;
+    RL_TRY(reg_workspace(ctx, 2 * off_bytes + tot_bytes + chunk * per_part * sizeof(double), &w));
+    long long* a_off = (long long*)w;
+    long long* b_off = (long long*)(w + off_bytes);
+    double* tot = (double*)(w + 2 * off_bytes);
+    double* part = (double*)(w + 2 * off_bytes + tot_bytes);
+    HIP_TRY(hipMemcpyAsync(a_off, ref_offsets, (size_t)n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(b_off, w_offsets, (size_t)n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    for (size_t first = 0; first < (size_t)n_pairs; first += chunk) {
+        const size_t n = std::min(chunk, (size_t)n_pairs - first);
+        AffArgs a;
+        a.a = ref_dev; a.w = w_dev; a.a_off = a_off + first; a.w_off = b_off + first; a.part = part; a.tot = tot; a.pairs = (int)n; a.g = g;
+        HIP_TRY(affine_sums(ref_dtype, w_dtype, a, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(sums_out + first * kAffFields, tot, n * kAffFields * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
     return RL_OK;

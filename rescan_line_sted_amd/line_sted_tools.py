@@ -43,7 +43,9 @@ overlaps the transfers with the iterations.
 Drift: `deconvolve_stack_registered` (registration.py) estimates the translation
 of every view and frame of such a stack on the device and undoes it before the
 iterations; `estimate_shifts` and `shift_images` are its two steps on their own
-(INTEGRATION.md section 5i).
+(INTEGRATION.md section 5i).  Rotation, scale and shear between the views:
+`deconvolve_stack_registered(model='rigid' | 'similarity' | 'affine')`, with
+`estimate_transforms` and `warp_images` on their own (section 5l).
 """
 import os
 import time
@@ -55,6 +57,8 @@ from ._lib import DeconvPlan, RNG_NONE, RNG_PHILOX
 from .tiling import deconvolve_tiled   # noqa: F401  (re-exported)
 from .stack import CameraModel, deconvolve_stack   # noqa: F401  (re-exported)
 from .registration import coarse_shifts, deconvolve_stack_registered, estimate_shifts, shift_images   # noqa: F401  (re-exported)
+from .registration import (compose_transforms, estimate_transforms, invert_transform, transform_matrix_offset,   # noqa: F401  (re-exported)
+                           warp_images)
 from .beads import find_beads, measure_psfs   # noqa: F401  (re-exported)
 from .calibration import calibrate_camera, find_defects, photon_transfer, repair_defects, temporal_stats   # noqa: F401  (re-exported)
 

@@ -11,6 +11,11 @@ SIGN CONVENTION, used everywhere: the shift of an image is the displacement d of
 image[y + d] ~ reference[y].  The correlation surface peaks at d, and shift_images(image, d) undoes it.
 
     estimates, info = deconvolve_stack_registered(raw, psfs, iterations, camera=CameraModel(dark=100.0, gain=0.46))
+
+Rotation, scale and shear between the views: estimate_transforms fits a
+translation, rigid, similarity or affine transform by Gauss-Newton on the intensities over a pyramid (rl_affine_sums forms the normal
+equations on the device, solve_transform solves them here), warp_images resamples through an affine map (rl_warp_images), and
+deconvolve_stack_registered(model=...) composes the view's transform with the frame's shift into one interpolation per image.
 """
 import ctypes
 
@@ -195,6 +200,203 @@ def _estimate_coarse(dev, ref, ref_offsets, mov, mov_offsets, ny, nx, max_shift,
     return shifts, info
 
 
+# ---- host logic: affine transforms (INTEGRATION.md section 5l) -----------------------------------------------------------------------
+# CONVENTION: a transform is T = [L | t], shape (..., 2, 3), in the centred form: with c = ((ny - 1) / 2, (nx - 1) / 2) the image B
+# with transform T relative to the reference A satisfies B(c + L (x - c) + t) ~ A(x); with L = I, t is the shift of estimate_shifts.
+# As a map of output pixels to source positions, T(x) = c + L (x - c) + t, and warp_images(B, T)(x) = B(T(x)).
+MODELS = ('translation', 'rigid', 'similarity', 'affine')
+AFFINE_FIELDS = 45                    # rl_affine_sums
+_PROJECTIONS = {                      # columns of the 8 unknowns (q_0 .. q_5, g, b) a model keeps, as (index, weight) lists
+    'translation': [[(0, 1.0)], [(1, 1.0)], [(6, 1.0)], [(7, 1.0)]],
+    'rigid': [[(0, 1.0)], [(1, 1.0)], [(4, 1.0), (3, -1.0)], [(6, 1.0)], [(7, 1.0)]],
+    'similarity': [[(0, 1.0)], [(1, 1.0)], [(2, 1.0), (5, 1.0)], [(4, 1.0), (3, -1.0)], [(6, 1.0)], [(7, 1.0)]],
+    'affine': [[(k, 1.0)] for k in range(8)],
+}
+MAX_CONDITION = 1e10                  # of the projected system after scaling to a unit diagonal
+
+
+def identity_transforms(n):
+    T = np.zeros((int(n), 2, 3))
+    T[:, 0, 0] = T[:, 1, 1] = 1.0
+    return T
+
+
+def shift_transforms(shifts):
+    """[I | d] for shifts (..., 2) as estimate_shifts returns them."""
+    shifts = np.asarray(shifts, dtype=np.float64)
+    T = np.zeros(shifts.shape[:-1] + (2, 3))
+    T[..., 0, 0] = T[..., 1, 1] = 1.0
+    T[..., 2] = shifts
+    return T
+
+
+def transform_matrix_offset(T, shape):
+    """(..., 6) = (m00, m01, m10, m11, o0, o1) of rl_warp_images -- the matrix and offset of scipy.ndimage.affine_transform -- for
+    transforms (..., 2, 3) of images of `shape`: matrix L, offset c + t - L c."""
+    T = np.asarray(T, dtype=np.float64)
+    c = np.array([(shape[0] - 1) / 2.0, (shape[1] - 1) / 2.0])
+    L, t = T[..., :2], T[..., 2]
+    out = np.empty(T.shape[:-2] + (6,))
+    out[..., :4] = L.reshape(T.shape[:-2] + (4,))
+    out[..., 4:] = c + t - L @ c
+    return out
+
+
+def compose_transforms(first, second):
+    """The transform of applying `first`, then `second`: warp(warp(B, first), second) = warp(B, compose_transforms(first, second)) up
+    to the interpolation -- as maps, first o second: L = L1 L2, t = L1 t2 + t1."""
+    a, b = np.asarray(first, dtype=np.float64), np.asarray(second, dtype=np.float64)
+    out = np.empty(np.broadcast(a, b).shape)
+    out[..., :2] = a[..., :2] @ b[..., :2]
+    out[..., 2] = (a[..., :2] @ b[..., 2:])[..., 0] + a[..., 2]
+    return out
+
+
+def invert_transform(T):
+    """[L^-1 | -L^-1 t]: warp(warp(B, T), invert_transform(T)) ~ B."""
+    T = np.asarray(T, dtype=np.float64)
+    Li = np.linalg.inv(T[..., :2])
+    out = np.empty(T.shape)
+    out[..., :2] = Li
+    out[..., 2] = -(Li @ T[..., 2:])[..., 0]
+    return out
+
+
+def corner_displacement(T, other, shape):
+    """The largest distance in pixels between T(x) and other(x) over the four corners of an image of `shape`."""
+    T, other = np.asarray(T, dtype=np.float64), np.asarray(other, dtype=np.float64)
+    cy, cx = (shape[0] - 1) / 2.0, (shape[1] - 1) / 2.0
+    corners = np.array([[-cy, -cx], [-cy, cx], [cy, -cx], [cy, cx]]).T
+    d = (T[..., :2] - other[..., :2]) @ corners + (T[..., 2:] - other[..., 2:])
+    return np.sqrt((d * d).sum(axis=-2)).max(axis=-1)
+
+
+def solve_transform(sums, model):
+    """One Gauss-Newton step from a pair's row of rl_affine_sums [45], projected on `model`: the 8 x 8 system in (q, g, b) of
+    a ~ g w + b + phi q restricted to the model's columns, scaled to a unit diagonal, solved in float64; d = q / g.  Returns a dict:
+    'dt' (2,), 'dL' (2, 2) -- the update is t <- t + L dt, L <- L (I + dL) --, 'gain', 'offset', 'residual' (the root of the residual
+    sum of squares over the reference's centred sum of squares) and 'flat' (a diagonal entry that is not positive, a condition number
+    above 1e10 or not finite, g <= 0, a reference without variance: the step is zero).  The device path and its numpy twin share it."""
+    sums = np.asarray(sums, dtype=np.float64)
+    G = np.zeros((8, 8))
+    G[np.triu_indices(8)] = sums[:36]
+    G = G + np.triu(G, 1).T
+    r, saa, n = sums[36:44], sums[44], sums[35]
+    cols = _PROJECTIONS[model]
+    P = np.zeros((8, len(cols)))
+    for k, col in enumerate(cols):
+        for i, wgt in col:
+            P[i, k] = wgt
+    flat = dict(dt=np.zeros(2), dL=np.zeros((2, 2)), gain=0.0, offset=0.0, residual=0.0, flat=True)
+    Gp, rp = P.T @ G @ P, P.T @ r
+    d = np.diag(Gp)
+    if not np.all(np.isfinite(Gp)) or not np.all(np.isfinite(rp)) or not np.all(d > 0.0) or not n > 0.0:
+        return flat
+    d = np.sqrt(d)
+    Gs = Gp / np.outer(d, d)
+    cond = np.linalg.cond(Gs)
+    var = saa - r[7] * r[7] / n
+    if not np.isfinite(cond) or cond > MAX_CONDITION or not var > 0.0:
+        return flat
+    eta = np.linalg.solve(Gs, rp / d) / d
+    theta = P @ eta
+    g = theta[6]
+    if not np.all(np.isfinite(theta)) or not g > 0.0:
+        return flat
+    q = theta[:6] / g
+    rss = saa - float(eta @ rp)
+    return dict(dt=q[:2].copy(), dL=q[2:].reshape(2, 2).copy(), gain=float(g), offset=float(theta[7]),
+                residual=float(np.sqrt(max(rss, 0.0) / var)), flat=False)
+
+
+def update_transform(T, step, model):
+    """The forward-compositional update of T (2, 3) by a step of solve_transform: t <- t + L dt, L <- L (I + dL); 'rigid' puts L
+    back on the rotations (the orthogonal factor of its polar decomposition)."""
+    L, t = T[:, :2], T[:, 2]
+    out = np.empty((2, 3))
+    out[:, 2] = t + L @ step['dt']
+    Ln = L @ (np.eye(2) + step['dL'])
+    if model == 'rigid':
+        u, _, vt = np.linalg.svd(Ln)
+        Ln = u @ vt
+        if np.linalg.det(Ln) < 0.0:
+            Ln = u @ np.diag([1.0, -1.0]) @ vt
+    out[:, :2] = Ln
+    return out
+
+
+def pyramid_shapes(ny, nx, min_side):
+    """The levels' shapes, finest first: halved (rounded down) while the halved shorter side is at least min_side."""
+    shapes = [(ny, nx)]
+    while min(shapes[-1]) // 2 >= min_side:
+        shapes.append((shapes[-1][0] // 2, shapes[-1][1] // 2))
+    return shapes
+
+
+BIN2 = (2.0, 0.0, 0.0, 2.0, 0.5, 0.5)     # rl_warp_images order 1 with this map is the 2 x 2 mean
+
+
+def _check_model(ny, nx, model, passes, min_side, margin):
+    if model not in MODELS:
+        raise ValueError('model: one of %s; got %r' % (', '.join(MODELS), model))
+    passes, min_side, margin = int(passes), int(min_side), int(margin)
+    if passes < 1:
+        raise ValueError('passes must be at least 1')
+    if margin < 1:
+        raise ValueError('margin must be at least 1')
+    if min_side < 2 * margin + 8:
+        raise ValueError('min_side must be at least 2 margin + 8 = %d (the interior of the coarsest level); got %d' % (2 * margin + 8, min_side))
+    if ny - 2 * margin < 8 or nx - 2 * margin < 8:
+        raise ValueError('a %d x %d image leaves no 8 x 8 interior inside a margin of %d' % (ny, nx, margin))
+    return passes, min_side, margin
+
+
+def _estimate_transforms(dev, ref, ref_offsets, mov, mov_offsets, ny, nx, model, passes, min_side, margin, init=None):
+    """estimate_transforms for the pairs (ref at ref_offsets[i], mov at mov_offsets[i]) through dev.alloc, dev.gather_warp and
+    dev.affine_sums.  The pyramid of both images by 2 x binning (rl_warp_images order 1), then per level, coarsest first, `passes`
+    passes of: the moving image warped by the current transform (order 3) into a float64 scratch, rl_affine_sums, solve_transform,
+    update_transform.  A fixed sequence of device calls whatever the data.  Returns (T (N, 2, 3), info)."""
+    N = len(mov_offsets)
+    shapes = pyramid_shapes(ny, nx, min_side)
+    uniq = sorted(set(ref_offsets))
+    ref_index = [uniq.index(o) for o in ref_offsets]
+    refs, movs = [(ref, list(uniq))], [(mov, list(mov_offsets))]
+    for lv in range(1, len(shapes)):
+        (py, px), (sy, sx) = shapes[lv - 1], shapes[lv]
+        for chain, count in ((refs, len(uniq)), (movs, N)):
+            buf = dev.alloc(count * sy * sx, 'f64')
+            dev.gather_warp(chain[-1][0], chain[-1][1], py, px, np.tile(BIN2, (count, 1)), 1, buf, sy, sx)
+            chain.append((buf, [k * sy * sx for k in range(count)]))
+    scratch = dev.alloc(N * ny * nx, 'f64')
+    T = identity_transforms(N)
+    if init is not None:
+        T[:, :, 2] = np.asarray(init, dtype=np.float64).reshape(N, 2)
+    T[:, :, 2] /= 2.0 ** (len(shapes) - 1)
+    flat = np.zeros(N, dtype=bool)
+    gain, offset, residual, step = np.zeros(N), np.zeros(N), np.zeros(N), np.zeros(N)
+    for lv in range(len(shapes) - 1, -1, -1):
+        sy, sx = shapes[lv]
+        for _ in range(passes):
+            dev.gather_warp(movs[lv][0], movs[lv][1], sy, sx, transform_matrix_offset(T, (sy, sx)), 3, scratch, sy, sx)
+            S = dev.affine_sums(refs[lv][0], [refs[lv][1][k] for k in ref_index], scratch, [k * sy * sx for k in range(N)], sy, sx, margin)
+            for i in range(N):
+                if flat[i]:
+                    continue
+                s = solve_transform(S[i], model)
+                if s['flat']:
+                    flat[i] = True
+                    continue
+                new = update_transform(T[i], s, model)
+                gain[i], offset[i], residual[i] = s['gain'], s['offset'], s['residual']
+                step[i] = corner_displacement(new, T[i], (sy, sx)) * 2.0 ** lv
+                T[i] = new
+        if lv:
+            T[:, :, 2] *= 2.0
+    T[flat] = identity_transforms(1)[0]
+    gain[flat] = offset[flat] = residual[flat] = step[flat] = 0.0
+    return T, {'gain': gain, 'offset': offset, 'residual': residual, 'step': step, 'flat': flat, 'levels': len(shapes)}
+
+
 # ---- the device ----------------------------------------------------------------------------------------------------------------------
 class _Buffer:
     """A device allocation of `elements` values of dtype 'f32' / 'f64' (or raw bytes: dtype None)."""
@@ -318,6 +520,34 @@ class _Device:
                 m += 1
             self.shift(src, offsets[k], m, ny, nx, shifts[k:k + m], order, None, dst, k * ny * nx)
             k += m
+
+    def warp(self, src, src_element, n, sy, sx, xf, order, floor, dst, dst_element, oy, ox):
+        """rl_warp_images on n consecutive images of sy x sx into n images of oy x ox; xf (n, 6); returns the statistics [n][2]."""
+        xf = np.ascontiguousarray(xf, dtype=np.float64).reshape(n, 6)
+        stats = np.empty((n, 2))
+        check(lib.rl_warp_images(self.ctx.handle, src.at(src_element), DTYPES[src.dtype], n, sy, sx, _lib.ptr(xf), order,
+                                 -np.inf if floor is None else float(floor), dst.at(dst_element), DTYPES[dst.dtype], oy, ox, _lib.ptr(stats)))
+        return stats
+
+    def gather_warp(self, src, offsets, sy, sx, xf, order, dst, oy, ox):
+        """The images at the element offsets of src, each through its map (no floor), to consecutive images of dst; runs of
+        consecutive images go through one call."""
+        offsets, k = list(offsets), 0
+        while k < len(offsets):
+            m = 1
+            while k + m < len(offsets) and offsets[k + m] == offsets[k] + m * sy * sx:
+                m += 1
+            self.warp(src, offsets[k], m, sy, sx, xf[k:k + m], order, None, dst, k * oy * ox, oy, ox)
+            k += m
+
+    def affine_sums(self, ref, ref_offsets, w, w_offsets, ny, nx, M):
+        """rl_affine_sums: S [pairs][45]."""
+        n = len(w_offsets)
+        ro, wo = np.ascontiguousarray(ref_offsets, dtype=np.int64), np.ascontiguousarray(w_offsets, dtype=np.int64)
+        S = np.empty((n, AFFINE_FIELDS))
+        check(lib.rl_affine_sums(self.ctx.handle, ref.ptr, DTYPES[ref.dtype], ro.ctypes.data_as(_I64P), w.ptr, DTYPES[w.dtype],
+                                 wo.ctypes.data_as(_I64P), n, ny, nx, M, _lib.ptr(S)))
+        return S
 
     def iterate(self, iterations):
         """The measurement buffer was written on the device: from ones, `iterations` iterations; returns the estimates (B, ny, nx)."""
@@ -456,9 +686,83 @@ def shift_images(images, shifts, order=3, floor=None, device=None):
         dev.close()
 
 
+def _check_transforms(transforms, shape, name='transforms'):
+    T = np.asarray(transforms, dtype=np.float64)
+    if T.shape != shape or not np.all(np.isfinite(T)):
+        raise ValueError('%s: expected finite values of shape %s; got shape %s' % (name, shape, T.shape))
+    return T
+
+
+def warp_images(images, transforms, order=3, floor=None, output_shape=None, device=None):
+    """max(scipy.ndimage.affine_transform(images[i], L_i, offset=c + t_i - L_i c, output_shape=..., order=order, mode='mirror'),
+    floor) for every image, on the device (rl_warp_images): image i sampled at T_i(x) = c + L_i (x - c) + t_i -- transforms as
+    estimate_transforms returns them undo the rotation, scale and displacement.  images: (N, ny, nx) or (ny, nx), float32 or float64;
+    transforms: (N, 2, 3) or (2, 3) in the centred form [L | t], c = ((ny - 1) / 2, (nx - 1) / 2) of the IMAGE.  The result has the
+    images' dtype (computed in float64, rounded once) and output_shape (default: the images').  order: 3 (cubic B-spline) or 1
+    (bilinear; with L = I and integer t a bit-exact copy of the displaced pixels).  floor: None or the least value of the output."""
+    images, dt = _float_images(images, 'images')
+    single = images.ndim == 2
+    if single:
+        images = images[None]
+    if images.ndim != 3 or 0 in images.shape:
+        raise ValueError('images: expected (N, ny, nx) or (ny, nx); got shape %s' % (images.shape,))
+    N, ny, nx = images.shape
+    T = np.asarray(transforms, dtype=np.float64)
+    T = _check_transforms(T[None] if T.ndim == 2 else T, (N, 2, 3))
+    if order not in (1, 3):
+        raise ValueError('order must be 1 or 3; got %r' % (order,))
+    if floor is not None and np.isnan(floor):
+        raise ValueError('floor is nan')
+    oy, ox = (ny, nx) if output_shape is None else (int(output_shape[0]), int(output_shape[1]))
+    if oy < 1 or ox < 1:
+        raise ValueError('output_shape must be at least 1 x 1; got %r' % (output_shape,))
+    dev = _Device(device=_lib.DEFAULT_DEVICE if device is None else device)
+    try:
+        src, dst = dev.alloc(images.size, dt), dev.alloc(N * oy * ox, dt)
+        dev.upload(src, images)
+        dev.warp(src, 0, N, ny, nx, transform_matrix_offset(T, (ny, nx)), order, floor, dst, 0, oy, ox)
+        out = dev.download(dst, N * oy * ox).astype(images.dtype).reshape(N, oy, ox)      # (exact: the values are of that type)
+        return out[0] if single else out
+    finally:
+        dev.close()
+
+
+def estimate_transforms(images, reference, model='rigid', passes=5, min_side=48, margin=4, init=None, device=None):
+    """The transform [L | t] of every image relative to its reference, B(c + L (x - c) + t) ~ A(x), by Gauss-Newton on the
+    intensities over a pyramid.  images: (N, ny, nx) or (ny, nx), float32 or float64; reference: (ny, nx), shared, or (N, ny, nx).
+    model: 'translation', 'rigid' (rotation), 'similarity' (rotation and isotropic scale) or 'affine'; a gain and an offset between
+    the two images are solved with the geometry in every model.  The pyramid: 2 x 2 binning of both images while the halved
+    shorter side is at least min_side.  Per level, coarsest first, `passes` passes of: warp by the current transform (order 3),
+    rl_affine_sums, solve_transform, update_transform; there is no data-dependent exit.  margin: pixels at every border kept out of
+    the sums at every level (min_side >= 2 margin + 8).  init: None or shifts (N, 2) from estimate_shifts -- needed where the
+    displacement exceeds a few pixels of the coarsest level.  Returns (transforms (N, 2, 3), info) with info['gain'], 'offset',
+    'residual' (root of the residual over the reference's centred sum of squares) and 'step' (the last step's largest corner
+    displacement in pixels: small where the iteration has settled), each (N,), 'flat' (N,) -- a singular or ill-conditioned system or
+    a gain that is not positive: the identity is returned for that pair -- and 'levels'."""
+    images, dt, reference, rdt = _pairs_on_device(images, reference)
+    N, ny, nx = images.shape
+    passes, min_side, margin = _check_model(ny, nx, model, passes, min_side, margin)
+    if init is not None:
+        init = np.asarray(init, dtype=np.float64)
+        if init.shape not in ((N, 2), (2,)) or not np.all(np.isfinite(init)):
+            raise ValueError('init: expected finite shifts of shape %s; got %s' % ((N, 2), init.shape))
+        init = np.broadcast_to(init, (N, 2))
+    dev = _Device(device=_lib.DEFAULT_DEVICE if device is None else device)
+    try:
+        mov, ref = dev.alloc(images.size, dt), dev.alloc(reference.size, rdt)
+        dev.upload(mov, images)
+        dev.upload(ref, reference)
+        n_pix = ny * nx
+        return _estimate_transforms(dev, ref, [i * n_pix if reference.ndim == 3 else 0 for i in range(N)], mov, [i * n_pix for i in range(N)],
+                                    ny, nx, model, passes, min_side, margin, init)
+    finally:
+        dev.close()
+
+
 def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame-view', roi=None, dtype='f32', batch=None, shifts=None,
                                 register=('views', 'frames'), max_shift=8, refine=1, interp=3, acceleration=None, tv_lambda=None,
-                                tv_epsilon=0.1, device=None, coarse=None, pipeline=False, out_dtype=None, out_scale=1.0, out=None):
+                                tv_epsilon=0.1, device=None, coarse=None, pipeline=False, out_dtype=None, out_scale=1.0, out=None,
+                                model='translation', view_transforms=None):
     """deconvolve_stack with every image registered on the device before the iterations.  raw, camera, order, roi, dtype, batch,
     acceleration, tv_lambda, tv_epsilon: exactly those of deconvolve_stack.
     register: 'frames' in it -- image (f, v) is registered to image (0, v), the same PSF: drift over time; 'views' in it -- image
@@ -478,6 +782,15 @@ def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame
     the narrow export -- out_dtype 'f32' (default), 'f64' or 'u16', out_scale and out exactly as for deconvolve_stack (page-locked
     raw and out arrays are copied to and from directly).  The shifts, the fields and, with out_dtype='f64', the estimates are the bits
     of pipeline=False.  Not with coarse; out_dtype, out_scale and out only with pipeline=True.
+    model: 'translation' (the default: everything above, call for call), or 'rigid', 'similarity', 'affine' -- the views of a line
+    scan differ by a residual rotation and magnification that no shift undoes: image (0, v) is registered to (0, 0) with
+    estimate_transforms(model) (5 passes, min_side 48, margin 4) in place of the view shift, the frames (f, v) to (0, v) by translation
+    as above, the two are composed to [L_v | t_v + d_fv], and ONE rl_warp_images (order interp, floor camera.epsilon) per image writes
+    the plan's measurement.  view_transforms: (V, 2, 3) skips the view estimate -- a calibration measured once on beads or a test
+    target; a chunk whose L are all exactly the identity goes through rl_shift_images, so identities give the bits of the translation
+    path.  With shifts= given they are the frame shifts d.  No flux rescaling by |det L| is applied.  Not with pipeline=True.  info
+    gains 'transforms' (F, V, 2, 3) as applied ('shifts' is their t), 'view_transforms' (V, 2, 3) and 'view_fit' (the info of
+    estimate_transforms for views 1 .., or None); 'view_flat' marks a view whose fit was flat (it gets the identity).
     Returns (estimates (F, ny, nx) float64 -- pipeline: of out_dtype --, info); info: the ingest statistics of deconvolve_stack
     ('level', 'clipped', 'saturated', 'invalid', each (F, V)), 'shifts' (F, V, 2) as applied, 'ncc', 'at_limit', 'flat' (F, V) of the
     frame estimates, 'view_ncc', 'view_at_limit', 'view_flat' (V,) of the view estimates, 'raised' (F, V) pixels raised to
@@ -494,6 +807,11 @@ def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame
     register = (register,) if isinstance(register, str) else tuple(register)
     if any(r not in ('views', 'frames') for r in register):
         raise ValueError("register: any of 'views', 'frames'; got %r" % (register,))
+    if model not in MODELS:
+        raise ValueError('model: one of %s; got %r' % (', '.join(MODELS), model))
+    affine = model != 'translation' or view_transforms is not None
+    if affine and pipeline:
+        raise ValueError("pipeline=True serves translations alone: model must be 'translation' and view_transforms None")
     if pipeline:
         if coarse is not None:
             raise ValueError('pipeline=True serves the window alone: coarse must be None')
@@ -527,6 +845,11 @@ def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame
         max_shift, refine, margin = _check_search(ny, nx, max_shift, refine, None)
         coarse = _check_coarse(ny, nx, coarse, max_shift, None)
     estimating = given is None and bool(register)
+    view_T, view_fit = identity_transforms(V), None
+    if view_transforms is not None:
+        view_T = _check_transforms(view_transforms, (V, 2, 3), 'view_transforms').copy()
+    elif affine and given is None and 'views' in register and V > 1:
+        _check_model(ny, nx, model, 5, 48, 4)
     if pipeline:
         return _registered_pipeline(raw, code, psfs, int(iterations), camera, order, (sy, sx), (y0, x0, ny, nx), dtype, batch, given, register,
                                     max_shift, refine, interp, acceleration, tv_lambda, tv_epsilon,
@@ -547,6 +870,7 @@ def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame
         out = np.empty((F, ny, nx))
         ingest_stats, applied, raised = np.zeros((F, V, INGEST_FIELDS)), np.zeros((F, V, 2)), np.zeros((F, V), dtype=np.int64)
         value, at_limit, flat = np.zeros((F, V)), np.zeros((F, V), dtype=bool), np.zeros((F, V), dtype=bool)
+        transforms = identity_transforms(F * V).reshape(F, V, 2, 3)
         view_shift, view_info = np.zeros((V, 2)), {'ncc': np.zeros(V), 'at_limit': np.zeros(V, dtype=bool), 'flat': np.zeros(V, dtype=bool)}
         use_coarse = coarse if estimating else None
         coarse_c, coarse_snr = np.zeros((F, V, 2), dtype=np.int64), np.zeros((F, V))
@@ -570,7 +894,12 @@ def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame
             if given is not None:
                 chunk[:nt] = given[first:first + nt]
             else:
-                if first == 0 and 'views' in register and V > 1:
+                if first == 0 and 'views' in register and V > 1 and affine:
+                    if view_transforms is None:
+                        view_T[1:], view_fit = _estimate_transforms(dev, refs, [0] * (V - 1), refs, [v * n_pix for v in range(1, V)], ny, nx,
+                                                                   model, 5, 48, 4)
+                        view_info['flat'][1:] = view_fit['flat']
+                elif first == 0 and 'views' in register and V > 1:
                     view_shift[1:], vi = _estimate(dev, refs, [0] * (V - 1), refs, [v * n_pix for v in range(1, V)], ny, nx, max_shift, refine,
                                                    margin, scratch, coarse=use_coarse)
                     for k in view_info:
@@ -588,7 +917,18 @@ def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame
                                 coarse_c[first + f, v], coarse_snr[first + f, v] = fi['coarse'][k], fi['coarse_snr'][k]
                             value[first + f, v], at_limit[first + f, v], flat[first + f, v] = fi['ncc'][k], fi['at_limit'][k], fi['flat'][k]
                 chunk[:nt] += view_shift
-            st = dev.shift(staging, 0, batch * V, ny, nx, chunk.reshape(-1, 2), interp, camera.epsilon, meas)
+            if affine:                                           # frame shift o view transform: [L_v | t_v + d_fv], ONE interpolation
+                Tc = np.broadcast_to(view_T, (batch, V, 2, 3)).copy()
+                Tc[..., 2] += chunk
+                transforms[first:first + nt] = Tc[:nt]
+                chunk = Tc[..., 2]
+                if np.any(Tc[..., :2] != np.eye(2)):
+                    st = dev.warp(staging, 0, batch * V, ny, nx, transform_matrix_offset(Tc.reshape(-1, 2, 3), (ny, nx)), interp, camera.epsilon,
+                                  meas, 0, ny, nx)
+                else:                                            # translations alone: the shift's fused passes, the bits of that path
+                    st = dev.shift(staging, 0, batch * V, ny, nx, chunk.reshape(-1, 2), interp, camera.epsilon, meas)
+            else:
+                st = dev.shift(staging, 0, batch * V, ny, nx, chunk.reshape(-1, 2), interp, camera.epsilon, meas)
             applied[first:first + nt] = chunk[:nt]
             raised[first:first + nt] = st[:, 0].reshape(batch, V)[:nt].astype(np.int64)
             out[first:first + nt] = dev.iterate(iterations)[:nt]
@@ -598,6 +938,8 @@ def deconvolve_stack_registered(raw, psfs, iterations, camera=None, order='frame
                 'view_at_limit': view_info['at_limit'], 'view_flat': view_info['flat'], 'raised': raised,
                 'unresolved': dev.unresolved(), 'strategy': dev.strategy(), 'chunks': -(-F // batch), 'batch': batch}
         info.update(camera.defect_info())
+        if affine:
+            info.update({'transforms': transforms, 'view_transforms': view_T, 'view_fit': view_fit})
         if use_coarse is not None:
             info.update({'coarse': coarse_c, 'coarse_snr': coarse_snr, 'view_coarse': view_coarse, 'view_coarse_snr': view_coarse_snr})
         return out, info
