@@ -12,21 +12,6 @@ using namespace rl;
 
 namespace {
 constexpr long long kMaxGrid = 0x7fffffffll;
-
-size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-int bead_workspace(rl_ctx* ctx, size_t bytes, char** out) {
-    if (bytes > ctx->beads.work_bytes) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->beads.work) (void)hipFree(ctx->beads.work);
-        ctx->beads.work = nullptr;
-        ctx->beads.work_bytes = 0;
-        HIP_TRY(hipMalloc(&ctx->beads.work, bytes));
-        ctx->beads.work_bytes = bytes;
-    }
-    *out = (char*)ctx->beads.work;
-    return RL_OK;
-}
 }  // namespace
 
 extern "C" int rl_find_peaks_chunk_bytes(rl_ctx* ctx, size_t bytes) {
@@ -40,7 +25,7 @@ extern "C" int rl_find_peaks(rl_ctx* ctx, const void* src_dev, int src_dtype, co
                              double* s_out, double* x_out, int64_t* count_out, double* levels_out) {
     if (!ctx || !src_dev || !offsets || !taps || !yx_out || !s_out || !x_out || !count_out || !levels_out)
         return fail(RL_ERR_INVALID, "NULL argument");
-    if (src_dtype != RL_F32 && src_dtype != RL_F64) return fail(RL_ERR_INVALID, "src_dtype must be RL_F32 or RL_F64");
+    if (!dtype_ok(src_dtype)) return fail(RL_ERR_INVALID, "src_dtype must be RL_F32 or RL_F64");
     if (n < 1) return fail(RL_ERR_INVALID, "n must be at least 1");
     if (h < 0 || h > kBpMaxH) return fail(RL_ERR_INVALID, "h must lie in 0 .. 16");
     if (r < 1 || r > kBpMaxR) return fail(RL_ERR_INVALID, "the suppression radius must lie in 1 .. 16");
@@ -61,27 +46,32 @@ extern "C" int rl_find_peaks(rl_ctx* ctx, const void* src_dev, int src_dtype, co
     a.ntx = (ndx + kBpTX - 1) / kBpTX;
     const long long tiles = (long long)a.nty * a.ntx;
     if (tiles > kMaxGrid) return fail(RL_ERR_INVALID, "the image has more tiles than a launch can hold");
-    const size_t part_b = round_up((size_t)tiles * 2 * sizeof(double), 256), mask_b = round_up((size_t)ndy * a.ntx * sizeof(unsigned), 256);
-    const size_t yx_b = round_up((size_t)cap * 2 * sizeof(int), 256), val_b = round_up((size_t)cap * sizeof(double), 256);
-    const size_t per = part_b + mask_b + yx_b + 2 * val_b;
-    size_t chunk = std::min<size_t>((size_t)n, std::max<size_t>(1, ctx->beads_cap / per));
+    // what one image takes of the workspace: its tile partials, mask, and the cap candidates' positions and two values
+    const size_t part_n = (size_t)tiles * 2, mask_n = (size_t)ndy * a.ntx, yx_n = (size_t)cap * 2, val_n = (size_t)cap;
+    WorkLayout one;
+    one.add<double>(part_n);
+    one.add<unsigned>(mask_n);
+    one.add<int>(yx_n);
+    one.add<double>(val_n, 2);
+    size_t chunk = chunk_under(ctx->beads_cap, one.bytes(), (size_t)n);
     chunk = std::min<size_t>(chunk, (size_t)(kMaxGrid / tiles));
-    const size_t taps_b = round_up((size_t)(2 * h + 1) * sizeof(double), 256), off_b = round_up((size_t)n * sizeof(long long), 256);
-    const size_t lev_b = round_up(chunk * kBpLevels * sizeof(double), 256), cnt_b = round_up(chunk * sizeof(long long), 256);
+    WorkLayout lay;
+    const auto r_taps = lay.add<double>((size_t)(2 * h + 1));
+    const auto r_off = lay.add<long long>((size_t)n);
+    const auto r_lev = lay.add<double>(chunk * kBpLevels);
+    const auto r_cnt = lay.add<long long>(chunk);
+    // (each of these holds chunk padded per-image slots; the kernels index it [img][...] with the unpadded strides, which fit)
+    const auto r_part = lay.add<double>(part_n, chunk);
+    const auto r_mask = lay.add<unsigned>(mask_n, chunk);
+    const auto r_yx = lay.add<int>(yx_n, chunk);
+    const auto r_sv = lay.add<double>(val_n, chunk), r_xv = lay.add<double>(val_n, chunk);
     char* w = nullptr;
-    RL_TRY(bead_workspace(ctx, taps_b + off_b + lev_b + cnt_b + chunk * per, &w));
-    char* q = w;
-    double* w_dev = (double*)q; q += taps_b;
-    long long* off_dev = (long long*)q; q += off_b;
+    RL_TRY(ctx->beads.reserve(ctx->stream, lay.bytes(), &w));
+    double* w_dev = r_taps.at(w);
+    long long* off_dev = r_off.at(w);
     a.w = w_dev;
-    a.levels = (double*)q; q += lev_b;
-    a.count = (long long*)q; q += cnt_b;
-    a.part = (double*)q; q += chunk * part_b;
-    a.mask = (unsigned*)q; q += chunk * mask_b;
-    a.yx = (int*)q; q += chunk * yx_b;
-    a.sv = (double*)q; q += chunk * val_b;
-    a.xv = (double*)q;
-    // (each region holds chunk padded per-image sizes; the kernels index it [img][...] with the unpadded strides, which fit)
+    a.levels = r_lev.at(w); a.count = r_cnt.at(w);
+    a.part = r_part.at(w); a.mask = r_mask.at(w); a.yx = r_yx.at(w); a.sv = r_sv.at(w); a.xv = r_xv.at(w);
     HIP_TRY(hipMemcpyAsync(w_dev, taps, (size_t)(2 * h + 1) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(off_dev, offsets, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     std::vector<double> lev(chunk * kBpLevels), sv(chunk * (size_t)cap), xv(chunk * (size_t)cap);

@@ -95,7 +95,7 @@ extern "C" int rl_calib_sums(rl_calib* c, void* sum_host, void* sumsq_host) {
 extern "C" int rl_calib_finalize(rl_calib* c, double* mean_dev, double* var_dev) {
     if (!c || (!mean_dev && !var_dev)) return fail(RL_ERR_INVALID, "NULL argument");
     if (c->frames < 1) return fail(RL_ERR_INVALID, "no frame has been accumulated");
-    if (mean_dev && var_dev && (const char*)mean_dev < (const char*)var_dev + c->n_pix() * 8 && (const char*)var_dev < (const char*)mean_dev + c->n_pix() * 8)
+    if (mean_dev && var_dev && overlaps(mean_dev, c->n_pix() * 8, var_dev, c->n_pix() * 8))
         return fail(RL_ERR_INVALID, "the two maps overlap");
     HIP_TRY(hipSetDevice(c->ctx->device));
     HIP_TRY(calib_finalize(c->raw_dtype, c->sum, c->sumsq, c->frames, c->n_pix(), mean_dev, var_dev, c->ctx->stream));
@@ -111,7 +111,7 @@ extern "C" int rl_calib_reset(rl_calib* c) {
 extern "C" int rl_repair_pixels(rl_ctx* ctx, void* img_dev, int dtype, int n_images, int ny, int nx, const unsigned char* mask_host,
                                 int radius, long long* unrepaired) {
     if (!ctx || !img_dev || !mask_host) return fail(RL_ERR_INVALID, "NULL argument");
-    if (dtype != RL_F32 && dtype != RL_F64) return fail(RL_ERR_INVALID, "dtype must be RL_F32 or RL_F64");
+    if (!dtype_ok(dtype)) return fail(RL_ERR_INVALID, "dtype must be RL_F32 or RL_F64");
     if (n_images < 1 || ny < 1 || nx < 1) return fail(RL_ERR_INVALID, "n_images, ny and nx must be at least 1");
     if ((size_t)ny * (size_t)nx > 0x7fffffffull) return fail(RL_ERR_INVALID, "an image of more than 2^31 - 1 pixels");
     if (radius < 1 || radius > kRepairMaxRadius) return fail(RL_ERR_INVALID, "radius must lie in 1 .. 3");
@@ -122,17 +122,12 @@ extern "C" int rl_repair_pixels(rl_ctx* ctx, void* img_dev, int dtype, int n_ima
         for (int i = 0; i < n_images; ++i) unrepaired[i] = left;
     if (list.empty()) return RL_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = list.size() * sizeof(RepairEntry);
-    if (bytes > ctx->calib.work_bytes) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->calib.work) (void)hipFree(ctx->calib.work);
-        ctx->calib.work = nullptr;
-        ctx->calib.work_bytes = 0;
-        HIP_TRY(hipMalloc(&ctx->calib.work, bytes));
-        ctx->calib.work_bytes = bytes;
-    }
-    HIP_TRY(hipMemcpyAsync(ctx->calib.work, list.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    WorkLayout lay;
+    const auto r_list = lay.add<RepairEntry>(list.size());
+    char* base = nullptr;
+    RL_TRY(ctx->calib.reserve(ctx->stream, lay.bytes(), &base));
+    HIP_TRY(hipMemcpyAsync(r_list.at(base), list.data(), r_list.bytes(), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));   // (the list goes away with this call)
-    HIP_TRY(repair(dtype, img_dev, n_images, (size_t)ny * nx, nx, (const RepairEntry*)ctx->calib.work, (int)list.size(), ctx->stream));
+    HIP_TRY(repair(dtype, img_dev, n_images, (size_t)ny * nx, nx, r_list.at(base), (int)list.size(), ctx->stream));
     return RL_OK;
 }

@@ -298,7 +298,7 @@ int rl_comm_gather_host(rl_comm* c, const double* local, const size_t* counts, i
 int rl_comm_gather_device(rl_comm* c, const void* dev_local, const size_t* counts, int dtype, int root, void* dev_out) {
     if (!c || !counts) return fail(RL_ERR_INVALID, "NULL argument");
     if (root < 0 || root >= c->world) return fail(RL_ERR_INVALID, "no such root rank");
-    if (dtype != RL_F32 && dtype != RL_F64) return fail(RL_ERR_INVALID, "dtype must be RL_F32 or RL_F64");
+    if (!rl::dtype_ok(dtype)) return fail(RL_ERR_INVALID, "dtype must be RL_F32 or RL_F64");
     const size_t mine = counts[c->rank], es = dtype == RL_F32 ? 4 : 8;
     if (mine && !dev_local) return fail(RL_ERR_INVALID, "dev_local is NULL");
     const ncclDataType_t nt = dtype == RL_F32 ? ncclFloat : ncclDouble;

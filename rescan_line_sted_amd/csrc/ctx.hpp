@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <map>
@@ -11,6 +12,7 @@
 
 #include "../../include/rlsted.h"
 #include "kernel_table.hpp"
+#include "work_layout.hpp"
 
 namespace rl {
 std::string& last_error();                 // thread local
@@ -44,27 +46,73 @@ inline int upload_as(int dtype, const std::vector<double>& h, void* dev) {
     }
     return RL_OK;
 }
+// ---- what every C-ABI call checks and sizes the same way ----
+inline bool dtype_ok(int d) { return d == RL_F32 || d == RL_F64; }
+inline size_t dtype_size(int d) { return d == RL_F32 ? sizeof(float) : sizeof(double); }
+inline bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    return (const char*)a < (const char*)b + b_bytes && (const char*)b < (const char*)a + a_bytes;
+}
+// the items of one chunk: as many of the n as stay under the cap, at least one (a larger single item runs alone)
+inline size_t chunk_under(size_t cap_bytes, size_t per_item_bytes, size_t n) {
+    return std::min(n, std::max<size_t>(1, cap_bytes / per_item_bytes));
+}
+// the image offsets of n pairs (the register and affine calls)
+inline int check_pair_offsets(const int64_t* a, const int64_t* b, int n) {
+    for (int i = 0; i < n; ++i)
+        if (a[i] < 0 || b[i] < 0) return fail(RL_ERR_INVALID, "pair " + std::to_string(i) + ": negative offset");
+    return RL_OK;
+}
+// the pixels a margin of M leaves inside an image (the register and affine calls)
+inline int check_interior(int ny, int nx, int M) {
+    if (ny < 1 || nx < 1 || (long long)ny - 2LL * M < 8 || (long long)nx - 2LL * M < 8)
+        return fail(RL_ERR_INVALID, "the interior must be at least 8 x 8 pixels: ny - 2 M >= 8 and nx - 2 M >= 8");
+    return RL_OK;
+}
+
+struct DevBuf {   // scoped device allocation
+    void* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int get(size_t bytes) {
+        HIP_TRY(hipMalloc(&p, bytes ? bytes : 8));
+        return RL_OK;
+    }
+};
+
+// Grow-only device scratch of one family of calls, freed with the context.  A call declares its regions in a WorkLayout
+// (work_layout.hpp), reserves the layout's bytes() here and takes every pointer from the regions' at(base).
+struct Workspace {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    int reserve(hipStream_t stream, size_t need, char** out) {
+        if (need > bytes) {
+            HIP_TRY(hipStreamSynchronize(stream));   // (a call still queued may use the present block)
+            if (ptr) (void)hipFree(ptr);
+            ptr = nullptr;
+            bytes = 0;
+            HIP_TRY(hipMalloc(&ptr, need));
+            bytes = need;
+        }
+        *out = (char*)ptr;
+        return RL_OK;
+    }
+    ~Workspace() { if (ptr) (void)hipFree(ptr); }
+};
 }  // namespace rl
 
 struct rl_ctx {
-    // grow-only device scratch for the PSF pipeline (float64 elements)
-    double* psf_work = nullptr;
-    size_t psf_work_elems = 0;
+    // the PSF pipeline, the figure scans and the f32 transfers of rl_device_upload / rl_device_download: float64 elements, carved
+    // by the callers in double offsets
+    rl::Workspace psf;
     int psf_workspace(size_t elems, double** out) {
-        if (elems > psf_work_elems) {
-            if (psf_work) (void)hipFree(psf_work);
-            psf_work = nullptr;
-            psf_work_elems = 0;
-            HIP_TRY(hipMalloc((void**)&psf_work, elems * sizeof(double)));
-            psf_work_elems = elems;
-        }
-        *out = psf_work;
+        char* p = nullptr;
+        RL_TRY(psf.reserve(stream, elems * sizeof(double), &p));
+        *out = (double*)p;
         return RL_OK;
     }
 
     // rl_ring_stats, rl_ring_sector_stats (ring_api.cpp): the device ring tables, one per (ny, nx, n_rings), the sector tables,
-    // one per (ny, nx, n_rings, n_sectors), and a grow-only workspace; freed with the context (rl_ctx_destroy deletes it with its
-    // device current)
+    // one per (ny, nx, n_rings, n_sectors), and the workspace of a call: its offsets and scales, the results and the spectra of
+    // the pairs in flight; freed with the context (rl_ctx_destroy deletes it with its device current)
     struct RingTable {
         int* row_ptr = nullptr;   // [n_rings + 1]; a sector table's cell_ptr [n_rings * n_sectors + 1]
         int* bins = nullptr;      // [row_ptr[n_rings]]
@@ -72,8 +120,7 @@ struct rl_ctx {
     struct RingCache {
         std::map<std::pair<std::pair<int, int>, int>, RingTable> tables;
         std::map<std::pair<std::pair<int, int>, std::pair<int, int>>, RingTable> sector_tables;
-        void* work = nullptr;
-        size_t work_bytes = 0;
+        rl::Workspace work;
         static void release(RingTable& t) {
             if (t.row_ptr) (void)hipFree(t.row_ptr);
             if (t.bins) (void)hipFree(t.bins);
@@ -81,38 +128,28 @@ struct rl_ctx {
         ~RingCache() {
             for (auto& kv : tables) release(kv.second);
             for (auto& kv : sector_tables) release(kv.second);
-            if (work) (void)hipFree(work);
         }
     } ring;
 
-    // rl_ensemble_stats (ensemble_api.cpp): a grow-only workspace for the offset tables, the partials and the totals; freed with
-    // the context
-    struct EnsembleWork {
-        void* work = nullptr;
-        size_t work_bytes = 0;
-        ~EnsembleWork() {
-            if (work) (void)hipFree(work);
-        }
-    } ensemble;
-    // rl_tile_gather, rl_tile_blend (tile_api.cpp): a grow-only workspace for the slot list / the layout tables of a call; freed
-    // with the context
-    EnsembleWork tile;
-    // rl_ingest, rl_export (stack_api.cpp): a grow-only workspace for the per-workgroup partials of a call's statistics; freed with
-    // the context
-    EnsembleWork ingest;
-    // rl_register_sums, rl_shift_images (register_api.cpp): a grow-only workspace for a call's offsets, taps, partials, totals
-    // and the shift's float64 intermediate; freed with the context
-    EnsembleWork reg;
+    // rl_ensemble_stats (ensemble_api.cpp): the offset tables, the partials and the totals
+    rl::Workspace ensemble;
+    // rl_tile_gather, rl_tile_blend (tile_api.cpp): the slot list / the layout tables of a call
+    rl::Workspace tile;
+    // rl_ingest, rl_export (stack_api.cpp): the per-workgroup partials of a call's statistics
+    rl::Workspace ingest;
+    // rl_register_sums, rl_shift_images and the other calls of register_api.cpp: a call's offsets, taps, partials, totals and the
+    // shift's float64 intermediate
+    rl::Workspace reg;
     // rl_warp_images (register_api.cpp, in the workspace above): warp_cap, the bytes the float64 intermediates of one chunk's images
     // may take (rl_warp_chunk_bytes); warp_direct, 1 when no tile is to be staged in LDS (rl_warp_path)
     size_t warp_cap = (size_t)512 << 20;
     int warp_direct = 0;
-    // rl_find_peaks (bead_api.cpp): a grow-only workspace for a call's taps, offsets, tile partials, levels, masks and candidate
-    // lists; freed with the context.  beads_cap: the bytes the images in flight of one chunk may take (rl_find_peaks_chunk_bytes)
-    EnsembleWork beads;
+    // rl_find_peaks (bead_api.cpp): a call's taps, offsets, tile partials, levels, masks and candidate lists.  beads_cap: the bytes
+    // the images in flight of one chunk may take (rl_find_peaks_chunk_bytes)
+    rl::Workspace beads;
     size_t beads_cap = (size_t)256 << 20;
-    // rl_repair_pixels (calib_api.cpp): a grow-only workspace for a call's defect list; freed with the context
-    EnsembleWork calib;
+    // rl_repair_pixels (calib_api.cpp): a call's defect list
+    rl::Workspace calib;
 
     int device = 0;
     hipStream_t stream = nullptr;
@@ -155,7 +192,7 @@ struct rl_ctx {
         std::vector<double> h(n, 0.0);
         if (count > 0) (column ? t->fill_tw_col[dtype] : t->fill_tw)(h.data());
         void* dev = nullptr;
-        HIP_TRY(hipMalloc(&dev, (dtype == RL_F64 ? sizeof(double) : sizeof(float)) * n));
+        HIP_TRY(hipMalloc(&dev, rl::dtype_size(dtype) * n));
         if (int r = rl::upload_as(dtype, h, dev)) {
             (void)hipFree(dev);
             return r;

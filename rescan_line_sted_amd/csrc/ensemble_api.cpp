@@ -13,25 +13,6 @@ static_assert(kEnsembleFields == RL_ENSEMBLE_FIELDS, "the header's field count i
 
 namespace {
 constexpr int kEnsembleMaxGroupsPerLaunch = 65535;   // grid.y
-
-size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-int ensemble_workspace(rl_ctx* ctx, size_t bytes, char** out) {
-    if (bytes > ctx->ensemble.work_bytes) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->ensemble.work) (void)hipFree(ctx->ensemble.work);
-        ctx->ensemble.work = nullptr;
-        ctx->ensemble.work_bytes = 0;
-        HIP_TRY(hipMalloc(&ctx->ensemble.work, bytes));
-        ctx->ensemble.work_bytes = bytes;
-    }
-    *out = (char*)ctx->ensemble.work;
-    return RL_OK;
-}
-
-bool overlaps(const char* a0, const char* a1, const void* b, size_t bytes) {
-    return b && (const char*)b < a1 && a0 < (const char*)b + bytes;
-}
 }  // namespace
 
 extern "C" int rl_ensemble_stats(rl_ctx* ctx, const void* src_dev, int src_dtype, const int64_t* member_offsets, const int32_t* group_ptr,
@@ -40,8 +21,8 @@ extern "C" int rl_ensemble_stats(rl_ctx* ctx, const void* src_dev, int src_dtype
     if (!ctx || !src_dev || !member_offsets || !group_ptr || !out) return fail(RL_ERR_INVALID, "NULL argument");
     if (n_groups < 1) return fail(RL_ERR_INVALID, "n_groups < 1");
     if (n_pixels < 1) return fail(RL_ERR_INVALID, "n_pixels < 1");
-    if (src_dtype != RL_F32 && src_dtype != RL_F64) return fail(RL_ERR_INVALID, "src_dtype must be RL_F32 or RL_F64");
-    if (truth_dev && truth_dtype != RL_F32 && truth_dtype != RL_F64) return fail(RL_ERR_INVALID, "truth_dtype must be RL_F32 or RL_F64");
+    if (!dtype_ok(src_dtype)) return fail(RL_ERR_INVALID, "src_dtype must be RL_F32 or RL_F64");
+    if (truth_dev && !dtype_ok(truth_dtype)) return fail(RL_ERR_INVALID, "truth_dtype must be RL_F32 or RL_F64");
     if (truth_dev && !truth_offsets) return fail(RL_ERR_INVALID, "a truth buffer without truth_offsets");
     if (group_ptr[0] < 0) return fail(RL_ERR_INVALID, "group_ptr[0] < 0");
     for (int g = 0; g < n_groups; ++g)
@@ -56,36 +37,36 @@ extern "C" int rl_ensemble_stats(rl_ctx* ctx, const void* src_dev, int src_dtype
     if (truth_dev)
         for (int g = 0; g < n_groups; ++g)
             if (truth_offsets[g] < 0) return fail(RL_ERR_INVALID, "negative truth offset");
-    const size_t esize = src_dtype == RL_F32 ? sizeof(float) : sizeof(double);
+    const size_t esize = dtype_size(src_dtype);
     const char* s0 = (const char*)src_dev + (size_t)lo * esize;
-    const char* s1 = (const char*)src_dev + ((size_t)hi + n_pixels) * esize;
+    const size_t s_bytes = ((size_t)hi - (size_t)lo + n_pixels) * esize;
     const size_t map_bytes = (size_t)n_groups * n_pixels * sizeof(double);
-    if (overlaps(s0, s1, mean_dev, map_bytes) || overlaps(s0, s1, var_dev, map_bytes))
+    if ((mean_dev && overlaps(s0, s_bytes, mean_dev, map_bytes)) || (var_dev && overlaps(s0, s_bytes, var_dev, map_bytes)))
         return fail(RL_ERR_INVALID, "a map overlaps the member images");
     HIP_TRY(hipSetDevice(ctx->device));
 
     const int nb = ensemble_blocks(n_pixels, esize);
-    const size_t b_off = round_up(members * 8, 256), b_ptr = round_up(((size_t)n_groups + 1) * 4, 256);
-    const size_t b_grp = round_up((size_t)n_groups * 8, 256);
-    const size_t b_part = round_up((size_t)n_groups * nb * kEnsembleSums * sizeof(double), 256);
-    const size_t b_out = round_up((size_t)n_groups * kEnsembleFields * sizeof(double), 256);
+    WorkLayout lay;
+    const auto r_off = lay.add<int64_t>(members);
+    const auto r_ptr = lay.add<int32_t>((size_t)n_groups + 1);
+    const auto r_toff = lay.add<int64_t>((size_t)n_groups);
+    const auto r_scale = lay.add<double>((size_t)n_groups);
+    const size_t b_tables = lay.bytes();   // the four tables, then what the device alone writes
+    const auto r_part = lay.add<double>((size_t)n_groups * nb * kEnsembleSums);
+    const auto r_out = lay.add<double>((size_t)n_groups * kEnsembleFields);
     char* base = nullptr;
-    RL_TRY(ensemble_workspace(ctx, b_off + b_ptr + 2 * b_grp + b_part + b_out, &base));
-    int64_t* d_off = (int64_t*)base;
-    int32_t* d_ptr = (int32_t*)(base + b_off);
-    int64_t* d_toff = (int64_t*)(base + b_off + b_ptr);
-    double* d_scale = (double*)(base + b_off + b_ptr + b_grp);
-    double* d_part = (double*)(base + b_off + b_ptr + 2 * b_grp);
-    double* d_out = (double*)(base + b_off + b_ptr + 2 * b_grp + b_part);
+    RL_TRY(ctx->ensemble.reserve(ctx->stream, lay.bytes(), &base));
+    int64_t *d_off = r_off.at(base), *d_toff = r_toff.at(base);
+    int32_t* d_ptr = r_ptr.at(base);
+    double *d_scale = r_scale.at(base), *d_part = r_part.at(base), *d_out = r_out.at(base);
 
     // the four tables go up in ONE copy, staged in the device layout (a pageable source: the copy has left it when it returns)
-    const size_t b_tables = b_off + b_ptr + 2 * b_grp;
     std::vector<char> stage(b_tables, 0);
-    std::copy(member_offsets, member_offsets + members, (int64_t*)stage.data());
-    std::copy(group_ptr, group_ptr + n_groups + 1, (int32_t*)(stage.data() + b_off));
+    std::copy(member_offsets, member_offsets + members, r_off.at(stage.data()));
+    std::copy(group_ptr, group_ptr + n_groups + 1, r_ptr.at(stage.data()));
     if (truth_dev) {
-        std::copy(truth_offsets, truth_offsets + n_groups, (int64_t*)(stage.data() + b_off + b_ptr));
-        double* sc = (double*)(stage.data() + b_off + b_ptr + b_grp);
+        std::copy(truth_offsets, truth_offsets + n_groups, r_toff.at(stage.data()));
+        double* sc = r_scale.at(stage.data());
         for (int g = 0; g < n_groups; ++g) sc[g] = truth_scale ? truth_scale[g] : 1.0;
     }
     HIP_TRY(hipMemcpyAsync(base, stage.data(), b_tables, hipMemcpyHostToDevice, ctx->stream));

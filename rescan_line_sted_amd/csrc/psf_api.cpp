@@ -194,11 +194,11 @@ int rl_psf_generate(rl_ctx* ctx, int psf_type, int ny, int nx, double exc_b, dou
         HIP_TRY(psf_blur_axis(L.tmp, L.ry, 1, ny, 1, 1, L.w, radius, s));
         HIP_TRY(psf_delta(L.tmp, 1, nx, 1, s));
         HIP_TRY(psf_blur_axis(L.tmp, L.rx, 1, 1, nx, 2, L.w, radius, s));
-        double* big = nullptr;
+        DevBuf big;
         L.cumu = work + fixed + 32;
         if (ratio > kRatioReserve) {
-            HIP_TRY(hipMalloc((void**)&big, (size_t)ratio * n * sizeof(double)));
-            L.cumu = big;
+            RL_TRY(big.get((size_t)ratio * n * sizeof(double)));
+            L.cumu = (double*)big.p;
         }
         hipError_t e = psf_rescan(sted + (size_t)cy * nx, L.w, radius, L.ry, L.rx, ny, nx, ratio, L.b0, L.cumu, descan,
                                   rescan, s);
@@ -214,11 +214,7 @@ int rl_psf_generate(rl_ctx* ctx, int psf_type, int ny, int nx, double exc_b, dou
             if (e == hipSuccess) e = hipMemcpyAsync(extras.emission, L.g, n * sizeof(double), hipMemcpyDeviceToHost, s);
         }
         if (e == hipSuccess && (extras.unscaled || extras.emission)) e = hipStreamSynchronize(s);
-        if (big) {
-            hipError_t e2 = hipStreamSynchronize(s);
-            (void)hipFree(big);
-            HIP_TRY(e2);
-        }
+        if (big.p) HIP_TRY(hipStreamSynchronize(s));   // (before the block goes away with this scope)
         HIP_TRY(e);
     }
 
@@ -398,12 +394,12 @@ int rl_psf_report_batch(rl_ctx* ctx, int n_sets, const double* params, double* r
     HIP_TRY(hipStreamSynchronize(s));   // the groups' host weight vectors were copied asynchronously
 
     // ---- all sets: saturation maths ----
-    PsfSetDesc* d_sets = nullptr;
-    ReduceJob* d_jobs = nullptr;
+    DevBuf sets_buf, jobs_buf;
     std::vector<ReduceJob> jobs;
-    HIP_TRY(hipMalloc((void**)&d_sets, sizeof(PsfSetDesc) * n_sets));
-    HIP_TRY(hipMalloc((void**)&d_jobs, sizeof(ReduceJob) * 16 * n_sets));
-    struct Free { void *a, *b; ~Free() { (void)hipFree(a); (void)hipFree(b); } } free_guard{d_sets, d_jobs};
+    RL_TRY(sets_buf.get(sizeof(PsfSetDesc) * n_sets));
+    RL_TRY(jobs_buf.get(sizeof(ReduceJob) * 16 * n_sets));
+    PsfSetDesc* d_sets = (PsfSetDesc*)sets_buf.p;
+    ReduceJob* d_jobs = (ReduceJob*)jobs_buf.p;
     auto run_jobs = [&]() -> int {
         HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(ReduceJob) * jobs.size(), hipMemcpyHostToDevice, s));
         HIP_TRY(psf_reduce_jobs(base, base, d_jobs, (int)jobs.size(), s));

@@ -8,17 +8,6 @@
 
 using namespace rl;
 
-namespace {
-struct DevBuf {   // scoped device allocation
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int get(size_t bytes) {
-        HIP_TRY(hipMalloc(&p, bytes ? bytes : 8));
-        return RL_OK;
-    }
-};
-}  // namespace
-
 extern "C" {
 
 int rl_fft2_magnitude(rl_ctx* ctx, const double* x, int n_img, int ny, int nx, double scale, int log1p, double* out) {

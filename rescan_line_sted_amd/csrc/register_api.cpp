@@ -33,26 +33,6 @@ const KernelTable* xcorr_table(int L) {
     return nullptr;
 }
 
-size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-bool float_dtype_ok(int d) { return d == RL_F32 || d == RL_F64; }
-size_t float_size(int d) { return d == RL_F32 ? sizeof(float) : sizeof(double); }
-bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    return (const char*)a < (const char*)b + b_bytes && (const char*)b < (const char*)a + a_bytes;
-}
-
-int reg_workspace(rl_ctx* ctx, size_t bytes, char** out) {
-    if (bytes > ctx->reg.work_bytes) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->reg.work) (void)hipFree(ctx->reg.work);
-        ctx->reg.work = nullptr;
-        ctx->reg.work_bytes = 0;
-        HIP_TRY(hipMalloc(&ctx->reg.work, bytes));
-        ctx->reg.work_bytes = bytes;
-    }
-    *out = (char*)ctx->reg.work;
-    return RL_OK;
-}
-
 // the sums of n pairs (offsets: device arrays) in chunks of `chunk` through tot / part, each chunk followed by its peaks into
 // peaks [n][5] and, when surf is not null, surf [n][nd]; enqueued on the context's stream
 int enqueue_sums_peaks(rl_ctx* ctx, const RegGeom& g, const void* ref, int ref_dtype, const long long* a_off, const void* mov, int mov_dtype,
@@ -70,7 +50,7 @@ int enqueue_sums_peaks(rl_ctx* ctx, const RegGeom& g, const void* ref, int ref_d
 }
 
 size_t sum_chunk(const RegGeom& g, size_t n) {
-    return std::min<size_t>(n, std::max<size_t>(1, kRegSumWorkBytes / (reg_part_doubles(g) * sizeof(double))));
+    return chunk_under(kRegSumWorkBytes, reg_part_doubles(g) * sizeof(double), n);
 }
 }  // namespace
 
@@ -78,27 +58,24 @@ extern "C" int rl_register_sums(rl_ctx* ctx, const void* ref_dev, int ref_dtype,
                                 int mov_dtype, const int64_t* mov_offsets, int n_pairs, int ny, int nx, int R, int M, double* sums_out,
                                 double* ref_out) {
     if (!ctx || !ref_dev || !ref_offsets || !mov_dev || !mov_offsets || !sums_out || !ref_out) return fail(RL_ERR_INVALID, "NULL argument");
-    if (!float_dtype_ok(ref_dtype) || !float_dtype_ok(mov_dtype)) return fail(RL_ERR_INVALID, "dtypes must be RL_F32 or RL_F64");
+    if (!dtype_ok(ref_dtype) || !dtype_ok(mov_dtype)) return fail(RL_ERR_INVALID, "dtypes must be RL_F32 or RL_F64");
     if (n_pairs < 1) return fail(RL_ERR_INVALID, "n_pairs must be at least 1");
     if (R < 1 || R > kRegMaxR) return fail(RL_ERR_INVALID, "the search radius must lie in 1 .. 32");
     if (M < R) return fail(RL_ERR_INVALID, "the margin must be at least the search radius");
-    if (ny < 1 || nx < 1 || (long long)ny - 2LL * M < 8 || (long long)nx - 2LL * M < 8)
-        return fail(RL_ERR_INVALID, "the interior must be at least 8 x 8 pixels: ny - 2 M >= 8 and nx - 2 M >= 8");
-    for (int i = 0; i < n_pairs; ++i)
-        if (ref_offsets[i] < 0 || mov_offsets[i] < 0) return fail(RL_ERR_INVALID, "pair " + std::to_string(i) + ": negative offset");
+    RL_TRY(check_interior(ny, nx, M));
+    RL_TRY(check_pair_offsets(ref_offsets, mov_offsets, n_pairs));
     static_assert(kRegFields == RL_REGISTER_FIELDS && kShiftFields == RL_SHIFT_FIELDS, "the header's field counts");
     HIP_TRY(hipSetDevice(ctx->device));
     const RegGeom g = reg_geom(ny, nx, R, M);
     const size_t per_tot = (size_t)g.nd * kRegFields + 2, per_part = reg_part_doubles(g);
-    const size_t chunk = std::min<size_t>((size_t)n_pairs, std::max<size_t>(1, kRegSumWorkBytes / (per_part * sizeof(double))));
-    const size_t off_bytes = round_up((size_t)n_pairs * sizeof(long long), 256);
-    const size_t tot_bytes = round_up(chunk * per_tot * sizeof(double), 256);
+    const size_t chunk = sum_chunk(g, (size_t)n_pairs);
+    WorkLayout lay;
+    const auto r_a = lay.add<long long>((size_t)n_pairs), r_b = lay.add<long long>((size_t)n_pairs);
+    const auto r_tot = lay.add<double>(chunk * per_tot), r_part = lay.add<double>(chunk * per_part);
     char* w = nullptr;
-    RL_TRY(reg_workspace(ctx, 2 * off_bytes + tot_bytes + chunk * per_part * sizeof(double), &w));
-    long long* a_off = (long long*)w;
-    long long* b_off = (long long*)(w + off_bytes);
-    double* tot = (double*)(w + 2 * off_bytes);
-    double* part = (double*)(w + 2 * off_bytes + tot_bytes);
+    RL_TRY(ctx->reg.reserve(ctx->stream, lay.bytes(), &w));
+    long long *a_off = r_a.at(w), *b_off = r_b.at(w);
+    double *tot = r_tot.at(w), *part = r_part.at(w);
     static_assert(sizeof(long long) == sizeof(int64_t), "offsets are copied as they are");
     HIP_TRY(hipMemcpyAsync(a_off, ref_offsets, (size_t)n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(b_off, mov_offsets, (size_t)n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
@@ -123,14 +100,14 @@ extern "C" int rl_register_sums(rl_ctx* ctx, const void* ref_dev, int ref_dtype,
 extern "C" int rl_shift_images(rl_ctx* ctx, const void* src_dev, int src_dtype, int n, int ny, int nx, const double* shifts, int order,
                                double floor, void* dst_dev, int dst_dtype, double* stats_out) {
     if (!ctx || !src_dev || !shifts || !dst_dev) return fail(RL_ERR_INVALID, "NULL argument");
-    if (!float_dtype_ok(src_dtype) || !float_dtype_ok(dst_dtype)) return fail(RL_ERR_INVALID, "dtypes must be RL_F32 or RL_F64");
+    if (!dtype_ok(src_dtype) || !dtype_ok(dst_dtype)) return fail(RL_ERR_INVALID, "dtypes must be RL_F32 or RL_F64");
     if (n < 1 || ny < 1 || nx < 1) return fail(RL_ERR_INVALID, "n, ny and nx must be at least 1");
     if (order != 1 && order != 3) return fail(RL_ERR_INVALID, "order must be 1 or 3");
     if (std::isnan(floor)) return fail(RL_ERR_INVALID, "floor is nan");
     for (size_t i = 0; i < 2 * (size_t)n; ++i)
         if (!(std::fabs(shifts[i]) <= 1e9)) return fail(RL_ERR_INVALID, "image " + std::to_string(i / 2) + ": the shift must be finite, at most 1e9 pixels");
     const size_t n_pix = (size_t)ny * nx;
-    if (overlaps(src_dev, (size_t)n * n_pix * float_size(src_dtype), dst_dev, (size_t)n * n_pix * float_size(dst_dtype)))
+    if (overlaps(src_dev, (size_t)n * n_pix * dtype_size(src_dtype), dst_dev, (size_t)n * n_pix * dtype_size(dst_dtype)))
         return fail(RL_ERR_INVALID, "the destination overlaps the source");
     HIP_TRY(hipSetDevice(ctx->device));
     std::vector<ShiftImage> table((size_t)n);
@@ -139,20 +116,20 @@ extern "C" int rl_shift_images(rl_ctx* ctx, const void* src_dev, int src_dtype, 
         shift_taps(shifts[2 * (size_t)i + 1], order, nx, table[i].gx, &table[i].ox, &table[i].ntx);
     }
     const int nb = shift_blocks_y(ny) * shift_blocks_x(nx);
-    const size_t chunk = std::min<size_t>((size_t)n, std::max<size_t>(1, kShiftWorkBytes / (n_pix * sizeof(double))));
-    const size_t table_bytes = round_up((size_t)n * sizeof(ShiftImage), 256), stats_bytes = round_up((size_t)n * kShiftFields * sizeof(double), 256);
-    const size_t part_bytes = round_up(chunk * nb * kShiftFields * sizeof(double), 256);
+    const size_t chunk = chunk_under(kShiftWorkBytes, n_pix * sizeof(double), (size_t)n);
+    WorkLayout lay;
+    const auto r_table = lay.add<ShiftImage>((size_t)n);
+    const auto r_stats = lay.add<double>((size_t)n * kShiftFields), r_part = lay.add<double>(chunk * nb * kShiftFields);
+    const auto r_tmp = lay.add<double>(chunk * n_pix);
     char* w = nullptr;
-    RL_TRY(reg_workspace(ctx, table_bytes + stats_bytes + part_bytes + chunk * n_pix * sizeof(double), &w));
-    ShiftImage* table_dev = (ShiftImage*)w;
-    double* stats = (double*)(w + table_bytes);
-    double* part = (double*)(w + table_bytes + stats_bytes);
-    double* tmp = (double*)(w + table_bytes + stats_bytes + part_bytes);
+    RL_TRY(ctx->reg.reserve(ctx->stream, lay.bytes(), &w));
+    ShiftImage* table_dev = r_table.at(w);
+    double *stats = r_stats.at(w), *part = r_part.at(w), *tmp = r_tmp.at(w);
     HIP_TRY(hipMemcpyAsync(table_dev, table.data(), (size_t)n * sizeof(ShiftImage), hipMemcpyHostToDevice, ctx->stream));
     for (size_t first = 0; first < (size_t)n; first += chunk) {
         ShiftArgs a;
-        a.src = (const char*)src_dev + first * n_pix * float_size(src_dtype);
-        a.dst = (char*)dst_dev + first * n_pix * float_size(dst_dtype);
+        a.src = (const char*)src_dev + first * n_pix * dtype_size(src_dtype);
+        a.dst = (char*)dst_dev + first * n_pix * dtype_size(dst_dtype);
         a.img = table_dev + first;
         a.part = stats_out ? part : nullptr;
         a.n = (int)std::min(chunk, (size_t)n - first);
@@ -172,15 +149,16 @@ extern "C" int rl_register_peaks(rl_ctx* ctx, const double* tot_dev, int n_pairs
     static_assert(kPeakFields == RL_PEAK_FIELDS, "the header's field count");
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t nd = (size_t)(2 * R + 1) * (2 * R + 1);
-    const size_t peaks_b = round_up((size_t)n_pairs * kPeakFields * sizeof(double), 256);
-    const size_t surf_b = surface_out ? (size_t)n_pairs * nd * sizeof(double) : 0;
+    WorkLayout lay;
+    const auto r_peaks = lay.add<double>((size_t)n_pairs * kPeakFields);
+    const auto r_surf = lay.add<double>(surface_out ? (size_t)n_pairs * nd : 0);
     char* w = nullptr;
-    RL_TRY(reg_workspace(ctx, peaks_b + surf_b, &w));
+    RL_TRY(ctx->reg.reserve(ctx->stream, lay.bytes(), &w));
     RegPeakArgs a;
-    a.tot = tot_dev; a.peaks = (double*)w; a.surf = surface_out ? (double*)(w + peaks_b) : nullptr; a.pairs = n_pairs; a.R = R; a.n = n_terms;
+    a.tot = tot_dev; a.peaks = r_peaks.at(w); a.surf = r_surf.at(w); a.pairs = n_pairs; a.R = R; a.n = n_terms;
     HIP_TRY(register_peaks(a, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(peaks_out, a.peaks, (size_t)n_pairs * kPeakFields * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (surface_out) HIP_TRY(hipMemcpyAsync(surface_out, a.surf, surf_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(peaks_out, a.peaks, r_peaks.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+    if (surface_out) HIP_TRY(hipMemcpyAsync(surface_out, a.surf, r_surf.bytes(), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return RL_OK;
 }
@@ -189,40 +167,32 @@ extern "C" int rl_register_estimate(rl_ctx* ctx, const void* ref_dev, int ref_dt
                                     int mov_dtype, const int64_t* mov_offsets, int n_pairs, int ny, int nx, int R, int M, int refine,
                                     double* scratch_dev, double* shifts_out, double* fields_out, double* surface_out) {
     if (!ctx || !ref_dev || !ref_offsets || !mov_dev || !mov_offsets || !shifts_out || !fields_out) return fail(RL_ERR_INVALID, "NULL argument");
-    if (!float_dtype_ok(ref_dtype) || !float_dtype_ok(mov_dtype)) return fail(RL_ERR_INVALID, "dtypes must be RL_F32 or RL_F64");
+    if (!dtype_ok(ref_dtype) || !dtype_ok(mov_dtype)) return fail(RL_ERR_INVALID, "dtypes must be RL_F32 or RL_F64");
     if (n_pairs < 1) return fail(RL_ERR_INVALID, "n_pairs must be at least 1");
     if (R < 1 || R > kRegMaxR) return fail(RL_ERR_INVALID, "the search radius must lie in 1 .. 32");
     if (M < R) return fail(RL_ERR_INVALID, "the margin must be at least the search radius");
-    if (ny < 1 || nx < 1 || (long long)ny - 2LL * M < 8 || (long long)nx - 2LL * M < 8)
-        return fail(RL_ERR_INVALID, "the interior must be at least 8 x 8 pixels: ny - 2 M >= 8 and nx - 2 M >= 8");
+    RL_TRY(check_interior(ny, nx, M));
     if (refine < 0) return fail(RL_ERR_INVALID, "refine must be at least 0");
     if (refine > 0 && !scratch_dev) return fail(RL_ERR_INVALID, "refine > 0 needs a scratch buffer");
-    for (int i = 0; i < n_pairs; ++i)
-        if (ref_offsets[i] < 0 || mov_offsets[i] < 0) return fail(RL_ERR_INVALID, "pair " + std::to_string(i) + ": negative offset");
+    RL_TRY(check_pair_offsets(ref_offsets, mov_offsets, n_pairs));
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t n = (size_t)n_pairs, n_pix = (size_t)ny * nx;
     const RegGeom g = reg_geom(ny, nx, R, M), g1 = reg_geom(ny, nx, 1, M);
     const size_t chunk = sum_chunk(g, n), chunk1 = sum_chunk(g1, n);
     const size_t per_tot = (size_t)g.nd * kRegFields + 2, per_tot1 = (size_t)g1.nd * kRegFields + 2;
-    const size_t schunk = std::min<size_t>(n, std::max<size_t>(1, kShiftWorkBytes / (n_pix * sizeof(double))));
-    const size_t off_b = round_up(n * sizeof(long long), 256), peaks_b = round_up(n * kPeakFields * sizeof(double), 256);
-    const size_t surf_b = surface_out ? round_up(n * g.nd * sizeof(double), 256) : 0;
-    const size_t tot_b = round_up(std::max(chunk * per_tot, chunk1 * per_tot1) * sizeof(double), 256);
-    const size_t part_b = round_up(std::max(chunk * reg_part_doubles(g), chunk1 * reg_part_doubles(g1)) * sizeof(double), 256);
-    const size_t table_b = refine ? round_up(n * sizeof(ShiftImage), 256) : 0, tmp_b = refine ? schunk * n_pix * sizeof(double) : 0;
+    const size_t schunk = chunk_under(kShiftWorkBytes, n_pix * sizeof(double), n);
+    WorkLayout lay;
+    const auto r_a = lay.add<long long>(n), r_b = lay.add<long long>(n), r_la = lay.add<long long>(n), r_lb = lay.add<long long>(n);
+    const auto r_peaks = lay.add<double>(n * kPeakFields), r_surf = lay.add<double>(surface_out ? n * g.nd : 0);
+    const auto r_tot = lay.add<double>(std::max(chunk * per_tot, chunk1 * per_tot1));   // (both stages' sums go through tot and part)
+    const auto r_part = lay.add<double>(std::max(chunk * reg_part_doubles(g), chunk1 * reg_part_doubles(g1)));
+    const auto r_table = lay.add<ShiftImage>(refine ? n : 0);
+    const auto r_tmp = lay.add<double>(refine ? schunk * n_pix : 0);
     char* w = nullptr;
-    RL_TRY(reg_workspace(ctx, 4 * off_b + peaks_b + surf_b + tot_b + part_b + table_b + tmp_b, &w));
-    long long* a_off = (long long*)w;
-    long long* b_off = (long long*)(w + off_b);
-    long long* la_off = (long long*)(w + 2 * off_b);
-    long long* lb_off = (long long*)(w + 3 * off_b);
-    char* q = w + 4 * off_b;
-    double* peaks = (double*)q; q += peaks_b;
-    double* surf = surface_out ? (double*)q : nullptr; q += surf_b;
-    double* tot = (double*)q; q += tot_b;
-    double* part = (double*)q; q += part_b;
-    ShiftImage* table_dev = (ShiftImage*)q; q += table_b;
-    double* tmp = (double*)q;
+    RL_TRY(ctx->reg.reserve(ctx->stream, lay.bytes(), &w));
+    long long *a_off = r_a.at(w), *b_off = r_b.at(w), *la_off = r_la.at(w), *lb_off = r_lb.at(w);
+    double *peaks = r_peaks.at(w), *surf = r_surf.at(w), *tot = r_tot.at(w), *part = r_part.at(w), *tmp = r_tmp.at(w);
+    ShiftImage* table_dev = r_table.at(w);
     static_assert(sizeof(long long) == sizeof(int64_t), "offsets are copied as they are");
     HIP_TRY(hipMemcpyAsync(a_off, ref_offsets, n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(b_off, mov_offsets, n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
@@ -248,7 +218,7 @@ extern "C" int rl_register_estimate(rl_ctx* ctx, const void* ref_dev, int ref_dt
         HIP_TRY(hipMemcpyAsync(la_off, la.data(), live.size() * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipMemcpyAsync(lb_off, lb.data(), live.size() * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
     }
-    const size_t mov_size = float_size(mov_dtype);
+    const size_t mov_size = dtype_size(mov_dtype);
     for (int pass = 0; pass < refine && !live.empty(); ++pass) {
         const size_t L = live.size();
         for (size_t k = 0; k < L; ++k) {
@@ -282,41 +252,41 @@ extern "C" int rl_register_xcorr(rl_ctx* ctx, const void* ref_dev, int ref_dtype
                                  int mov_dtype, const int64_t* mov_offsets, int n_pairs, int ny, int nx, int R, double* peaks_out,
                                  float* surface_out) {
     if (!ctx || !ref_dev || !ref_offsets || !mov_dev || !mov_offsets || !peaks_out) return fail(RL_ERR_INVALID, "NULL argument");
-    if (!float_dtype_ok(ref_dtype) || !float_dtype_ok(mov_dtype)) return fail(RL_ERR_INVALID, "dtypes must be RL_F32 or RL_F64");
+    if (!dtype_ok(ref_dtype) || !dtype_ok(mov_dtype)) return fail(RL_ERR_INVALID, "dtypes must be RL_F32 or RL_F64");
     if (n_pairs < 1) return fail(RL_ERR_INVALID, "n_pairs must be at least 1");
     if (ny < 1 || nx < 1) return fail(RL_ERR_INVALID, "ny and nx must be at least 1");
     if (R < 1 || R > std::min(ny, nx) / 2) return fail(RL_ERR_INVALID, "the search radius must lie in 1 .. min(ny, nx) / 2");
     const int Ly = select_xcorr((long long)ny + R), Lx = select_xcorr((long long)nx + R);
     if (!Ly || !Lx)
         return fail(RL_ERR_INVALID, "ny + R and nx + R must not exceed the largest transform length of the coarse stage (" + std::to_string(kXcMaxL) + ")");
-    for (int i = 0; i < n_pairs; ++i)
-        if (ref_offsets[i] < 0 || mov_offsets[i] < 0) return fail(RL_ERR_INVALID, "pair " + std::to_string(i) + ": negative offset");
+    RL_TRY(check_pair_offsets(ref_offsets, mov_offsets, n_pairs));
     static_assert(kXcFields == RL_XCORR_FIELDS, "the header's field count");
     HIP_TRY(hipSetDevice(ctx->device));
     void *tw_y = nullptr, *tw_x = nullptr;
     RL_TRY(ctx->twiddles(xcorr_table(Ly), RL_F32, &tw_y));
     RL_TRY(ctx->twiddles(xcorr_table(Lx), RL_F32, &tw_x));
     const size_t W = 2 * (size_t)R + 1;
-    const size_t spec_b = round_up((size_t)ny * Lx * sizeof(cx<float>), 256), rows_b = round_up(W * Lx * sizeof(cx<float>), 256);
-    const size_t corr_b = round_up(W * W * sizeof(float), 256), surf_b = surface_out ? corr_b : 0;
-    const size_t per = spec_b + rows_b + corr_b + surf_b;
-    const size_t chunk = std::min<size_t>((size_t)n_pairs, std::max<size_t>(1, kXcorrWorkBytes / per));
-    const size_t off_bytes = round_up((size_t)n_pairs * sizeof(long long), 256);
-    const size_t stats_b = round_up(chunk * 4 * sizeof(double), 256), peaks_b = round_up(chunk * kXcFields * sizeof(double), 256);
+    // what one pair takes of the workspace: its spectrum, kept rows, correlation window and, when asked for, surface
+    const size_t spec_n = (size_t)ny * Lx, rows_n = W * Lx, corr_n = W * W, surf_n = surface_out ? corr_n : 0;
+    WorkLayout one;
+    one.add<cx<float>>(spec_n);
+    one.add<cx<float>>(rows_n);
+    one.add<float>(corr_n);
+    one.add<float>(surf_n);
+    const size_t chunk = chunk_under(kXcorrWorkBytes, one.bytes(), (size_t)n_pairs);
+    WorkLayout lay;
+    const auto r_a = lay.add<long long>((size_t)n_pairs), r_b = lay.add<long long>((size_t)n_pairs);
+    const auto r_stats = lay.add<double>(chunk * 4), r_peaks = lay.add<double>(chunk * kXcFields);
+    const auto r_spec = lay.add<cx<float>>(spec_n, chunk), r_rows = lay.add<cx<float>>(rows_n, chunk);   // (a padded slot per pair)
+    const auto r_corr = lay.add<float>(corr_n, chunk), r_surf = lay.add<float>(surf_n, chunk);
     char* w = nullptr;
-    RL_TRY(reg_workspace(ctx, 2 * off_bytes + stats_b + peaks_b + chunk * per, &w));
-    long long* a_off = (long long*)w;
-    long long* b_off = (long long*)(w + off_bytes);
+    RL_TRY(ctx->reg.reserve(ctx->stream, lay.bytes(), &w));
+    long long *a_off = r_a.at(w), *b_off = r_b.at(w);
     XcArgs a;
     a.a = ref_dev; a.b = mov_dev; a.a_f64 = ref_dtype == RL_F64; a.b_f64 = mov_dtype == RL_F64;
     a.ny = ny; a.nx = nx; a.R = R; a.Ly = Ly; a.Lx = Lx;
-    char* q = w + 2 * off_bytes;
-    a.stats = (double*)q; q += stats_b;
-    a.peaks = (double*)q; q += peaks_b;
-    a.spec = (cx<float>*)q; q += chunk * spec_b;
-    a.rows = (cx<float>*)q; q += chunk * rows_b;
-    a.corr = (float*)q; q += chunk * corr_b;
-    a.surf = surface_out ? (float*)q : nullptr;
+    a.stats = r_stats.at(w); a.peaks = r_peaks.at(w);
+    a.spec = r_spec.at(w); a.rows = r_rows.at(w); a.corr = r_corr.at(w); a.surf = r_surf.at(w);
     a.tw_y = (const cx<float>*)tw_y; a.tw_x = (const cx<float>*)tw_x;
     HIP_TRY(hipMemcpyAsync(a_off, ref_offsets, (size_t)n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(b_off, mov_offsets, (size_t)n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
@@ -347,7 +317,7 @@ extern "C" int rl_warp_path(rl_ctx* ctx, int path) {
 extern "C" int rl_warp_images(rl_ctx* ctx, const void* src_dev, int src_dtype, int n, int sy, int sx, const double* xf, int order,
                               double floor, void* dst_dev, int dst_dtype, int oy, int ox, double* stats_out) {
     if (!ctx || !src_dev || !xf || !dst_dev) return fail(RL_ERR_INVALID, "NULL argument");
-    if (!float_dtype_ok(src_dtype) || !float_dtype_ok(dst_dtype)) return fail(RL_ERR_INVALID, "dtypes must be RL_F32 or RL_F64");
+    if (!dtype_ok(src_dtype) || !dtype_ok(dst_dtype)) return fail(RL_ERR_INVALID, "dtypes must be RL_F32 or RL_F64");
     if (n < 1 || sy < 1 || sx < 1 || oy < 1 || ox < 1) return fail(RL_ERR_INVALID, "n, sy, sx, oy and ox must be at least 1");
     if (order != 1 && order != 3) return fail(RL_ERR_INVALID, "order must be 1 or 3");
     if (std::isnan(floor)) return fail(RL_ERR_INVALID, "floor is nan");
@@ -363,25 +333,22 @@ extern "C" int rl_warp_images(rl_ctx* ctx, const void* src_dev, int src_dtype, i
         }
     }
     const size_t s_pix = (size_t)sy * sx, o_pix = (size_t)oy * ox;
-    if (overlaps(src_dev, (size_t)n * s_pix * float_size(src_dtype), dst_dev, (size_t)n * o_pix * float_size(dst_dtype)))
+    if (overlaps(src_dev, (size_t)n * s_pix * dtype_size(src_dtype), dst_dev, (size_t)n * o_pix * dtype_size(dst_dtype)))
         return fail(RL_ERR_INVALID, "the destination overlaps the source");
     static_assert(kWarpFields == RL_SHIFT_FIELDS, "the header's field count");
     HIP_TRY(hipSetDevice(ctx->device));
     const int nb = warp_blocks_y(oy) * warp_blocks_x(ox);
     const size_t per = (order == 3 ? 2 * s_pix * sizeof(double) + sizeof(ShiftImage) : 0) + (size_t)nb * kWarpFields * sizeof(double);
-    const size_t chunk = std::min<size_t>((size_t)n, std::max<size_t>(1, ctx->warp_cap / per));
-    const size_t xf_bytes = round_up((size_t)n * kWarpXf * sizeof(double), 256), stats_bytes = round_up((size_t)n * kWarpFields * sizeof(double), 256);
-    const size_t part_bytes = round_up(chunk * nb * kWarpFields * sizeof(double), 256);
-    const size_t table_bytes = order == 3 ? round_up(chunk * sizeof(ShiftImage), 256) : 0;
-    const size_t img_bytes = order == 3 ? round_up(chunk * s_pix * sizeof(double), 256) : 0;
+    const size_t chunk = chunk_under(ctx->warp_cap, per, (size_t)n);
+    WorkLayout lay;
+    const auto r_xf = lay.add<double>((size_t)n * kWarpXf), r_stats = lay.add<double>((size_t)n * kWarpFields);
+    const auto r_part = lay.add<double>(chunk * nb * kWarpFields);
+    const auto r_table = lay.add<ShiftImage>(order == 3 ? chunk : 0);   // (the prefilter's regions: order 3 alone)
+    const auto r_tmp = lay.add<double>(order == 3 ? chunk * s_pix : 0), r_coef = lay.add<double>(order == 3 ? chunk * s_pix : 0);
     char* w = nullptr;
-    RL_TRY(reg_workspace(ctx, xf_bytes + stats_bytes + part_bytes + table_bytes + 2 * img_bytes, &w));
-    double* xf_dev = (double*)w;
-    double* stats = (double*)(w + xf_bytes);
-    double* part = (double*)(w + xf_bytes + stats_bytes);
-    ShiftImage* table_dev = (ShiftImage*)(w + xf_bytes + stats_bytes + part_bytes);
-    double* tmp = (double*)(w + xf_bytes + stats_bytes + part_bytes + table_bytes);
-    double* coef = (double*)(w + xf_bytes + stats_bytes + part_bytes + table_bytes + img_bytes);
+    RL_TRY(ctx->reg.reserve(ctx->stream, lay.bytes(), &w));
+    double *xf_dev = r_xf.at(w), *stats = r_stats.at(w), *part = r_part.at(w), *tmp = r_tmp.at(w), *coef = r_coef.at(w);
+    ShiftImage* table_dev = r_table.at(w);
     HIP_TRY(hipMemcpyAsync(xf_dev, xf, (size_t)n * kWarpXf * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     std::vector<ShiftImage> table;
     if (order == 3) {           // the same taps for every image of a chunk
@@ -393,7 +360,7 @@ extern "C" int rl_warp_images(rl_ctx* ctx, const void* src_dev, int src_dtype, i
     }
     for (size_t first = 0; first < (size_t)n; first += chunk) {
         const size_t m = std::min(chunk, (size_t)n - first);
-        const char* src = (const char*)src_dev + first * s_pix * float_size(src_dtype);
+        const char* src = (const char*)src_dev + first * s_pix * dtype_size(src_dtype);
         if (order == 3) {       // the prefilter alone: along x into tmp, along y into coef
             ShiftArgs f;
             f.src = src; f.dst = coef; f.img = table_dev; f.part = nullptr; f.n = (int)m; f.ny = sy; f.nx = sx; f.floor = -HUGE_VAL;
@@ -401,7 +368,7 @@ extern "C" int rl_warp_images(rl_ctx* ctx, const void* src_dev, int src_dtype, i
         }
         WarpArgs a;
         a.src = order == 3 ? (const void*)coef : (const void*)src;
-        a.dst = (char*)dst_dev + first * o_pix * float_size(dst_dtype);
+        a.dst = (char*)dst_dev + first * o_pix * dtype_size(dst_dtype);
         a.xf = xf_dev + first * kWarpXf;
         a.part = stats_out ? part : nullptr;
         a.n = (int)m; a.sy = sy; a.sx = sx; a.oy = oy; a.ox = ox; a.order = order; a.direct = ctx->warp_direct; a.floor = floor;
@@ -415,27 +382,24 @@ extern "C" int rl_warp_images(rl_ctx* ctx, const void* src_dev, int src_dtype, i
 extern "C" int rl_affine_sums(rl_ctx* ctx, const void* ref_dev, int ref_dtype, const int64_t* ref_offsets, const void* w_dev, int w_dtype,
                               const int64_t* w_offsets, int n_pairs, int ny, int nx, int M, double* sums_out) {
     if (!ctx || !ref_dev || !ref_offsets || !w_dev || !w_offsets || !sums_out) return fail(RL_ERR_INVALID, "NULL argument");
-    if (!float_dtype_ok(ref_dtype) || !float_dtype_ok(w_dtype)) return fail(RL_ERR_INVALID, "dtypes must be RL_F32 or RL_F64");
+    if (!dtype_ok(ref_dtype) || !dtype_ok(w_dtype)) return fail(RL_ERR_INVALID, "dtypes must be RL_F32 or RL_F64");
     if (n_pairs < 1) return fail(RL_ERR_INVALID, "n_pairs must be at least 1");
     if (M < 1) return fail(RL_ERR_INVALID, "the margin must be at least 1");
-    if (ny < 1 || nx < 1 || (long long)ny - 2LL * M < 8 || (long long)nx - 2LL * M < 8)
-        return fail(RL_ERR_INVALID, "the interior must be at least 8 x 8 pixels: ny - 2 M >= 8 and nx - 2 M >= 8");
+    RL_TRY(check_interior(ny, nx, M));
     if ((long long)ny * nx > 0x7fffffffLL) return fail(RL_ERR_INVALID, "an image must have fewer than 2^31 pixels");
-    for (int i = 0; i < n_pairs; ++i)
-        if (ref_offsets[i] < 0 || w_offsets[i] < 0) return fail(RL_ERR_INVALID, "pair " + std::to_string(i) + ": negative offset");
+    RL_TRY(check_pair_offsets(ref_offsets, w_offsets, n_pairs));
     static_assert(kAffFields == RL_AFFINE_FIELDS, "the header's field count");
     HIP_TRY(hipSetDevice(ctx->device));
     const AffGeom g = aff_geom(ny, nx, M);
     const size_t per_part = (size_t)g.nb * kAffFields;
-    const size_t chunk = std::min<size_t>((size_t)n_pairs, std::max<size_t>(1, kRegSumWorkBytes / (per_part * sizeof(double))));
-    const size_t off_bytes = round_up((size_t)n_pairs * sizeof(long long), 256);
-    const size_t tot_bytes = round_up(chunk * kAffFields * sizeof(double), 256);
+    const size_t chunk = chunk_under(kRegSumWorkBytes, per_part * sizeof(double), (size_t)n_pairs);
+    WorkLayout lay;
+    const auto r_a = lay.add<long long>((size_t)n_pairs), r_b = lay.add<long long>((size_t)n_pairs);
+    const auto r_tot = lay.add<double>(chunk * kAffFields), r_part = lay.add<double>(chunk * per_part);
     char* w = nullptr;
-    RL_TRY(reg_workspace(ctx, 2 * off_bytes + tot_bytes + chunk * per_part * sizeof(double), &w));
-    long long* a_off = (long long*)w;
-    long long* b_off = (long long*)(w + off_bytes);
-    double* tot = (double*)(w + 2 * off_bytes);
-    double* part = (double*)(w + 2 * off_bytes + tot_bytes);
+    RL_TRY(ctx->reg.reserve(ctx->stream, lay.bytes(), &w));
+    long long *a_off = r_a.at(w), *b_off = r_b.at(w);
+    double *tot = r_tot.at(w), *part = r_part.at(w);
     HIP_TRY(hipMemcpyAsync(a_off, ref_offsets, (size_t)n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(b_off, w_offsets, (size_t)n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     for (size_t first = 0; first < (size_t)n_pairs; first += chunk) {

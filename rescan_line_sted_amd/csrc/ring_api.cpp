@@ -16,8 +16,6 @@ constexpr size_t kRingWorkBytes = (size_t)256 << 20;
 constexpr int kRingMaxPairsPerLaunch = 65535;   // grid.z
 constexpr int kRingMaxRings = 4 * kRingMaxN;
 
-size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 int upload_table(const std::vector<int>& row_ptr, const std::vector<int>& bins, rl_ctx::RingTable* t) {
     HIP_TRY(hipMalloc((void**)&t->row_ptr, row_ptr.size() * sizeof(int)));
     hipError_t e = hipMalloc((void**)&t->bins, std::max<size_t>(bins.size(), 1) * sizeof(int));
@@ -64,18 +62,6 @@ int sector_table(rl_ctx* ctx, int ny, int nx, int n_rings, int n_sectors, rl_ctx
     return RL_OK;
 }
 
-int ring_workspace(rl_ctx* ctx, size_t bytes, char** out) {
-    if (bytes > ctx->ring.work_bytes) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->ring.work) (void)hipFree(ctx->ring.work);
-        ctx->ring.work = nullptr;
-        ctx->ring.work_bytes = 0;
-        HIP_TRY(hipMalloc(&ctx->ring.work, bytes));
-        ctx->ring.work_bytes = bytes;
-    }
-    *out = (char*)ctx->ring.work;
-    return RL_OK;
-}
 // both entry points: n_sectors = 0 is rl_ring_stats (the ring table, k_ring_reduce), n_sectors >= 1 rl_ring_sector_stats (the
 // sector table, k_ring_reduce_sectors, n_sectors times the result); everything else is one path
 int ring_run(rl_ctx* ctx, const void* a_dev, int a_dtype, const int64_t* a_offsets, const void* b_dev, int b_dtype,
@@ -84,8 +70,7 @@ int ring_run(rl_ctx* ctx, const void* a_dev, int a_dtype, const int64_t* a_offse
     if (n_pairs < 1) return fail(RL_ERR_INVALID, "n_pairs < 1");
     if (ny < 2 || nx < 2) return fail(RL_ERR_INVALID, "ny and nx must be at least 2");
     if (n_rings < 1) return fail(RL_ERR_INVALID, "n_rings < 1");
-    if ((a_dtype != RL_F32 && a_dtype != RL_F64) || (b_dtype != RL_F32 && b_dtype != RL_F64))
-        return fail(RL_ERR_INVALID, "dtype must be RL_F32 or RL_F64");
+    if (!dtype_ok(a_dtype) || !dtype_ok(b_dtype)) return fail(RL_ERR_INVALID, "dtype must be RL_F32 or RL_F64");
     if (ny > kRingMaxN || nx > kRingMaxN) return fail(RL_ERR_UNSUPPORTED, "ring statistics cover images up to 4096 x 4096");
     if (n_rings > kRingMaxRings) return fail(RL_ERR_UNSUPPORTED, "more than 16384 rings");
     if (n_sectors > kRingMaxSectors) return fail(RL_ERR_UNSUPPORTED, "more than 64 sectors");
@@ -102,18 +87,18 @@ int ring_run(rl_ctx* ctx, const void* a_dev, int a_dtype, const int64_t* a_offse
 
     const size_t img = (size_t)ny * nx * sizeof(RingC);
     const size_t per_out = (size_t)n_rings * (n_sectors ? n_sectors : 1) * kRingFields * sizeof(double);
-    int chunk = (int)std::min<size_t>({(size_t)n_pairs, (size_t)kRingMaxPairsPerLaunch, std::max<size_t>(1, kRingWorkBytes / (2 * img))});
-    if (n_sectors) chunk = (int)std::min<size_t>((size_t)chunk, std::max<size_t>(1, kRingWorkBytes / per_out));   // the results of a chunk stay under the cap too
-    const size_t meta = round_up((size_t)n_pairs * 8, 256);
-    const size_t res = round_up((size_t)chunk * per_out, 256);
+    int chunk = (int)std::min<size_t>(chunk_under(kRingWorkBytes, 2 * img, (size_t)n_pairs), (size_t)kRingMaxPairsPerLaunch);
+    if (n_sectors) chunk = (int)chunk_under(kRingWorkBytes, per_out, (size_t)chunk);   // the results of a chunk stay under the cap too
+    WorkLayout lay;
+    const auto r_aoff = lay.add<int64_t>((size_t)n_pairs), r_boff = lay.add<int64_t>((size_t)n_pairs);
+    const auto r_scale = lay.add<double>((size_t)n_pairs);
+    const auto r_out = lay.add<double>((size_t)chunk * per_out / sizeof(double));
+    const auto r_tf = lay.add<char>(2 * (size_t)chunk * img);   // T, then F behind it without padding
     char* base = nullptr;
-    RL_TRY(ring_workspace(ctx, 3 * meta + res + 2 * (size_t)chunk * img, &base));
-    int64_t* d_aoff = (int64_t*)base;
-    int64_t* d_boff = (int64_t*)(base + meta);
-    double* d_scale = (double*)(base + 2 * meta);
-    double* d_out = (double*)(base + 3 * meta);
-    char* d_t = base + 3 * meta + res;
-    char* d_f = d_t + (size_t)chunk * img;
+    RL_TRY(ctx->ring.work.reserve(ctx->stream, lay.bytes(), &base));
+    int64_t *d_aoff = r_aoff.at(base), *d_boff = r_boff.at(base);
+    double *d_scale = r_scale.at(base), *d_out = r_out.at(base);
+    char *d_t = r_tf.at(base), *d_f = d_t + (size_t)chunk * img;
 
     std::vector<double> ones;
     if (!b_scale) {

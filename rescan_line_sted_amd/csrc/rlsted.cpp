@@ -66,8 +66,6 @@ const KernelTable* table_for(int L) {
 }
 const int kLengths[] = {64, 192, 256, 576, 1152, 2304, 4608};
 
-size_t esize(int dtype) { return dtype == RL_F32 ? 4 : 8; }
-
 // Device temporaries of the plan set-up: freed when the scope ends, whichever way it ends (hipFree waits for the device).
 struct TempBuffers {
     std::vector<void*> bufs;
@@ -155,7 +153,7 @@ struct rl_deconv {
     }
     // host float64 values -> a device array of the plan's dtype (the stencils' taps)
     int upload_taps(void** p, const std::vector<double>& v) {
-        RL_TRY(alloc(p, v.size() * esize(dtype), UNCOUNTED));
+        RL_TRY(alloc(p, v.size() * dtype_size(dtype), UNCOUNTED));
         return rl::upload_as(dtype, v, *p);
     }
     // H_t views summed before the inverse transforms (one clamp of the sum instead of one per
@@ -236,9 +234,9 @@ struct rl_deconv {
     void *acc_x = nullptr, *acc_y = nullptr, *acc_g = nullptr;
     double *acc_part = nullptr, *acc_alpha = nullptr;
     long acc_steps = 0;
-    int acc_blocks() const { return accel_blocks(n_img(), esize(dtype)); }
+    int acc_blocks() const { return accel_blocks(n_img(), dtype_size(dtype)); }
     int ensure_accel() {
-        const size_t img = (size_t)B * n_img() * esize(dtype), part = (size_t)B * acc_blocks() * 2 * sizeof(double);
+        const size_t img = (size_t)B * n_img() * dtype_size(dtype), part = (size_t)B * acc_blocks() * 2 * sizeof(double);
         for (void** p : {&acc_x, &acc_y, &acc_g})
             if (!*p) RL_TRY(alloc(p, img));
         if (!acc_part) RL_TRY(alloc(&acc_part, part));
@@ -278,12 +276,12 @@ struct rl_deconv {
     StopFrame* stop_state = nullptr;                   // [2][B]
     size_t n_frame() const { return (size_t)V * n_img(); }   // values of one frame's measurement: all its views
     int ensure_divergence() {
-        if (!stop_part) RL_TRY(alloc(&stop_part, (size_t)B * stop_blocks(n_frame(), esize(dtype)) * sizeof(double)));
+        if (!stop_part) RL_TRY(alloc(&stop_part, (size_t)B * stop_blocks(n_frame(), dtype_size(dtype)) * sizeof(double)));
         if (!stop_d) RL_TRY(alloc(&stop_d, (size_t)B * sizeof(double)));
         return RL_OK;
     }
     int ensure_latch() {
-        if (!stop_result) RL_TRY(alloc(&stop_result, (size_t)B * n_img() * esize(dtype)));
+        if (!stop_result) RL_TRY(alloc(&stop_result, (size_t)B * n_img() * dtype_size(dtype)));
         if (!stop_state) RL_TRY(alloc(&stop_state, 2 * (size_t)B * sizeof(StopFrame)));
         return RL_OK;
     }
@@ -325,7 +323,7 @@ struct rl_deconv {
     bool tv_sum_valid = false;
     bool tv_on() const { return tv_lambda > 0.0; }
     int ensure_tv() {
-        if (!tv_w) RL_TRY(alloc(&tv_w, (size_t)B * n_img() * esize(dtype)));
+        if (!tv_w) RL_TRY(alloc(&tv_w, (size_t)B * n_img() * dtype_size(dtype)));
         if (!tv_part) RL_TRY(alloc(&tv_part, (size_t)B * acc_blocks() * sizeof(double)));
         return RL_OK;
     }
@@ -422,7 +420,7 @@ struct rl_deconv {
     // multiple.  Worth 2-4 % on the long rows, costs 3 % at lx = 576 (4608-byte rows: left alone).
     int pair_pitch = 0;
     size_t n_spec_pair() const { return spec_image_elems(ny, pair_pitch); }
-    void* pair_spec(int f0) const { return (char*)spec_a + (size_t)(f0 / 2) * n_spec_pair() * 2 * esize(dtype); }
+    void* pair_spec(int f0) const { return (char*)spec_a + (size_t)(f0 / 2) * n_spec_pair() * 2 * dtype_size(dtype); }
     // ---- column / row launches.  Layout of the spectra: HALF -- per frame, [ny][pitch] with kx columns -- or PAIR -- two frames in
     // one complex image, [ny][pair_pitch] with lx columns.
     enum Layout { HALF, PAIR };
@@ -469,7 +467,7 @@ struct rl_deconv {
         return launch_col(p, kind);
     }
     int col_pair(const void* in, void* out, int pairs, ColKind kind, const Iter* it = nullptr) {
-        const size_t sp = n_spec_pair() * 2 * esize(dtype);
+        const size_t sp = n_spec_pair() * 2 * dtype_size(dtype);
         const size_t in_per = kind == COL_H ? 1 : (size_t)V, out_per = kind == COL_H ? (size_t)V : 1;
         for (int p0 = 0; p0 < pairs; p0 += kMaxGridY) {
             const int np = std::min((int)kMaxGridY, pairs - p0);
@@ -517,7 +515,7 @@ struct rl_deconv {
     // views > 1 (ROW_RATIO of a multi-view plan): one launch image per (pair, view); spectra [pair][view], images [frame][view]
     int row_pair(int mode, int frames, const void* spec_in, void* spec_out, const void* src, void* dst, const void* nrm, int in_mod = 0,
                  int views = 1, const Iter* it = nullptr) {
-        const size_t sp = n_spec_pair() * 2 * esize(dtype), im = n_img() * esize(dtype);
+        const size_t sp = n_spec_pair() * 2 * dtype_size(dtype), im = n_img() * dtype_size(dtype);
         const int step = 2 * ((int)kMaxGridY / views);
         for (int f0 = 0; f0 < frames; f0 += step) {
             const int nf = std::min(step, frames - f0);
@@ -543,7 +541,7 @@ struct rl_deconv {
         const bool multi = mode == SEP_SUM_ || mode == SEP_UPDATE_;
         for (int f0 = 0; f0 < frames; f0 += 65535) {
             const int n = std::min(65535, frames - f0);
-            const size_t img = n_img() * esize(dtype), in_off = (size_t)f0 * (multi ? V : 1) * img, out_off = (size_t)f0 * (multi ? 1 : V) * img;
+            const size_t img = n_img() * dtype_size(dtype), in_off = (size_t)f0 * (multi ? V : 1) * img, out_off = (size_t)f0 * (multi ? 1 : V) * img;
             HIP_TRY(sep2d(dtype, opt.sep_th, mode, (const char*)in + in_off, sep_uf, sep_vf, aux ? (const char*)aux + out_off : nullptr, nrm,
                           (char*)dst + out_off, n, ny, nx, py, px, V, cur()));
         }
@@ -553,8 +551,8 @@ struct rl_deconv {
     int sep_rows_(const void* in, void* out, int images, int in_div) {
         for (int i0 = 0; i0 < images; i0 += 65535 / V * V) {   // grid.z pieces of whole frames
             const int n = std::min(65535 / V * V, images - i0);
-            HIP_TRY(sep_rows(dtype, (const char*)in + (size_t)(i0 / in_div) * n_img() * esize(dtype),
-                             (char*)out + (size_t)i0 * n_img() * esize(dtype), sep_v, n, ny, nx, px, V, in_div, cur()));
+            HIP_TRY(sep_rows(dtype, (const char*)in + (size_t)(i0 / in_div) * n_img() * dtype_size(dtype),
+                             (char*)out + (size_t)i0 * n_img() * dtype_size(dtype), sep_v, n, ny, nx, px, V, in_div, cur()));
         }
         return RL_OK;
     }
@@ -564,7 +562,7 @@ struct rl_deconv {
         const int step = multi ? 65535 : 65535 / V * V;
         for (int i0 = 0; i0 < count; i0 += step) {
             const int n = std::min(step, count - i0);
-            const size_t in_off = (size_t)i0 * (multi ? V : 1) * n_img() * esize(dtype), out_off = (size_t)i0 * n_img() * esize(dtype);
+            const size_t in_off = (size_t)i0 * (multi ? V : 1) * n_img() * dtype_size(dtype), out_off = (size_t)i0 * n_img() * dtype_size(dtype);
             HIP_TRY(sep_cols(dtype, mode, (const char*)tmp + in_off, sep_u, aux ? (const char*)aux + out_off : nullptr, nrm,
                              (char*)dst + out_off, n, ny, nx, py, V, cur()));
         }
@@ -697,7 +695,7 @@ struct rl_deconv {
     // are launched in pieces (whole frames each) with the pointers moved on
     static constexpr int kMaxGridY = 65535;
     int col(const void* in, void* out, int frames, ColKind kind, const Iter* it = nullptr) {
-        const size_t sp = n_spec() * 2 * esize(dtype);   // bytes of one spectrum image
+        const size_t sp = n_spec() * 2 * dtype_size(dtype);   // bytes of one spectrum image
         const size_t in_per = kind == COL_H ? 1 : (size_t)V, out_per = kind == COL_HT_FUSED ? 1 : (size_t)V;
         const int step = std::max(1, kMaxGridY / V);
         for (int f0 = 0; f0 < frames; f0 += step) {
@@ -711,7 +709,7 @@ struct rl_deconv {
     int row(int mode, unsigned gy, const void* spec_in, void* spec_out, const void* src, void* dst, const void* nrm,
             const void* scale = nullptr, int views = -1, int in_mod = 0, const Iter* it = nullptr) {
         if (views < 0) views = V;
-        const size_t sp = n_spec() * 2 * esize(dtype), im = n_img() * esize(dtype);
+        const size_t sp = n_spec() * 2 * dtype_size(dtype), im = n_img() * dtype_size(dtype);
         const bool multi = mode == ROW_UPDATE || mode == ROW_ADJ;   // `views` input spectra per image
         const unsigned piece = in_mod > 0 ? (unsigned)(kMaxGridY / in_mod * in_mod) : (unsigned)kMaxGridY;
         for (unsigned g0 = 0; g0 < gy; g0 += piece) {
@@ -722,7 +720,7 @@ struct rl_deconv {
             void* so = spec_out ? (char*)spec_out + (size_t)g0 * sp : nullptr;
             const void* sr = src ? (const char*)src + (size_t)g0 * im : nullptr;
             void* ds = dst ? (char*)dst + (size_t)g0 * im : nullptr;
-            const void* sc = scale ? (const char*)scale + (size_t)g0 * esize(dtype) : nullptr;
+            const void* sc = scale ? (const char*)scale + (size_t)g0 * dtype_size(dtype) : nullptr;
             RL_TRY(dtype == RL_F32 ? row_t<float>(HALF, mode, (int)ng, si, so, sr, ds, nrm, sc, views, in_mod, it)
                                    : row_t<double>(HALF, mode, (int)ng, si, so, sr, ds, nrm, sc, views, in_mod, it));
         }
@@ -757,7 +755,7 @@ struct rl_deconv {
         for (size_t f0 = 0; f0 < count; f0 += per) {
             const size_t nf = f0 + per <= count ? per : count - f0;
             HIP_TRY(hipMemcpyAsync(stage_dev, src + f0 * n, nf * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(aux_scale_convert(dtype, stage_dev, (char*)dst + f0 * n * esize(dtype), n, nf,
+            HIP_TRY(aux_scale_convert(dtype, stage_dev, (char*)dst + f0 * n * dtype_size(dtype), n, nf,
                                       target ? stage_aux + f0 : nullptr, stage_sums + f0, ctx->stream, target != nullptr || sums_out != nullptr));
             if (sums_out) HIP_TRY(hipMemcpyAsync(sums_out->data() + f0, stage_sums + f0, nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(hipStreamSynchronize(ctx->stream));   // the staging buffer is reused by the next slice
@@ -777,17 +775,17 @@ struct rl_deconv {
         RL_TRY(ensure_stage());
         for (size_t o = 0; o < n; o += kStageElems) {
             const size_t m = o + kStageElems <= n ? kStageElems : n - o;
-            HIP_TRY(aux_to_f64(dtype, (const char*)src + o * esize(dtype), stage_dev, m, ctx->stream));
+            HIP_TRY(aux_to_f64(dtype, (const char*)src + o * dtype_size(dtype), stage_dev, m, ctx->stream));
             HIP_TRY(hipMemcpyAsync(dst + o, stage_dev, m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(hipStreamSynchronize(ctx->stream));
         }
         return RL_OK;
     }
 
-    char* off(void* base, size_t elems) const { return (char*)base + elems * esize(dtype); }
+    char* off(void* base, size_t elems) const { return (char*)base + elems * dtype_size(dtype); }
     // frames of a slice of the batch (cycle_schedule.hpp: the rules and what they measured)
     int chunk_frames() const {
-        return rl::chunk_frames({B, V, n_img(), n_spec(), esize(dtype), one_buffer(), accel != RL_ACCEL_NONE, tv_on(), pair, opt.chunk_mb_set,
+        return rl::chunk_frames({B, V, n_img(), n_spec(), dtype_size(dtype), one_buffer(), accel != RL_ACCEL_NONE, tv_on(), pair, opt.chunk_mb_set,
                                  opt.chunk_mb, opt.lanes, ty->C[dtype], kx});
     }
     // rowFFT(est) of frames [f0, f0 + nf) in the layout of the loop at hand (a stencil plan keeps no spectrum)
@@ -927,13 +925,13 @@ struct rl_deconv {
             RL_TRY(release(&cls_spec_a));
             RL_TRY(release(&cls_spec_b));
             RL_TRY(release(&cls_spec_x));
-            const size_t cap = (total + 7) / 8 * 8, sp = n_spec() * 2 * esize(dtype);
-            RL_TRY(alloc(&obj_c, cap * n_img() * esize(dtype), SLACK));
-            RL_TRY(alloc(&noiseless_c, cap * V * n_img() * esize(dtype), SLACK));
+            const size_t cap = (total + 7) / 8 * 8, sp = n_spec() * 2 * dtype_size(dtype);
+            RL_TRY(alloc(&obj_c, cap * n_img() * dtype_size(dtype), SLACK));
+            RL_TRY(alloc(&noiseless_c, cap * V * n_img() * dtype_size(dtype), SLACK));
             if (!pair_layout) RL_TRY(alloc(&cls_spec_a, cap * sp, SLACK));   // (a pair plan simulates in place unless its frames' levels forbid pairs: forward_classes)
             RL_TRY(alloc(&cls_spec_b, cap * V * sp, SLACK));
             if (col_split()) {
-                const size_t parked_bytes = cap * V * n_spec_x() * 2 * esize(dtype);
+                const size_t parked_bytes = cap * V * n_spec_x() * 2 * dtype_size(dtype);
                 RL_TRY(alloc(&cls_spec_x, parked_bytes));
                 HIP_TRY(hipMemsetAsync(cls_spec_x, 0, parked_bytes, ctx->stream));
             }
@@ -958,7 +956,7 @@ struct rl_deconv {
     int forward_classes(int n) {
         void* sb = cls_spec_b;
         if (!pair && !cls_spec_a) {   // a pair plan whose frames at hand run the per-frame loop (choose_loop): first use
-            RL_TRY(alloc(&cls_spec_a, share_cap * n_spec() * 2 * esize(dtype), SLACK));
+            RL_TRY(alloc(&cls_spec_a, share_cap * n_spec() * 2 * dtype_size(dtype), SLACK));
             HIP_TRY(hipStreamSynchronize(ctx->stream));   // (the zeroed slack, before another stream's kernels read past the end)
         }
         void* sa = !pair ? cls_spec_a : sb;   // (as forward_frames does)
@@ -1007,7 +1005,7 @@ struct rl_deconv {
     double* cp_part = nullptr;
     int ensure_checkpoint_part() {
         if (cp_part) return RL_OK;
-        return alloc(&cp_part, (size_t)B * checkpoint_blocks(n_img(), esize(dtype)) * kCheckpointFields * sizeof(double));
+        return alloc(&cp_part, (size_t)B * checkpoint_blocks(n_img(), dtype_size(dtype)) * kCheckpointFields * sizeof(double));
     }
     int take_checkpoint(const Checkpoints& cp, int j, int f0, int nf) {
         const int frames = std::min(f0 + nf, cp.nt) - f0;
@@ -1015,8 +1013,8 @@ struct rl_deconv {
         double* tr = cp.trace ? cp.trace[j] : nullptr;
         if (frames <= 0 || (!dst && !tr)) return RL_OK;
         const size_t o = (size_t)f0 * n_img();
-        double* part = tr ? cp_part + (size_t)f0 * checkpoint_blocks(n_img(), esize(dtype)) * kCheckpointFields : nullptr;
-        HIP_TRY(checkpoint_take(dtype, off(est, o), off(obj, o), cp.out_dtype, dst ? (char*)dst + o * esize(cp.out_dtype) : nullptr, part,
+        double* part = tr ? cp_part + (size_t)f0 * checkpoint_blocks(n_img(), dtype_size(dtype)) * kCheckpointFields : nullptr;
+        HIP_TRY(checkpoint_take(dtype, off(est, o), off(obj, o), cp.out_dtype, dst ? (char*)dst + o * dtype_size(cp.out_dtype) : nullptr, part,
                                 n_img(), frames, cur()));
         if (tr) HIP_TRY(checkpoint_totals(dtype, part, n_img(), frames, tr + (size_t)f0 * kCheckpointFields, cur()));
         return RL_OK;
@@ -1234,7 +1232,6 @@ int rl_ctx_destroy(rl_ctx* c) {
     if (!c) return RL_OK;
     (void)hipSetDevice(c->device);
     for (auto& kv : c->tw) (void)hipFree(kv.second);
-    if (c->psf_work) (void)hipFree(c->psf_work);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return RL_OK;
@@ -1286,7 +1283,7 @@ static int build_psf_hat(rl_deconv* h, const double* psfs, void* hat, int width,
     const size_t nz = V * (size_t)width * h->ly;
     double* stats = nullptr;
     double hs[2] = {1.0, 1.0};
-    RL_TRY(h->alloc(re, nz * esize(h->dtype), rl_deconv::SLACK));
+    RL_TRY(h->alloc(re, nz * dtype_size(h->dtype), rl_deconv::SLACK));
     RL_TRY(tmp.get((void**)&stats, sizeof(hs)));
     HIP_TRY(aux_split_real(h->dtype, hat, nz, *re, stats, ctx->stream));
     HIP_TRY(hipMemcpyAsync(hs, stats, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
@@ -1312,7 +1309,7 @@ static int deconv_build(rl_deconv* h, const double* psfs) {
     RL_TRY(ctx->prepare(h->tx));
     RL_TRY(ctx->twiddles(h->ty, h->dtype, &h->twy, true));
     RL_TRY(ctx->twiddles(h->tx, h->dtype, &h->twx));
-    const size_t es = esize(h->dtype), B = (size_t)h->B, V = (size_t)h->V;
+    const size_t es = dtype_size(h->dtype), B = (size_t)h->B, V = (size_t)h->V;
     // (measured, pitch lx against lx + 32: 512^2 18.7 k against 18.1 k frames/s, 2048^2 690 against 716, 4096^2 K = 100 28.0 against 28.6)
     h->pair_pitch = h->lx + (h->lx >= 1152 ? 32 : 0);
     struct Req { void** p; size_t n; };
@@ -1473,7 +1470,7 @@ int rl_deconv_create_with(rl_ctx* ctx, const double* psfs, int n_psf, int py, in
     if (!ctx || !psfs || !out) return fail(RL_ERR_INVALID, "NULL argument");
     *out = nullptr;
     if (n_psf < 1 || py < 1 || px < 1 || batch < 1 || ny < 1 || nx < 1) return fail(RL_ERR_INVALID, "non-positive size");
-    if (dtype != RL_F32 && dtype != RL_F64) return fail(RL_ERR_INVALID, "dtype must be RL_F32 or RL_F64");
+    if (!dtype_ok(dtype)) return fail(RL_ERR_INVALID, "dtype must be RL_F32 or RL_F64");
     if (n_psf > rl_deconv::kMaxGridY) return fail(RL_ERR_UNSUPPORTED, "more than 65535 views");
     OptionLookup lookup;
     std::string bad;
@@ -1736,7 +1733,7 @@ int rl_deconv_iterate_until(rl_deconv* h, int k_max, int check_every, int rule, 
         if (all) break;
     }
     // the latched estimates become the plan's estimate, as a set estimate does: a point without history
-    HIP_TRY(hipMemcpyAsync(h->est, h->stop_result, (size_t)h->B * h->n_img() * esize(h->dtype), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->est, h->stop_result, (size_t)h->B * h->n_img() * dtype_size(h->dtype), hipMemcpyDeviceToDevice, s));
     RL_TRY(h->set_estimate());
     for (int f = 0; f < h->B; ++f) {
         if (iterations_out) iterations_out[f] = state[f].iterations;
@@ -1902,7 +1899,7 @@ static int batch_submit(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_i
     if (!h || (!tasks && n_tasks > 0)) return fail(RL_ERR_INVALID, "NULL argument");
     if (n_tasks < 0 || k_iters < 0) return fail(RL_ERR_INVALID, "negative count");
     if (rng_kind != RL_RNG_NONE && rng_kind != RL_RNG_PHILOX) return fail(RL_ERR_INVALID, "unknown rng_kind");
-    if (dev_out && out_dtype != RL_F32 && out_dtype != RL_F64) return fail(RL_ERR_INVALID, "out_dtype must be RL_F32 or RL_F64");
+    if (dev_out && !dtype_ok(out_dtype)) return fail(RL_ERR_INVALID, "out_dtype must be RL_F32 or RL_F64");
     for (int t = 0; t < n_tasks; ++t) {
         if (!tasks[t].object) return fail(RL_ERR_INVALID, "task without an object");
         if ((uint64_t)tasks[t].image_id * (uint64_t)h->V + (uint64_t)h->V > 0xffffffffull) return fail(RL_ERR_INVALID, "image id too large");
@@ -1989,7 +1986,7 @@ static int batch_submit(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_i
             if (ck->out) {
                 ck_out.assign(ck->out, ck->out + ck->n_k);
                 for (void*& p : ck_out)
-                    if (p) p = (char*)p + (size_t)t0 * n * esize(out_dtype);
+                    if (p) p = (char*)p + (size_t)t0 * n * dtype_size(out_dtype);
                 cp.out = ck_out.data();
             }
             if (ck->trace) {
@@ -2005,7 +2002,7 @@ static int batch_submit(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_i
         RL_TRY(rc);
         h->have_meas = true;
         if (dev_out && !ck)
-            HIP_TRY(aux_cast(h->dtype, h->est, out_dtype, (char*)dev_out + (size_t)t0 * n * esize(out_dtype), (size_t)nt * n, s));
+            HIP_TRY(aux_cast(h->dtype, h->est, out_dtype, (char*)dev_out + (size_t)t0 * n * dtype_size(out_dtype), (size_t)nt * n, s));
     }
     return RL_OK;
 }
@@ -2029,7 +2026,7 @@ int rl_batch_run(rl_deconv* h, const rl_task* tasks, int n_tasks, int k_iters, i
     if (!h || (!tasks && n_tasks > 0)) return fail(RL_ERR_INVALID, "NULL argument");
     if (n_tasks < 0 || k_iters < 0) return fail(RL_ERR_INVALID, "negative count");
     HIP_TRY(hipSetDevice(h->ctx->device));
-    const size_t need = (size_t)n_tasks * h->n_img() * esize(h->dtype);
+    const size_t need = (size_t)n_tasks * h->n_img() * dtype_size(h->dtype);
     if (estimates_out && need > h->batch_out_bytes) {
         HIP_TRY(hipStreamSynchronize(h->ctx->stream));
         h->batch_out_bytes = 0;
@@ -2062,7 +2059,7 @@ int rl_device_free(rl_ctx* ctx, void* dev) {
 
 int rl_device_upload(rl_ctx* ctx, void* dev, int dtype, size_t n_elements, const double* host) {
     if (!ctx || (n_elements && (!dev || !host))) return fail(RL_ERR_INVALID, "NULL argument");
-    if (dtype != RL_F32 && dtype != RL_F64) return fail(RL_ERR_INVALID, "dtype must be RL_F32 or RL_F64");
+    if (!dtype_ok(dtype)) return fail(RL_ERR_INVALID, "dtype must be RL_F32 or RL_F64");
     HIP_TRY(hipSetDevice(ctx->device));
     if (dtype == RL_F64) {
         HIP_TRY(hipMemcpyAsync(dev, host, n_elements * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -2083,7 +2080,7 @@ int rl_device_upload(rl_ctx* ctx, void* dev, int dtype, size_t n_elements, const
 
 int rl_device_download(rl_ctx* ctx, const void* dev, int dtype, size_t n_elements, double* host_out) {
     if (!ctx || (n_elements && (!dev || !host_out))) return fail(RL_ERR_INVALID, "NULL argument");
-    if (dtype != RL_F32 && dtype != RL_F64) return fail(RL_ERR_INVALID, "dtype must be RL_F32 or RL_F64");
+    if (!dtype_ok(dtype)) return fail(RL_ERR_INVALID, "dtype must be RL_F32 or RL_F64");
     HIP_TRY(hipSetDevice(ctx->device));
     if (dtype == RL_F64) {
         HIP_TRY(hipMemcpyAsync(host_out, dev, n_elements * 8, hipMemcpyDeviceToHost, ctx->stream));

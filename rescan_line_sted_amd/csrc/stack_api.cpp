@@ -18,28 +18,17 @@
 using namespace rl;
 
 namespace {
-size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-int ingest_workspace(rl_ctx* ctx, size_t bytes, double** out) {
-    if (bytes > ctx->ingest.work_bytes) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->ingest.work) (void)hipFree(ctx->ingest.work);
-        ctx->ingest.work = nullptr;
-        ctx->ingest.work_bytes = 0;
-        HIP_TRY(hipMalloc(&ctx->ingest.work, bytes));
-        ctx->ingest.work_bytes = bytes;
-    }
-    *out = (double*)ctx->ingest.work;
-    return RL_OK;
-}
-
-bool float_dtype_ok(int d) { return d == RL_F32 || d == RL_F64; }
-size_t float_size(int d) { return d == RL_F32 ? sizeof(float) : sizeof(double); }
 size_t raw_size(int d) { return d == RL_RAW_U8 ? 1 : (d == RL_RAW_F32 ? 4 : (d == RL_RAW_U16 || d == RL_RAW_I16 ? 2 : 0)); }
 size_t out_size(int d) { return d == RL_OUT_F32 ? 4 : (d == RL_OUT_F64 ? 8 : (d == RL_OUT_U16 ? 2 : 0)); }
 
-bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    return (const char*)a < (const char*)b + b_bytes && (const char*)b < (const char*)a + a_bytes;
+// the per-workgroup partials of a call's statistics, `doubles` of them, in the context's ingest workspace
+int stats_partials(rl_ctx* ctx, size_t doubles, double** out) {
+    WorkLayout lay;
+    const auto r_part = lay.add<double>(doubles);
+    char* base = nullptr;
+    RL_TRY(ctx->ingest.reserve(ctx->stream, lay.bytes(), &base));
+    *out = r_part.at(base);
+    return RL_OK;
 }
 
 // the camera's numbers (rl_ingest's and rl_stack_create's)
@@ -81,7 +70,7 @@ extern "C" int rl_ingest(rl_ctx* ctx, const void* raw_dev, int raw_dtype, int sr
                          int dst_dtype, double* stats_dev) {
     if (!ctx || !raw_dev || !dst_dev) return fail(RL_ERR_INVALID, "NULL argument");
     if (!raw_size(raw_dtype)) return fail(RL_ERR_INVALID, "raw_dtype must be one of RL_RAW_*");
-    if (!float_dtype_ok(dst_dtype)) return fail(RL_ERR_INVALID, "dst_dtype must be RL_F32 or RL_F64");
+    if (!dtype_ok(dst_dtype)) return fail(RL_ERR_INVALID, "dst_dtype must be RL_F32 or RL_F64");
     if (src_images < 1 || src_ny < 1 || src_pitch < 1 || n_slots < 1 || V < 1 || ny < 1 || nx < 1)
         return fail(RL_ERR_INVALID, "src_images, src_ny, src_pitch, n_slots, V, ny and nx must be at least 1");
     if (n_valid < 0 || n_valid > n_slots) return fail(RL_ERR_INVALID, "n_valid must lie in 0 .. n_slots");
@@ -96,7 +85,7 @@ extern "C" int rl_ingest(rl_ctx* ctx, const void* raw_dev, int raw_dtype, int sr
             }
     }
     const size_t src_bytes = (size_t)src_images * src_ny * src_pitch * raw_size(raw_dtype);
-    const size_t images = (size_t)n_slots * V, dst_bytes = images * ny * nx * float_size(dst_dtype);
+    const size_t images = (size_t)n_slots * V, dst_bytes = images * ny * nx * dtype_size(dst_dtype);
     if (overlaps(raw_dev, src_bytes, dst_dev, dst_bytes)) return fail(RL_ERR_INVALID, "the destination overlaps the source");
     if (dark_dev && overlaps(dark_dev, (size_t)ny * nx * sizeof(float), dst_dev, dst_bytes))
         return fail(RL_ERR_INVALID, "the destination overlaps the dark map");
@@ -110,10 +99,7 @@ extern "C" int rl_ingest(rl_ctx* ctx, const void* raw_dev, int raw_dtype, int sr
     a.frame_stride = frame_stride; a.view_stride = view_stride;
     a.src_ny = src_ny; a.src_pitch = src_pitch; a.y0 = y0; a.x0 = x0; a.n_slots = n_slots; a.n_valid = n_valid; a.V = V; a.ny = ny; a.nx = nx;
     a.offset = offset; a.gain = gain; a.epsilon = epsilon; a.saturation = saturation;
-    if (stats_dev) {
-        const size_t part = images * ingest_blocks(ingest_vectors(ny, nx)) * kIngestFields * sizeof(double);
-        RL_TRY(ingest_workspace(ctx, round_up(part, 256), &a.part));
-    }
+    if (stats_dev) RL_TRY(stats_partials(ctx, images * ingest_blocks(ingest_vectors(ny, nx)) * kIngestFields, &a.part));
     HIP_TRY(ingest(raw_dtype, dst_dtype, a, ctx->stream));
     return RL_OK;
 }
@@ -121,22 +107,19 @@ extern "C" int rl_ingest(rl_ctx* ctx, const void* raw_dev, int raw_dtype, int sr
 extern "C" int rl_export(rl_ctx* ctx, const void* est_dev, int est_dtype, int n, int ny, int nx, double scale, void* out_dev,
                          int out_dtype, double* stats_dev) {
     if (!ctx || !est_dev || !out_dev) return fail(RL_ERR_INVALID, "NULL argument");
-    if (!float_dtype_ok(est_dtype)) return fail(RL_ERR_INVALID, "est_dtype must be RL_F32 or RL_F64");
+    if (!dtype_ok(est_dtype)) return fail(RL_ERR_INVALID, "est_dtype must be RL_F32 or RL_F64");
     if (!out_size(out_dtype)) return fail(RL_ERR_INVALID, "out_dtype must be one of RL_OUT_*");
     if (n < 1 || ny < 1 || nx < 1) return fail(RL_ERR_INVALID, "n, ny and nx must be at least 1");
     if (std::isnan(scale)) return fail(RL_ERR_INVALID, "scale is nan");
     static_assert(OUT_F32 == RL_OUT_F32 && OUT_F64 == RL_OUT_F64 && OUT_U16 == RL_OUT_U16, "the header's codes");
-    const size_t n_pix = (size_t)ny * nx, est_bytes = (size_t)n * n_pix * float_size(est_dtype), out_bytes = (size_t)n * n_pix * out_size(out_dtype);
+    const size_t n_pix = (size_t)ny * nx, est_bytes = (size_t)n * n_pix * dtype_size(est_dtype), out_bytes = (size_t)n * n_pix * out_size(out_dtype);
     if (overlaps(est_dev, est_bytes, out_dev, out_bytes)) return fail(RL_ERR_INVALID, "the output overlaps the estimates");
     if (stats_dev && overlaps(stats_dev, (size_t)n * kExportFields * sizeof(double), out_dev, out_bytes))
         return fail(RL_ERR_INVALID, "the output overlaps the statistics");
     HIP_TRY(hipSetDevice(ctx->device));
     ExportArgs a;
     a.est = est_dev; a.out = out_dev; a.part = nullptr; a.stats = stats_dev; a.n = n; a.n_pix = n_pix; a.scale = scale;
-    if (stats_dev) {
-        const size_t part = (size_t)n * ingest_blocks(export_vectors(n_pix)) * kExportFields * sizeof(double);
-        RL_TRY(ingest_workspace(ctx, round_up(part, 256), &a.part));
-    }
+    if (stats_dev) RL_TRY(stats_partials(ctx, (size_t)n * ingest_blocks(export_vectors(n_pix)) * kExportFields, &a.part));
     HIP_TRY(export_estimates(est_dtype, out_dtype, a, ctx->stream));
     return RL_OK;
 }
@@ -427,7 +410,7 @@ int stack_compute_registered(rl_stack* st, const Chunk& c, int k_iters, RegRun& 
     const rl_stack_params& p = st->prm;
     const bool by_view = p.order == RL_ORDER_VIEW_FRAME;
     const int V = st->V, B = st->B;
-    const size_t n_pix = (size_t)st->ny * st->nx, esz = st->dtype == RL_F32 ? sizeof(float) : sizeof(double);
+    const size_t n_pix = (size_t)st->ny * st->nx, esz = dtype_size(st->dtype);
     double* stats = (double*)(sl.dev_out + st->stats_offset());
     HIP_TRY(hipStreamWaitEvent(s, sl.uploaded, 0));
     if (sl.used) HIP_TRY(hipStreamWaitEvent(s, sl.downloaded, 0));
@@ -542,7 +525,7 @@ extern "C" int rl_stack_run_registered(rl_stack* st, const void* raw_host, int n
     }
     HIP_TRY(hipSetDevice(st->ctx->device));
     const auto t0 = std::chrono::steady_clock::now();
-    const size_t n_pix = (size_t)st->ny * st->nx, esz = st->dtype == RL_F32 ? sizeof(float) : sizeof(double);
+    const size_t n_pix = (size_t)st->ny * st->nx, esz = dtype_size(st->dtype);
     if (!st->staging) HIP_TRY(hipMalloc(&st->staging, (size_t)st->B * V * n_pix * esz));
     if (!st->refs) HIP_TRY(hipMalloc(&st->refs, (size_t)V * n_pix * esz));
     if (r.estimating && rp->refine > 0 && !st->scratch) HIP_TRY(hipMalloc((void**)&st->scratch, (size_t)st->B * V * n_pix * sizeof(double)));

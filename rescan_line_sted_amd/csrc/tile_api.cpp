@@ -12,28 +12,6 @@
 using namespace rl;
 
 namespace {
-size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-int tile_workspace(rl_ctx* ctx, size_t bytes, char** out) {
-    if (bytes > ctx->tile.work_bytes) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->tile.work) (void)hipFree(ctx->tile.work);
-        ctx->tile.work = nullptr;
-        ctx->tile.work_bytes = 0;
-        HIP_TRY(hipMalloc(&ctx->tile.work, bytes));
-        ctx->tile.work_bytes = bytes;
-    }
-    *out = (char*)ctx->tile.work;
-    return RL_OK;
-}
-
-bool dtype_ok(int d) { return d == RL_F32 || d == RL_F64; }
-size_t esize_of(int d) { return d == RL_F32 ? sizeof(float) : sizeof(double); }
-
-bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    return (const char*)a < (const char*)b + b_bytes && (const char*)b < (const char*)a + a_bytes;
-}
-
 // the origins of one axis of a blend: inside the image, non-decreasing, every pixel covered -> the coverage tables
 int blend_axis(const char* name, int n, int t, int count, const int* origins, int32_t* first, int32_t* cover) {
     for (int i = 0; i < count; ++i) {
@@ -80,15 +58,16 @@ extern "C" int rl_tile_gather(rl_ctx* ctx, const void* src_dev, int src_dtype, i
         if (f < 0 || f >= F) return fail(RL_ERR_INVALID, "slot " + std::to_string(k) + ": frame out of range");
         if (ay < 0 || ay > NY - ty || ax < 0 || ax > NX - tx) return fail(RL_ERR_INVALID, "slot " + std::to_string(k) + ": the tile overhangs the image");
     }
-    const size_t src_bytes = (size_t)F * V * NY * NX * esize_of(src_dtype), dst_bytes = (size_t)n_slots * V * ty * tx * esize_of(dst_dtype);
+    const size_t src_bytes = (size_t)F * V * NY * NX * dtype_size(src_dtype), dst_bytes = (size_t)n_slots * V * ty * tx * dtype_size(dst_dtype);
     if (overlaps(src_dev, src_bytes, dst_dev, dst_bytes)) return fail(RL_ERR_INVALID, "the destination overlaps the source");
     HIP_TRY(hipSetDevice(ctx->device));
+    WorkLayout lay;
+    const auto r_slots = lay.add<int32_t>((size_t)n_slots * 3);
     char* base = nullptr;
-    const size_t bytes = (size_t)n_slots * 3 * sizeof(int32_t);
-    RL_TRY(tile_workspace(ctx, round_up(bytes, 256), &base));
+    RL_TRY(ctx->tile.reserve(ctx->stream, lay.bytes(), &base));
     // (a pageable source: the copy has left it when it returns)
-    HIP_TRY(hipMemcpyAsync(base, slots, bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(tile_gather(src_dtype, dst_dtype, src_dev, dst_dev, (const int32_t*)base, n_slots, V, NY, NX, ty, tx, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(r_slots.at(base), slots, r_slots.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(tile_gather(src_dtype, dst_dtype, src_dev, dst_dev, r_slots.at(base), n_slots, V, NY, NX, ty, tx, ctx->stream));
     return RL_OK;
 }
 
@@ -100,30 +79,29 @@ extern "C" int rl_tile_blend(rl_ctx* ctx, const void* tiles_dev, int tiles_dtype
     if (F < 1 || NY < 1 || NX < 1) return fail(RL_ERR_INVALID, "F, NY and NX must be at least 1");
     if (ny_tiles < 1 || nx_tiles < 1) return fail(RL_ERR_INVALID, "ny_tiles and nx_tiles must be at least 1");
     if (ty < 1 || tx < 1 || ty > NY || tx > NX) return fail(RL_ERR_INVALID, "the tile must lie within the image");
-    const size_t b_oy = round_up((size_t)ny_tiles * 4, 256), b_ox = round_up((size_t)nx_tiles * 4, 256);
-    const size_t b_wy = round_up((size_t)ny_tiles * ty * 8, 256), b_wx = round_up((size_t)nx_tiles * tx * 8, 256);
-    const size_t b_gy = round_up((size_t)NY * 4, 256), b_gx = round_up((size_t)NX * 4, 256);
-    const size_t o_ox = b_oy, o_wy = o_ox + b_ox, o_wx = o_wy + b_wy, o_fy = o_wx + b_wx, o_cy = o_fy + b_gy, o_fx = o_cy + b_gy,
-                 o_cx = o_fx + b_gx, total = o_cx + b_gx;
+    WorkLayout lay;
+    const auto r_oy = lay.add<int32_t>((size_t)ny_tiles), r_ox = lay.add<int32_t>((size_t)nx_tiles);
+    const auto r_wy = lay.add<double>((size_t)ny_tiles * ty), r_wx = lay.add<double>((size_t)nx_tiles * tx);
+    const auto r_fy = lay.add<int32_t>((size_t)NY), r_cy = lay.add<int32_t>((size_t)NY);
+    const auto r_fx = lay.add<int32_t>((size_t)NX), r_cx = lay.add<int32_t>((size_t)NX);
     // the eight tables go up in ONE copy, staged in the device layout
-    std::vector<char> stage(total, 0);
-    RL_TRY(blend_axis("rows", NY, ty, ny_tiles, origins_y, (int32_t*)(stage.data() + o_fy), (int32_t*)(stage.data() + o_cy)));
-    RL_TRY(blend_axis("columns", NX, tx, nx_tiles, origins_x, (int32_t*)(stage.data() + o_fx), (int32_t*)(stage.data() + o_cx)));
-    std::copy(origins_y, origins_y + ny_tiles, (int32_t*)stage.data());
-    std::copy(origins_x, origins_x + nx_tiles, (int32_t*)(stage.data() + o_ox));
-    std::copy(wy, wy + (size_t)ny_tiles * ty, (double*)(stage.data() + o_wy));
-    std::copy(wx, wx + (size_t)nx_tiles * tx, (double*)(stage.data() + o_wx));
-    const size_t tiles_bytes = (size_t)F * ny_tiles * nx_tiles * ty * tx * esize_of(tiles_dtype);
-    const size_t out_bytes = (size_t)F * NY * NX * esize_of(out_dtype);
+    std::vector<char> stage(lay.bytes(), 0);
+    char* h = stage.data();
+    RL_TRY(blend_axis("rows", NY, ty, ny_tiles, origins_y, r_fy.at(h), r_cy.at(h)));
+    RL_TRY(blend_axis("columns", NX, tx, nx_tiles, origins_x, r_fx.at(h), r_cx.at(h)));
+    std::copy(origins_y, origins_y + ny_tiles, r_oy.at(h));
+    std::copy(origins_x, origins_x + nx_tiles, r_ox.at(h));
+    std::copy(wy, wy + (size_t)ny_tiles * ty, r_wy.at(h));
+    std::copy(wx, wx + (size_t)nx_tiles * tx, r_wx.at(h));
+    const size_t tiles_bytes = (size_t)F * ny_tiles * nx_tiles * ty * tx * dtype_size(tiles_dtype);
+    const size_t out_bytes = (size_t)F * NY * NX * dtype_size(out_dtype);
     if (overlaps(tiles_dev, tiles_bytes, out_dev, out_bytes)) return fail(RL_ERR_INVALID, "the output overlaps the tile store");
     HIP_TRY(hipSetDevice(ctx->device));
     char* base = nullptr;
-    RL_TRY(tile_workspace(ctx, total, &base));
-    HIP_TRY(hipMemcpyAsync(base, stage.data(), total, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(tile_blend(tiles_dtype, out_dtype, tiles_dev, out_dev, (const int32_t*)base, (const int32_t*)(base + o_ox),
-                       (const double*)(base + o_wy), (const double*)(base + o_wx), (const int32_t*)(base + o_fy),
-                       (const int32_t*)(base + o_cy), (const int32_t*)(base + o_fx), (const int32_t*)(base + o_cx), F, NY, NX, ny_tiles,
-                       nx_tiles, ty, tx, ctx->stream));
+    RL_TRY(ctx->tile.reserve(ctx->stream, lay.bytes(), &base));
+    HIP_TRY(hipMemcpyAsync(base, h, lay.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(tile_blend(tiles_dtype, out_dtype, tiles_dev, out_dev, r_oy.at(base), r_ox.at(base), r_wy.at(base), r_wx.at(base), r_fy.at(base),
+                       r_cy.at(base), r_fx.at(base), r_cx.at(base), F, NY, NX, ny_tiles, nx_tiles, ty, tx, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return RL_OK;
 }

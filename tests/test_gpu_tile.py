@@ -77,6 +77,33 @@ def test_gather_is_numpy_slicing(src_dtype, dst_dtype):
         assert np.all(got[0] == 1.0) and np.all(got[-1] == 1.0)
 
 
+def test_gather_grows_its_workspace_behind_a_queued_call():
+    """rl_tile_gather does not wait for its kernel.  A second call whose slot list outgrows the context's tile workspace (24 bytes,
+    then 2400) finds the first still queued: the workspace waits for the stream before it frees the block the first call reads, and
+    both destinations are numpy slicing bit for bit.  On a context of its own: the shared one's workspace has grown in other tests."""
+    L = _lib()
+    rng = np.random.default_rng(12)
+    src = rng.random((1, 1, 16, 16)) + 0.25
+    few = np.array([(0, 3, 5), (-1, 0, 0)], dtype=np.intc)
+    real = [(0, int(ay), int(ax)) for ay, ax in rng.integers(0, 9, (197, 2))]
+    many = np.array([(-1, 0, 0)] + real + [(-1, 3, 3), (-1, 0, 0)], dtype=np.intc)
+    assert (few.nbytes, many.nbytes) == (24, 2400)
+    d_src = _Dev(src, 'f64')
+    dsts = [_Dev(np.full(len(s) * 64, -7.0), 'f64', 1) for s in (few, many)]
+    ctx = L.Context(0)
+    try:
+        for s, d in zip((few, many), dsts):                             # at once: nothing waits between the two calls
+            L.check(L.lib.rl_tile_gather(ctx.handle, d_src.dev, d_src.code, 1, 1, 16, 16, _ints(s), len(s), 8, 8, d.dev, d.code))
+        ctx.synchronize()
+        for s, d in zip((few, many), dsts):
+            want = tr.gather(src, s, (8, 8), np.float64)
+            got = d.download().reshape(want.shape)
+            assert np.array_equal(got, want), len(s)
+        assert np.all(got[0] == 1.0) and np.all(got[-1] == 1.0)
+    finally:
+        L.check(L.lib.rl_ctx_destroy(ctx.handle))
+
+
 def test_gather_and_blend_reject_bad_geometry():
     L = _lib()
     d = _Dev(np.zeros(2 * 37 * 53), 'f32')
