@@ -61,6 +61,39 @@ int rl_ctx_create(int device, rl_ctx** out);
 int rl_ctx_destroy(rl_ctx* ctx);
 int rl_ctx_synchronize(rl_ctx* ctx);
 
+/* The host calls that cut their work into chunks keep the workspace of one chunk under a cap in bytes, held by the context.  The
+ * RESULTS DO NOT DEPEND ON THE CAP: every item's arithmetic is a function of the item alone, in a fixed order, and what a call
+ * carries from one chunk to the next (rl_fig3_scan's running sum) makes the same additions in the same order.  At least one item
+ * runs per chunk, whatever the cap.  which, and the default:
+ *   RL_CHUNK_REGISTER_SUMS  rl_register_sums, rl_affine_sums, the sums of rl_register_estimate: the partials of the pairs in
+ *                           flight; 256 MiB
+ *   RL_CHUNK_SHIFT          rl_shift_images, the refine passes' shifts of rl_register_estimate: the float64 intermediates of the
+ *                           images in flight; 512 MiB
+ *   RL_CHUNK_XCORR          rl_register_xcorr: the spectra, kept rows and windows of the pairs in flight; 32 MiB
+ *   RL_CHUNK_RING           rl_ring_stats, rl_ring_sector_stats: the two spectra of the pairs in flight, and the sector results of
+ *                           the pairs in flight; 256 MiB
+ *   RL_CHUNK_FIG3           rl_fig3_scan: one float64 image stack of the positions in flight (the call holds three); 512 MiB
+ *   RL_CHUNK_WARP           rl_warp_images (the cap of rl_warp_chunk_bytes); 512 MiB
+ *   RL_CHUNK_BEADS          rl_find_peaks (the cap of rl_find_peaks_chunk_bytes); 256 MiB
+ * rl_chunk_bytes sets the cap of `which` for the later calls on this context.  RL_ERR_INVALID, the cap unchanged: a NULL ctx, a
+ * `which` that is none of the above, 0 bytes.
+ * rl_chunks_run: the trips the chunk loop under that cap made in the most recent call on this context that has such a loop; 0
+ * before any such call, and for a NULL ctx or an unknown `which`.  A host counter: nothing on the device knows of it.
+ * rl_register_estimate counts its first sums stage under RL_CHUNK_REGISTER_SUMS and the shift launches of its last refine pass
+ * under RL_CHUNK_SHIFT (left as it was when no pass shifts anything). */
+enum {
+    RL_CHUNK_REGISTER_SUMS = 0,
+    RL_CHUNK_SHIFT = 1,
+    RL_CHUNK_XCORR = 2,
+    RL_CHUNK_RING = 3,
+    RL_CHUNK_FIG3 = 4,
+    RL_CHUNK_WARP = 5,
+    RL_CHUNK_BEADS = 6,
+    RL_CHUNK_COUNT = 7
+};
+int rl_chunk_bytes(rl_ctx* ctx, int which, size_t bytes);
+int rl_chunks_run(rl_ctx* ctx, int which);
+
 /* Smallest supported transform length >= n (0 if none). */
 int rl_fft_length_for(int n);
 
@@ -511,7 +544,7 @@ int rl_spline_sample(rl_ctx* ctx, const double* image, int ny, int nx, const dou
  * rl_deconv_device_ptr) of dtype a_dtype / b_dtype (RL_F32 / RL_F64, they may differ); image i of the pair starts at ELEMENT
  * offset a_offsets[i] / b_offsets[i] (host arrays [n_pairs]; any offset >= 0, no alignment assumed).  a_dev and b_dev may be the
  * same buffer, and many pairs may name the same image.  b_scale: host [n_pairs], or NULL for 1.
- * Pairs are processed in chunks whose working memory stays under a fixed cap; the ring table and the workspace are kept in the
+ * Pairs are processed in chunks whose working memory stays under a cap (rl_chunk_bytes); the ring table and the workspace are kept in the
  * context and freed with it.  Synchronises the context's stream.
  * RL_ERR_INVALID: a NULL pointer, n_pairs < 1, ny or nx < 2, n_rings < 1, a dtype that is neither, a negative offset;
  * RL_ERR_UNSUPPORTED: ny or nx > 4096 (the transform is the O(n^3) matrix form), n_rings > 16384.                        */
@@ -740,7 +773,7 @@ int rl_device_upload_bytes(rl_ctx* ctx, void* dev, const void* host, size_t byte
  * ...) over the strips in increasing order.  S_a and S_aa: per image row from 0.0 over the interior's columns in increasing order
  * (S_a + a; fma(a, a, S_aa)), then (((0.0 + row_M) + row_{M+1}) + ...), followed by + 0.0 for the rows that complete the last TY.
  * No floating-point atomics: bit-identical from run to run, and a pair's result does not depend on the other pairs of the call.
- * Nothing outside an image is read.  Pairs are processed in chunks whose partial sums stay under a fixed cap; the workspace is kept
+ * Nothing outside an image is read.  Pairs are processed in chunks whose partial sums stay under a cap (rl_chunk_bytes); the workspace is kept
  * in the context and freed with it.  Synchronises the context's stream.
  * RL_ERR_INVALID (no kernel is launched): a NULL argument, a dtype that is neither, n_pairs < 1, R outside 1 .. 32, M < R, an
  * interior smaller than 8 x 8, a negative offset.
@@ -756,7 +789,7 @@ int rl_device_upload_bytes(rl_ctx* ctx, void* dev, const void* host, size_t byte
  * are formed on the host in long double; a pixel is g_0 v_0, then fma(g_m, v_m, .) for m = 1, 2, ...; x first, then y.
  * stats_out: NULL, or host [n][RL_SHIFT_FIELDS] = the count of pixels raised to `floor`, the float64 sum of the stored image in
  * the fixed order of csrc/register_kernels.hpp (thread, binary tree over 256 threads, workgroups in increasing order; no atomics).
- * Writes exactly n * ny * nx values.  Images are processed in chunks whose float64 intermediate stays under a fixed cap, in the
+ * Writes exactly n * ny * nx values.  Images are processed in chunks whose float64 intermediate stays under a cap (rl_chunk_bytes), in the
  * context's workspace.  Synchronises the context's stream.
  * RL_ERR_INVALID (no kernel is launched): a NULL ctx / source / shifts / destination, a dtype that is neither, n, ny or nx < 1, an
  * order that is neither, floor nan, a shift that is not finite or beyond 1e9, a destination that overlaps the source. */
@@ -790,7 +823,7 @@ int rl_shift_images(rl_ctx* ctx, const void* src_dev, int src_dtype, int n, int 
  * in increasing order.  Results are bit-identical from run to run, a pair's result does not depend on the other pairs of the call,
  * and nothing outside an image is read.  Error of C against exact arithmetic: tests/xcorr_reference.py derives
  *     |C_dev - C| <= kappa eps_f32 (log2 Ly + log2 Lx) ||a||_2 ||b||_2.
- * Pairs are processed in chunks whose spectra stay under a fixed cap, in the context's workspace.  Synchronises the context's stream.
+ * Pairs are processed in chunks whose spectra stay under a cap (rl_chunk_bytes), in the context's workspace.  Synchronises the context's stream.
  * RL_ERR_INVALID (no kernel is launched): a NULL ctx / buffer / offsets / peaks_out, a dtype that is neither, n_pairs < 1, ny or
  * nx < 1, R < 1, R > min(ny, nx) / 2, ny + R or nx + R > 1152 (the lengths 2304 and 4608 have a column geometry of their own and
  * are not served), a negative offset. */
@@ -877,7 +910,7 @@ int rl_register_estimate(rl_ctx* ctx, const void* ref_dev, int ref_dtype, const 
  * ceil(n / 8192)) runs of ceil(n / nb); thread t of a run's 256 takes its pixels t, t + 256, ... in increasing order from 0.0; the
  * halving tree s[t] = s[t] + s[t + h], h = 128, ..., 1; (((0.0 + run_0) + run_1) + ...).  Bit-identical from run to run, a pair's
  * result does not depend on the other pairs of the call, and nothing outside an image is read.  Pairs are processed in chunks whose
- * partial sums stay under a fixed cap, in the context's workspace.  Synchronises the context's stream.
+ * partial sums stay under a cap (rl_chunk_bytes), in the context's workspace.  Synchronises the context's stream.
  * RL_ERR_INVALID (no kernel is launched): a NULL argument, a dtype that is neither, n_pairs < 1, M < 1, an interior smaller than
  * 8 x 8, 2^31 pixels or more, a negative offset. */
 #define RL_AFFINE_FIELDS 45

@@ -19,6 +19,10 @@ RL_ACCEL_NONE, RL_ACCEL_BIGGS_ANDREWS = 0, 1
 ACCELERATIONS = {None: RL_ACCEL_NONE, 'none': RL_ACCEL_NONE, 'biggs-andrews': RL_ACCEL_BIGGS_ANDREWS}
 RL_STOP_DISCREPANCY, RL_STOP_RELATIVE = 1, 2
 STOP_RULES = {'discrepancy': RL_STOP_DISCREPANCY, 'relative': RL_STOP_RELATIVE}
+# which of rl_chunk_bytes / rl_chunks_run (include/rlsted.h RL_CHUNK_*)
+CHUNK_CAPS = {'register_sums': 0, 'shift': 1, 'xcorr': 2, 'ring': 3, 'fig3': 4, 'warp': 5, 'beads': 6}
+CHUNK_DEFAULTS = {'register_sums': 256 << 20, 'shift': 512 << 20, 'xcorr': 32 << 20, 'ring': 256 << 20, 'fig3': 512 << 20,
+                  'warp': 512 << 20, 'beads': 256 << 20}          # the caps of a fresh context, in bytes (csrc/ctx.hpp)
 
 
 def accel_mode(acceleration):
@@ -53,6 +57,8 @@ PROTOTYPES = {
     'rl_ctx_create': (_i, [_i, _c.POINTER(_vp)]),
     'rl_ctx_destroy': (_i, [_vp]),
     'rl_ctx_synchronize': (_i, [_vp]),
+    'rl_chunk_bytes': (_i, [_vp, _i, _c.c_size_t]),
+    'rl_chunks_run': (_i, [_vp, _i]),
     'rl_fft_length_for': (_i, [_i]),
     'rl_deconv_create': (_i, [_vp, _dp, _i, _i, _i, _i, _i, _i, _i, _c.POINTER(_vp)]),
     'rl_deconv_create_with': (_i, [_vp, _dp, _i, _i, _i, _i, _i, _i, _i, _c.c_char_p, _c.POINTER(_vp)]),
@@ -247,6 +253,15 @@ class Context:
 
     def synchronize(self):
         check(lib.rl_ctx_synchronize(self.handle))
+
+    def chunk_bytes(self, which, nbytes):
+        """The workspace cap of one family of chunked calls (a key of CHUNK_CAPS) for the later calls on this context
+        (include/rlsted.h rl_chunk_bytes).  The results do not depend on it."""
+        check(lib.rl_chunk_bytes(self.handle, CHUNK_CAPS[which], int(nbytes)))
+
+    def chunks_run(self, which):
+        """The trips of the chunk loop under that cap in the most recent call that has one (rl_chunks_run)."""
+        return lib.rl_chunks_run(self.handle, CHUNK_CAPS[which])
 
 
 def common_psf_shape(psfs):

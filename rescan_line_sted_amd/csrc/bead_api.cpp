@@ -77,8 +77,10 @@ extern "C" int rl_find_peaks(rl_ctx* ctx, const void* src_dev, int src_dtype, co
     std::vector<double> lev(chunk * kBpLevels), sv(chunk * (size_t)cap), xv(chunk * (size_t)cap);
     std::vector<long long> cnt(chunk);
     std::vector<int> yx(chunk * (size_t)cap * 2);
+    int& trips = ctx->chunks_run[RL_CHUNK_BEADS] = 0;
     for (size_t first = 0; first < (size_t)n; first += chunk) {
         const size_t m = std::min(chunk, (size_t)n - first);
+        ++trips;
         a.off = off_dev + first;
         a.n = (int)m;
         HIP_TRY(find_peaks(a, ctx->stream));

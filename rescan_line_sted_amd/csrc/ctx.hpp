@@ -150,6 +150,31 @@ struct rl_ctx {
     size_t beads_cap = (size_t)256 << 20;
     // rl_repair_pixels (calib_api.cpp): a call's defect list
     rl::Workspace calib;
+    // the other chunked calls' caps (rl_chunk_bytes).  reg_sum_cap: the partials of the pairs in flight of rl_register_sums,
+    // rl_register_estimate and rl_affine_sums; shift_cap: the float64 intermediates of the images in flight of rl_shift_images and
+    // the refine passes; xcorr_cap: the spectra and kept rows of rl_register_xcorr's pairs in flight; ring_cap: T and F of the
+    // pairs in flight of the ring statistics, and their sector results; fig3_cap: one image stack of rl_fig3_scan's positions in
+    // flight.  A larger single item runs alone.
+    size_t reg_sum_cap = (size_t)256 << 20;
+    size_t shift_cap = (size_t)512 << 20;
+    size_t xcorr_cap = (size_t)32 << 20;
+    size_t ring_cap = (size_t)256 << 20;
+    size_t fig3_cap = ((size_t)64 << 20) * sizeof(double);
+    // the cap of RL_CHUNK_* `which`, or nullptr
+    size_t* chunk_cap(int which) {
+        switch (which) {
+            case RL_CHUNK_REGISTER_SUMS: return &reg_sum_cap;
+            case RL_CHUNK_SHIFT: return &shift_cap;
+            case RL_CHUNK_XCORR: return &xcorr_cap;
+            case RL_CHUNK_RING: return &ring_cap;
+            case RL_CHUNK_FIG3: return &fig3_cap;
+            case RL_CHUNK_WARP: return &warp_cap;
+            case RL_CHUNK_BEADS: return &beads_cap;
+        }
+        return nullptr;
+    }
+    // the trips of the chunk loop under each cap in the most recent call that has one (rl_chunks_run); host bookkeeping only
+    int chunks_run[RL_CHUNK_COUNT] = {};
 
     int device = 0;
     hipStream_t stream = nullptr;

@@ -294,6 +294,11 @@ int rl_fig3_scan(rl_ctx* ctx, const rl_fig3_params* p, const double* rot_obj, co
     if (p->imaging_type < 0 || p->imaging_type > 3) return fail(RL_ERR_INVALID, "imaging_type must be 0..3");
     if (p->ny < 2 || p->nx < 1 || n_pos < 1 || n_display < 0 || !(p->psf_sigma > 1e-15)) return fail(RL_ERR_INVALID, "bad shape / sigma");
     if (n_display > 0 && (!display || !display_out)) return fail(RL_ERR_INVALID, "display list without output");
+    // (checked here and not where a chunk meets them: a call that fails leaves no copy to the caller's arrays in flight)
+    for (int k = 0; k < n_display; ++k) {
+        if (display[k] < 0 || (k > 0 && display[k] <= display[k - 1])) return fail(RL_ERR_INVALID, "display indices must ascend");
+        if (display[k] >= n_pos) return fail(RL_ERR_INVALID, "display index beyond the last position");
+    }
     const int type = p->imaging_type, ny = p->ny, nx = p->nx;
     const bool rescan = type == 3, multipoint = type == 1, line = type == 2;
     if (rescan && !cum_final) return fail(RL_ERR_INVALID, "rescan_line needs cum_final");
@@ -306,8 +311,8 @@ int rl_fig3_scan(rl_ctx* ctx, const rl_fig3_params* p, const double* rot_obj, co
     const size_t n = (size_t)ny * nx;
     int radius = 0;
     const std::vector<double> hw = gaussian_weights(p->psf_sigma, 4.0, &radius);
-    // chunk of positions: three image stacks of at most ~1.5 GB together
-    int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_pos, ((size_t)64 << 20) / n));
+    // chunk of positions: three image stacks, each under the cap (by default ~1.5 GB together)
+    int chunk = (int)rl::chunk_under(ctx->fig3_cap, n * sizeof(double), (size_t)n_pos);
     double* work = nullptr;
     const size_t need = 3 * n + (size_t)chunk * (3 * n + 4 + n_val) + hw.size() + (size_t)chunk + 64;
     RL_TRY(ctx->psf_workspace(need, &work));
@@ -326,8 +331,10 @@ int rl_fig3_scan(rl_ctx* ctx, const rl_fig3_params* p, const double* rot_obj, co
     if (rescan && (out_ny < 1 || out_ny > ny)) return fail(RL_ERR_INVALID, "rescan_scale must shrink the image");
     std::vector<double> sc;
     int next_display = 0;
+    int& trips = ctx->chunks_run[RL_CHUNK_FIG3] = 0;
     for (int p0 = 0; p0 < n_pos; p0 += chunk) {
         const int np_ = std::min(chunk, n_pos - p0);
+        ++trips;
         const size_t total = (size_t)np_ * n;
         HIP_TRY(hipMemcpyAsync(d_pos, positions + 2 * (size_t)p0, (size_t)np_ * 2 * sizeof(int), hipMemcpyHostToDevice, s));
         k_glow<<<blocks(total), 256, 0, s>>>(d_obj, d_exc, d_pos, np_, ny, nx, multipoint ? 1 : 0, a);
@@ -355,13 +362,11 @@ int rl_fig3_scan(rl_ctx* ctx, const rl_fig3_params* p, const double* rot_obj, co
         if (n_val) HIP_TRY(hipMemcpyAsync(pos_values + (size_t)p0 * n_val, d_val, (size_t)np_ * n_val * 8, hipMemcpyDeviceToHost, s));
         for (; next_display < n_display && display[next_display] < p0 + np_; ++next_display) {
             const int d = display[next_display];
-            if (d < p0 || (next_display > 0 && d <= display[next_display - 1])) return fail(RL_ERR_INVALID, "display indices must ascend");
             HIP_TRY(hipMemcpyAsync(display_out + (size_t)next_display * 2 * n, inst + (size_t)(d - p0) * n, n * 8, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipMemcpyAsync(display_out + (size_t)next_display * 2 * n + n, cum + (size_t)(d - p0) * n, n * 8, hipMemcpyDeviceToHost, s));
         }
         HIP_TRY(hipStreamSynchronize(s));   // the chunk buffers are reused
     }
-    if (next_display != n_display) return fail(RL_ERR_INVALID, "display index beyond the last position");
     if (rescan) {
         HIP_TRY(hipMemcpyAsync(cum_final, d_cum, n * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));

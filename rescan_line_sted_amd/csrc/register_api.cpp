@@ -18,10 +18,6 @@
 using namespace rl;
 
 namespace {
-constexpr size_t kRegSumWorkBytes = (size_t)256 << 20;     // the partials of the pairs in flight; a larger single pair runs alone
-constexpr size_t kShiftWorkBytes = (size_t)512 << 20;      // the float64 intermediates of the images in flight
-constexpr size_t kXcorrWorkBytes = (size_t)32 << 20;       // the spectra and kept rows of the pairs in flight; a larger single pair runs alone
-
 const KernelTable* xcorr_table(int L) {
     switch (L) {
         case 64: return table_64();
@@ -34,10 +30,13 @@ const KernelTable* xcorr_table(int L) {
 }
 
 // the sums of n pairs (offsets: device arrays) in chunks of `chunk` through tot / part, each chunk followed by its peaks into
-// peaks [n][5] and, when surf is not null, surf [n][nd]; enqueued on the context's stream
+// peaks [n][5] and, when surf is not null, surf [n][nd]; enqueued on the context's stream.  trips: null, or where the loop's trips go
 int enqueue_sums_peaks(rl_ctx* ctx, const RegGeom& g, const void* ref, int ref_dtype, const long long* a_off, const void* mov, int mov_dtype,
-                       const long long* b_off, size_t n, size_t chunk, double* tot, double* part, double n_terms, double* peaks, double* surf) {
+                       const long long* b_off, size_t n, size_t chunk, double* tot, double* part, double n_terms, double* peaks, double* surf,
+                       int* trips) {
+    if (trips) *trips = 0;
     for (size_t first = 0; first < n; first += chunk) {
+        if (trips) ++*trips;
         const size_t m = std::min(chunk, n - first);
         RegSumArgs a;
         a.a = ref; a.b = mov; a.a_off = a_off + first; a.b_off = b_off + first; a.part = part; a.tot = tot; a.pairs = (int)m; a.g = g;
@@ -49,8 +48,8 @@ int enqueue_sums_peaks(rl_ctx* ctx, const RegGeom& g, const void* ref, int ref_d
     return RL_OK;
 }
 
-size_t sum_chunk(const RegGeom& g, size_t n) {
-    return chunk_under(kRegSumWorkBytes, reg_part_doubles(g) * sizeof(double), n);
+size_t sum_chunk(const rl_ctx* ctx, const RegGeom& g, size_t n) {
+    return chunk_under(ctx->reg_sum_cap, reg_part_doubles(g) * sizeof(double), n);
 }
 }  // namespace
 
@@ -68,7 +67,7 @@ extern "C" int rl_register_sums(rl_ctx* ctx, const void* ref_dev, int ref_dtype,
     HIP_TRY(hipSetDevice(ctx->device));
     const RegGeom g = reg_geom(ny, nx, R, M);
     const size_t per_tot = (size_t)g.nd * kRegFields + 2, per_part = reg_part_doubles(g);
-    const size_t chunk = sum_chunk(g, (size_t)n_pairs);
+    const size_t chunk = sum_chunk(ctx, g, (size_t)n_pairs);
     WorkLayout lay;
     const auto r_a = lay.add<long long>((size_t)n_pairs), r_b = lay.add<long long>((size_t)n_pairs);
     const auto r_tot = lay.add<double>(chunk * per_tot), r_part = lay.add<double>(chunk * per_part);
@@ -80,8 +79,10 @@ extern "C" int rl_register_sums(rl_ctx* ctx, const void* ref_dev, int ref_dtype,
     HIP_TRY(hipMemcpyAsync(a_off, ref_offsets, (size_t)n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(b_off, mov_offsets, (size_t)n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     std::vector<double> host(chunk * per_tot);
+    int& trips = ctx->chunks_run[RL_CHUNK_REGISTER_SUMS] = 0;
     for (size_t first = 0; first < (size_t)n_pairs; first += chunk) {
         const size_t n = std::min(chunk, (size_t)n_pairs - first);
+        ++trips;
         RegSumArgs a;
         a.a = ref_dev; a.b = mov_dev; a.a_off = a_off + first; a.b_off = b_off + first; a.part = part; a.tot = tot; a.pairs = (int)n; a.g = g;
         HIP_TRY(register_sums(ref_dtype, mov_dtype, a, ctx->stream));
@@ -116,7 +117,7 @@ extern "C" int rl_shift_images(rl_ctx* ctx, const void* src_dev, int src_dtype, 
         shift_taps(shifts[2 * (size_t)i + 1], order, nx, table[i].gx, &table[i].ox, &table[i].ntx);
     }
     const int nb = shift_blocks_y(ny) * shift_blocks_x(nx);
-    const size_t chunk = chunk_under(kShiftWorkBytes, n_pix * sizeof(double), (size_t)n);
+    const size_t chunk = chunk_under(ctx->shift_cap, n_pix * sizeof(double), (size_t)n);
     WorkLayout lay;
     const auto r_table = lay.add<ShiftImage>((size_t)n);
     const auto r_stats = lay.add<double>((size_t)n * kShiftFields), r_part = lay.add<double>(chunk * nb * kShiftFields);
@@ -126,7 +127,9 @@ extern "C" int rl_shift_images(rl_ctx* ctx, const void* src_dev, int src_dtype, 
     ShiftImage* table_dev = r_table.at(w);
     double *stats = r_stats.at(w), *part = r_part.at(w), *tmp = r_tmp.at(w);
     HIP_TRY(hipMemcpyAsync(table_dev, table.data(), (size_t)n * sizeof(ShiftImage), hipMemcpyHostToDevice, ctx->stream));
+    int& trips = ctx->chunks_run[RL_CHUNK_SHIFT] = 0;
     for (size_t first = 0; first < (size_t)n; first += chunk) {
+        ++trips;
         ShiftArgs a;
         a.src = (const char*)src_dev + first * n_pix * dtype_size(src_dtype);
         a.dst = (char*)dst_dev + first * n_pix * dtype_size(dst_dtype);
@@ -178,9 +181,9 @@ extern "C" int rl_register_estimate(rl_ctx* ctx, const void* ref_dev, int ref_dt
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t n = (size_t)n_pairs, n_pix = (size_t)ny * nx;
     const RegGeom g = reg_geom(ny, nx, R, M), g1 = reg_geom(ny, nx, 1, M);
-    const size_t chunk = sum_chunk(g, n), chunk1 = sum_chunk(g1, n);
+    const size_t chunk = sum_chunk(ctx, g, n), chunk1 = sum_chunk(ctx, g1, n);
     const size_t per_tot = (size_t)g.nd * kRegFields + 2, per_tot1 = (size_t)g1.nd * kRegFields + 2;
-    const size_t schunk = chunk_under(kShiftWorkBytes, n_pix * sizeof(double), n);
+    const size_t schunk = chunk_under(ctx->shift_cap, n_pix * sizeof(double), n);
     WorkLayout lay;
     const auto r_a = lay.add<long long>(n), r_b = lay.add<long long>(n), r_la = lay.add<long long>(n), r_lb = lay.add<long long>(n);
     const auto r_peaks = lay.add<double>(n * kPeakFields), r_surf = lay.add<double>(surface_out ? n * g.nd : 0);
@@ -199,7 +202,8 @@ extern "C" int rl_register_estimate(rl_ctx* ctx, const void* ref_dev, int ref_dt
     const double n_terms = (double)(((long long)ny - 2LL * M) * ((long long)nx - 2LL * M));
     // stages 1 - 3: sums, peaks, 5 doubles per pair down
     std::vector<double> pk(n * kPeakFields);
-    RL_TRY(enqueue_sums_peaks(ctx, g, ref_dev, ref_dtype, a_off, mov_dev, mov_dtype, b_off, n, chunk, tot, part, n_terms, peaks, surf));
+    RL_TRY(enqueue_sums_peaks(ctx, g, ref_dev, ref_dtype, a_off, mov_dev, mov_dtype, b_off, n, chunk, tot, part, n_terms, peaks, surf,
+                              &ctx->chunks_run[RL_CHUNK_REGISTER_SUMS]));
     HIP_TRY(hipMemcpyAsync(pk.data(), peaks, n * kPeakFields * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (surface_out) HIP_TRY(hipMemcpyAsync(surface_out, surf, n * g.nd * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -227,7 +231,9 @@ extern "C" int rl_register_estimate(rl_ctx* ctx, const void* ref_dev, int ref_dt
             shift_taps(s[1], 3, nx, table[k].gx, &table[k].ox, &table[k].ntx);
         }
         HIP_TRY(hipMemcpyAsync(table_dev, table.data(), L * sizeof(ShiftImage), hipMemcpyHostToDevice, ctx->stream));
+        int& trips = ctx->chunks_run[RL_CHUNK_SHIFT] = 0;
         for (size_t k = 0; k < L;) {            // runs of consecutive moving images, at most schunk at a time
+            ++trips;
             size_t m = 1;
             while (k + m < L && m < schunk && mov_offsets[live[k + m]] == mov_offsets[live[k]] + (int64_t)(m * n_pix)) ++m;
             ShiftArgs a;
@@ -240,7 +246,7 @@ extern "C" int rl_register_estimate(rl_ctx* ctx, const void* ref_dev, int ref_dt
             HIP_TRY(shift_images(mov_dtype, RL_F64, a, tmp, nullptr, ctx->stream));
             k += m;
         }
-        RL_TRY(enqueue_sums_peaks(ctx, g1, ref_dev, ref_dtype, la_off, scratch_dev, RL_F64, lb_off, L, chunk1, tot, part, n_terms, peaks, nullptr));
+        RL_TRY(enqueue_sums_peaks(ctx, g1, ref_dev, ref_dtype, la_off, scratch_dev, RL_F64, lb_off, L, chunk1, tot, part, n_terms, peaks, nullptr, nullptr));
         HIP_TRY(hipMemcpyAsync(pk.data(), peaks, L * kPeakFields * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         for (size_t k = 0; k < L; ++k) reg_estimate_refine(&pk[k * kPeakFields], shifts_out + 2 * live[k], fields_out + 3 * live[k]);
@@ -273,7 +279,7 @@ extern "C" int rl_register_xcorr(rl_ctx* ctx, const void* ref_dev, int ref_dtype
     one.add<cx<float>>(rows_n);
     one.add<float>(corr_n);
     one.add<float>(surf_n);
-    const size_t chunk = chunk_under(kXcorrWorkBytes, one.bytes(), (size_t)n_pairs);
+    const size_t chunk = chunk_under(ctx->xcorr_cap, one.bytes(), (size_t)n_pairs);
     WorkLayout lay;
     const auto r_a = lay.add<long long>((size_t)n_pairs), r_b = lay.add<long long>((size_t)n_pairs);
     const auto r_stats = lay.add<double>(chunk * 4), r_peaks = lay.add<double>(chunk * kXcFields);
@@ -290,8 +296,10 @@ extern "C" int rl_register_xcorr(rl_ctx* ctx, const void* ref_dev, int ref_dtype
     a.tw_y = (const cx<float>*)tw_y; a.tw_x = (const cx<float>*)tw_x;
     HIP_TRY(hipMemcpyAsync(a_off, ref_offsets, (size_t)n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(b_off, mov_offsets, (size_t)n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    int& trips = ctx->chunks_run[RL_CHUNK_XCORR] = 0;
     for (size_t first = 0; first < (size_t)n_pairs; first += chunk) {
         const size_t n = std::min(chunk, (size_t)n_pairs - first);
+        ++trips;
         a.a_off = a_off + first; a.b_off = b_off + first; a.pairs = (int)n;
         HIP_TRY(xcorr_pairs(a, ctx->stream));
         HIP_TRY(hipMemcpyAsync(peaks_out + first * kXcFields, a.peaks, n * kXcFields * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -358,8 +366,10 @@ extern "C" int rl_warp_images(rl_ctx* ctx, const void* src_dev, int src_dtype, i
         for (size_t k = 1; k < chunk; ++k) table[k] = table[0];
         HIP_TRY(hipMemcpyAsync(table_dev, table.data(), chunk * sizeof(ShiftImage), hipMemcpyHostToDevice, ctx->stream));
     }
+    int& trips = ctx->chunks_run[RL_CHUNK_WARP] = 0;
     for (size_t first = 0; first < (size_t)n; first += chunk) {
         const size_t m = std::min(chunk, (size_t)n - first);
+        ++trips;
         const char* src = (const char*)src_dev + first * s_pix * dtype_size(src_dtype);
         if (order == 3) {       // the prefilter alone: along x into tmp, along y into coef
             ShiftArgs f;
@@ -392,7 +402,7 @@ extern "C" int rl_affine_sums(rl_ctx* ctx, const void* ref_dev, int ref_dtype, c
     HIP_TRY(hipSetDevice(ctx->device));
     const AffGeom g = aff_geom(ny, nx, M);
     const size_t per_part = (size_t)g.nb * kAffFields;
-    const size_t chunk = chunk_under(kRegSumWorkBytes, per_part * sizeof(double), (size_t)n_pairs);
+    const size_t chunk = chunk_under(ctx->reg_sum_cap, per_part * sizeof(double), (size_t)n_pairs);
     WorkLayout lay;
     const auto r_a = lay.add<long long>((size_t)n_pairs), r_b = lay.add<long long>((size_t)n_pairs);
     const auto r_tot = lay.add<double>(chunk * kAffFields), r_part = lay.add<double>(chunk * per_part);
@@ -402,8 +412,10 @@ extern "C" int rl_affine_sums(rl_ctx* ctx, const void* ref_dev, int ref_dtype, c
     double *tot = r_tot.at(w), *part = r_part.at(w);
     HIP_TRY(hipMemcpyAsync(a_off, ref_offsets, (size_t)n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(b_off, w_offsets, (size_t)n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    int& trips = ctx->chunks_run[RL_CHUNK_REGISTER_SUMS] = 0;
     for (size_t first = 0; first < (size_t)n_pairs; first += chunk) {
         const size_t n = std::min(chunk, (size_t)n_pairs - first);
+        ++trips;
         AffArgs a;
         a.a = ref_dev; a.w = w_dev; a.a_off = a_off + first; a.w_off = b_off + first; a.part = part; a.tot = tot; a.pairs = (int)n; a.g = g;
         HIP_TRY(affine_sums(ref_dtype, w_dtype, a, ctx->stream));

@@ -11,8 +11,6 @@
 using namespace rl;
 
 namespace {
-// T and F of the pairs in flight (2 * 16 * ny * nx bytes per pair) stay below this; a single pair larger than it runs alone
-constexpr size_t kRingWorkBytes = (size_t)256 << 20;
 constexpr int kRingMaxPairsPerLaunch = 65535;   // grid.z
 constexpr int kRingMaxRings = 4 * kRingMaxN;
 
@@ -87,8 +85,9 @@ int ring_run(rl_ctx* ctx, const void* a_dev, int a_dtype, const int64_t* a_offse
 
     const size_t img = (size_t)ny * nx * sizeof(RingC);
     const size_t per_out = (size_t)n_rings * (n_sectors ? n_sectors : 1) * kRingFields * sizeof(double);
-    int chunk = (int)std::min<size_t>(chunk_under(kRingWorkBytes, 2 * img, (size_t)n_pairs), (size_t)kRingMaxPairsPerLaunch);
-    if (n_sectors) chunk = (int)chunk_under(kRingWorkBytes, per_out, (size_t)chunk);   // the results of a chunk stay under the cap too
+    // T and F of the pairs in flight (2 * 16 * ny * nx bytes per pair) stay below the cap; a single pair larger than it runs alone
+    int chunk = (int)std::min<size_t>(chunk_under(ctx->ring_cap, 2 * img, (size_t)n_pairs), (size_t)kRingMaxPairsPerLaunch);
+    if (n_sectors) chunk = (int)chunk_under(ctx->ring_cap, per_out, (size_t)chunk);   // the results of a chunk stay under the cap too
     WorkLayout lay;
     const auto r_aoff = lay.add<int64_t>((size_t)n_pairs), r_boff = lay.add<int64_t>((size_t)n_pairs);
     const auto r_scale = lay.add<double>((size_t)n_pairs);
@@ -109,8 +108,10 @@ int ring_run(rl_ctx* ctx, const void* a_dev, int a_dtype, const int64_t* a_offse
     HIP_TRY(hipMemcpyAsync(d_aoff, a_offsets, (size_t)n_pairs * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_boff, b_offsets, (size_t)n_pairs * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_scale, b_scale, (size_t)n_pairs * 8, hipMemcpyHostToDevice, ctx->stream));
+    int& trips = ctx->chunks_run[RL_CHUNK_RING] = 0;
     for (int p0 = 0; p0 < n_pairs; p0 += chunk) {
         const int np = std::min(chunk, n_pairs - p0);
+        ++trips;
         HIP_TRY(ring_rows(a_dtype, b_dtype, a_dev, b_dev, d_aoff + p0, d_boff + p0, d_scale + p0, wx, d_t, ny, nx, np, ctx->stream));
         HIP_TRY(ring_cols(d_t, wy, d_f, ny, nx, np, ctx->stream));
         if (n_sectors) HIP_TRY(ring_reduce_sectors(d_f, table.row_ptr, table.bins, d_out, ny, nx, n_rings, n_sectors, np, ctx->stream));

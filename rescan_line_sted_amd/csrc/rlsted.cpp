@@ -1243,6 +1243,15 @@ int rl_ctx_synchronize(rl_ctx* c) {
     return RL_OK;
 }
 
+int rl_chunk_bytes(rl_ctx* c, int which, size_t bytes) {
+    size_t* cap = c ? c->chunk_cap(which) : nullptr;
+    if (!cap || bytes < 1) return fail(RL_ERR_INVALID, "NULL context, an unknown chunk cap or a cap of 0 bytes");
+    *cap = bytes;
+    return RL_OK;
+}
+
+int rl_chunks_run(rl_ctx* c, int which) { return c && which >= 0 && which < RL_CHUNK_COUNT ? c->chunks_run[which] : 0; }
+
 int rl_deconv_destroy(rl_deconv* h) {
     if (!h) return RL_OK;
     (void)hipSetDevice(h->ctx->device);

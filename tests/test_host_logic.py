@@ -221,3 +221,24 @@ def test_default_path_kernels_do_not_spill(tmp_path):
                 assert v == 0, (k, v)          # the split pass with the real multiplier (what the reference's PSFs run)
             elif 'k_rowpair' in k or ('k_rowpass' in k and 'true, float, true' not in k):
                 assert v == 0, (k, v)
+
+
+def test_chunk_cap_codes_and_defaults_are_the_headers(lib):
+    """_lib.CHUNK_CAPS holds the values of the RL_CHUNK_* enum of include/rlsted.h (parsed from the header, RL_CHUNK_COUNT being
+    their number), and _lib.CHUNK_DEFAULTS the initialisers of the context's caps in csrc/ctx.hpp -- what a test that lowers a
+    cap puts back.  Without a device: rl_chunk_bytes refuses a NULL context and rl_chunks_run of one is 0."""
+    text = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'rlsted.h')).read(), flags=re.S)
+    enum = dict((k.lower(), int(v)) for k, v in re.findall(r'\bRL_CHUNK_([A-Z0-9_]+)\s*=\s*(\d+)', text))
+    assert enum.pop('count') == len(enum) == 7 and sorted(enum.values()) == list(range(7))
+    assert lib.CHUNK_CAPS == enum
+    ctx_hpp = open(os.path.join(ROOT, 'rescan_line_sted_amd', 'csrc', 'ctx.hpp')).read()
+    field = {'register_sums': 'reg_sum_cap', 'shift': 'shift_cap', 'xcorr': 'xcorr_cap', 'ring': 'ring_cap', 'fig3': 'fig3_cap',
+             'warp': 'warp_cap', 'beads': 'beads_cap'}
+    assert sorted(field) == sorted(lib.CHUNK_DEFAULTS) == sorted(enum)
+    for which, name in field.items():
+        init, = re.findall(r'size_t %s = ([^;]+);' % name, ctx_hpp)
+        assert re.search(r'case RL_CHUNK_%s: return &%s;' % (which.upper(), name), ctx_hpp), which
+        value = eval(init.replace('(size_t)', '').replace('sizeof(double)', '8'), {'__builtins__': {}})
+        assert lib.CHUNK_DEFAULTS[which] == value, (which, init)
+    assert lib.lib.rl_chunk_bytes(None, 0, 1) == -1 and b'NULL context' in lib.lib.rl_last_error()
+    assert lib.lib.rl_chunks_run(None, 0) == 0
